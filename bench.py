@@ -10,12 +10,25 @@ Nothing is cached across timed steps.  With N > 1 the pool is row-sharded
 
 Default workload (N = 1 and N > 1): BASELINE config 4, the north-star pool
 (2,000,000 x 256 U[0,1) fp32 from numpy default_rng(0), the BASELINE.md pool),
-T = 10, k = 100, E = {0..9}.  Config 2 (100k x 64) runs beside it as the
-``extra.config2`` key.  After timing, the bench checks its own work: the last
-timed step's selection must equal (indices and fp64 scores, bit for bit) the
-selection of the exact separable density path on the same pool.
+T = 10, k = 100, E = {0..9}.
+
+A plain run does only what the headline figure needs: it builds the pool,
+runs the warmup steps, times the --steps steps, writes the last timed step's
+outputs when --dump-outputs DIR is given (DIR/indices.npy and
+DIR/selected_scores.npy, float64: what a caller of the step receives; the
+inputs are seeded, so two builds are compared output for output) and prints
+the headline.  Its roofline entry is the Gram launch as the timed steps'
+HIP events saw it.
+
+With --full the run also measures and checks everything else, as before:
+the configs of --extra beside the headline (config 2 as ``extra.config2``,
+...), the CPU baselines, the accuracy block, the warm and separable paths,
+the per-kernel K2 / K3 rooflines, the forest fit, and the self-checks: the
+last timed step's selection must equal (indices and fp64 scores, bit for
+bit) the selection of the exact separable density path on the same pool.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+                  [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py launches its
@@ -26,10 +39,11 @@ DAL_BENCH_SHARDED=1 with --gpus 1 runs the same step through the sharded path
 N = 1, beside the single-GPU headline.
 
 Output (rank 0): one compact JSON line per extra workload ({"extra": label,
-...}, <= 1 KB each), then the compact headline as the LAST stdout line
-(<= 4 KB: metric, value, roofline, cpu_baseline, self-checks, world size).
-The full result with every note and sub-field goes to --out
-(default gpurun_out/bench_full.json).
+...}, <= 1 KB each; --full only), then the compact headline as the LAST stdout
+line (<= 4 KB: metric, value, ms_per_step, roofline, world size; with --full
+also cpu_baseline and the self-checks).  The full result with every note and
+sub-field goes to --out (default with --full: build/bench_full.json; a plain
+run writes it only when --out names a file).
 """
 from __future__ import annotations
 
@@ -448,6 +462,26 @@ def abs_rowsum_tolerance(x_host, pick, gram_density, n_excluded, m=256, chunk=32
 
 
 _POOLS = {}
+# the headline workload's last timed step, as its caller received it (host
+# numpy arrays by name); --dump-outputs writes them
+LAST_OUTPUTS = {}
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath: str, arrays: dict, max_bytes: int = DUMP_MAX_BYTES):
+    """``dirpath/<name>.npy`` for every array, as float64 (float32 arrays
+    stay float32; row indices are exact in float64).  Arrays that together
+    would pass ``max_bytes`` are cut to a fixed sample each (sorted positions
+    drawn by default_rng(0), the same for every run)."""
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {nm: np.asarray(a) for nm, a in arrays.items()}
+    arrays = {nm: a if a.dtype == np.float32 else a.astype(np.float64) for nm, a in arrays.items()}
+    budget = max_bytes // max(len(arrays), 1)
+    for nm, a in arrays.items():
+        if a.nbytes > budget:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, budget // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(dirpath, f"{nm}.npy"), a)
 
 
 def cached_pool(n, d, dist, lo, hi, dev):
@@ -514,8 +548,12 @@ def time_step_select(state, forest, flags, dens, lut_dev, k: int, beta: float, x
     state.step_select_events.append(ev)
 
 
-def bench_dw(args, config, steps, warmup, warm_steps, world, rank, dev, dist, backend, cpu=True, cfg=None):
+def bench_dw(args, config, steps, warmup, warm_steps, world, rank, dev, dist, backend, cpu=True, cfg=None,
+             full=True, main=False):
     """Density-weighted selection on one config; returns the JSON dict.
+
+    full=False (a plain run): setup, warmup and the timed steps only.
+    main=True: the headline workload, whose last outputs --dump-outputs writes.
 
     The step runs through the sharded path (dal/parallel.py) when world > 1,
     or at world 1 when DAL_BENCH_SHARDED=1 (an RCCL group of one rank: the
@@ -579,39 +617,54 @@ def bench_dw(args, config, steps, warmup, warm_steps, world, rank, dev, dist, ba
         g_max, ag_max = _max_over_ranks([gram_ms, ag_ms], world, dist, tdev)
         ranks = {"gram_ms_max": g_max, "gram_ms_min": gram_min, "all_gather_ms_max": ag_max}
     elapsed, gram_ms_max = _max_over_ranks([elapsed, gram_ms], world, dist, tdev)
+    if main:  # what a caller of the last timed step received (--dump-outputs)
+        LAST_OUTPUTS.clear()
+        LAST_OUTPUTS.update(indices=idx_g.cpu().numpy(), selected_scores=sc_g.cpu().numpy())
 
-    # accuracy (outside the timed region): the timed step's
-    # Gram density on sampled rows vs an fp64 host restatement
-    s_host = host_colsum64(x_host, lo, N_EXCLUDED)
-    if world > 1:
-        t = torch.from_numpy(s_host).to(tdev)
-        dist.all_reduce(t)
-        s_host = t.cpu().numpy()
-    dens_gram = state.density("gram")
-    acc_max, acc_mean, dref_min, abs_max, n_acc = density_accuracy(
-        x_host, lo, lambda pick: dens_gram[torch.from_numpy(pick).to(dev)].cpu().numpy(), s_host, N_EXCLUDED)
-    tol_abs = None
-    if world == 1 and cfg["dist"] == "normal" and n * d <= 20_000_000:  # signed data (config 3)
-        tol_abs = abs_rowsum_tolerance(x_host, sample_rows(n, 0, N_EXCLUDED, 4096),
-                                       lambda pick: dens_gram[torch.from_numpy(pick).to(dev)].cpu().numpy(),
-                                       N_EXCLUDED)
-    del dens_gram
-    err_bound = float(engine.density_error(state))
-    n_cols = n - N_EXCLUDED
-    acc_max, acc_mean_max, bound_rel, abs_ncols = _max_over_ranks(
-        [acc_max, acc_mean, err_bound / dref_min, abs_max / n_cols], world, dist, tdev)
+    accuracy = None
+    if full:
+        # accuracy (outside the timed region): the timed step's
+        # Gram density on sampled rows vs an fp64 host restatement
+        s_host = host_colsum64(x_host, lo, N_EXCLUDED)
+        if world > 1:
+            t = torch.from_numpy(s_host).to(tdev)
+            dist.all_reduce(t)
+            s_host = t.cpu().numpy()
+        dens_gram = state.density("gram")
+        acc_max, acc_mean, dref_min, abs_max, n_acc = density_accuracy(
+            x_host, lo, lambda pick: dens_gram[torch.from_numpy(pick).to(dev)].cpu().numpy(), s_host, N_EXCLUDED)
+        tol_abs = None
+        if world == 1 and cfg["dist"] == "normal" and n * d <= 20_000_000:  # signed data (config 3)
+            tol_abs = abs_rowsum_tolerance(x_host, sample_rows(n, 0, N_EXCLUDED, 4096),
+                                           lambda pick: dens_gram[torch.from_numpy(pick).to(dev)].cpu().numpy(),
+                                           N_EXCLUDED)
+        del dens_gram
+        err_bound = float(engine.density_error(state))
+        n_cols = n - N_EXCLUDED
+        acc_max, acc_mean_max, bound_rel, abs_ncols = _max_over_ranks(
+            [acc_max, acc_mean, err_bound / dref_min, abs_max / n_cols], world, dist, tdev)
+        accuracy = {"density_max_rel_err": acc_max, "density_mean_rel_err": acc_mean_max,
+                    "density_max_abs_err_over_ncols": abs_ncols,
+                    "density_err_bound_over_ncols": err_bound / n_cols,
+                    "density_max_err_over_abs_rowsum": tol_abs,
+                    "sampled_rows_per_rank": n_acc,
+                    "density_err_bound_rel": bound_rel}
 
     # self-check (outside the timed region): the timed step's selection equals
     # the exact separable-density selection, indices and fp64 score bits
-    idx_s, sc_s = step("separable")
-    same = bool(torch.equal(idx_g, idx_s)) and bool(torch.equal(sc_g.view(torch.int64), sc_s.view(torch.int64)))
-    if not same:
-        raise SystemExit(f"bench self-check FAILED: gram-mode selection != separable-mode selection "
-                         f"({idx_g[:8].tolist()} vs {idx_s[:8].tolist()})")
+    same = None
+    if full:
+        idx_s, sc_s = step("separable")
+        same = bool(torch.equal(idx_g, idx_s)) and bool(torch.equal(sc_g.view(torch.int64), sc_s.view(torch.int64)))
+        if not same:
+            raise SystemExit(f"bench self-check FAILED: gram-mode selection != separable-mode selection "
+                             f"({idx_g[:8].tolist()} vs {idx_s[:8].tolist()})")
 
     # warm path: density cached (the reference's density is constant per pool)
     warm_ms = forest_ms = select_ms = step_select_ms = forest_used = None
     warm_same = None
+    if not full:
+        warm_steps = 0  # (the warm, separable and per-kernel K2 / K3 runs are --full's)
     if warm_steps > 0:
         step()
         # per-kernel HIP-event timing of K2 / K3 (eager launches, events on the launch stream)
@@ -654,12 +707,24 @@ def bench_dw(args, config, steps, warmup, warm_steps, world, rank, dev, dist, ba
 
     # k-th boundary gap: the (k+1)-best score from the exact path, beside the
     # observed Gram error (the exact re-rank makes the selection independent of it)
-    if sharded:
-        _, sc_k1 = parallel.select(sel, comm, unl, forest, k + 1, mode="dw", density_mode="separable")
-    else:
-        sc_k1 = engine.density_step(state, unl, forest, k + 1, mode="separable").selected_scores
-    sk = sc_k1.cpu().numpy()
-    gap_rel = float((sk[k - 1] - sk[k]) / abs(sk[k - 1])) if len(sk) > k and sk[k - 1] != 0 else None
+    if full:
+        if sharded:
+            _, sc_k1 = parallel.select(sel, comm, unl, forest, k + 1, mode="dw", density_mode="separable")
+        else:
+            sc_k1 = engine.density_step(state, unl, forest, k + 1, mode="separable").selected_scores
+        sk = sc_k1.cpu().numpy()
+        gap_rel = float((sk[k - 1] - sk[k]) / abs(sk[k - 1])) if len(sk) > k and sk[k - 1] != 0 else None
+        accuracy.update(
+            kth_gap_rel=gap_rel,
+            note="Gram-path density (MFMA, fixed point) of evenly spaced sampled rows vs "
+                 "<u_i, sum_j u_j> in fp64 numpy on the host (max over ranks); *_over_ncols: "
+                 "absolute errors / (N - |E|) >= sum_j |S_ij| / (N - |E|) scale, the form "
+                 "for signed data; *_over_abs_rowsum: |dd_i| / sum_j |S_ij| on 256 of the "
+                 "sampled rows (SURVEY config-3 tolerance 1e-5; signed one-GPU pools); "
+                 "the bound is the rigorous interval "
+                 "half-width; "
+                 "kth_gap_rel = (s_k - s_k+1) / |s_k| of the exact scores (the selection "
+                 "itself is exact: interval keys + fp64 re-rank)")
 
     # roofline of the dominant kernel (density Gram row-sum), this rank's launch
     rows_local = (hi - lo) - int(np.sum((excluded >= lo) & (excluded < hi)))
@@ -692,26 +757,12 @@ def bench_dw(args, config, steps, warmup, warm_steps, world, rank, dev, dist, ba
                       else "per-rank dal_dw_plan replay -> packed all-gather -> one-launch merge, one status read"
                       if sharded and state.use_graphs else "eager launches"),
         "warm_rows_per_s": (n_scored / (warm_ms * 1e-3)) if warm_ms else None,
-        "self_check": {"gram_selection_equals_separable_selection": same,
-                       "warm_selection_equals_cold_selection": warm_same, "k": k,
-                       "note": "last timed step vs the exact O(N*D) density path, and the last warm step "
-                               "vs the cold one: indices + fp64 score bits"},
-        "accuracy": {"density_max_rel_err": acc_max, "density_mean_rel_err": acc_mean_max,
-                     "density_max_abs_err_over_ncols": abs_ncols,
-                     "density_err_bound_over_ncols": err_bound / n_cols,
-                     "density_max_err_over_abs_rowsum": tol_abs,
-                     "sampled_rows_per_rank": n_acc,
-                     "density_err_bound_rel": bound_rel,
-                     "kth_gap_rel": gap_rel,
-                     "note": "Gram-path density (MFMA, fixed point) of evenly spaced sampled rows vs "
-                             "<u_i, sum_j u_j> in fp64 numpy on the host (max over ranks); *_over_ncols: "
-                             "absolute errors / (N - |E|) >= sum_j |S_ij| / (N - |E|) scale, the form "
-                             "for signed data; *_over_abs_rowsum: |dd_i| / sum_j |S_ij| on 256 of the "
-                             "sampled rows (SURVEY config-3 tolerance 1e-5; signed one-GPU pools); "
-                             "the bound is the rigorous interval "
-                             "half-width; "
-                             "kth_gap_rel = (s_k - s_k+1) / |s_k| of the exact scores (the selection "
-                             "itself is exact: interval keys + fp64 re-rank)"},
+        "full": bool(full),
+        "self_check": ({"gram_selection_equals_separable_selection": same,
+                        "warm_selection_equals_cold_selection": warm_same, "k": k,
+                        "note": "last timed step vs the exact O(N*D) density path, and the last warm step "
+                                "vs the cold one: indices + fp64 score bits"} if full else None),
+        "accuracy": accuracy,
         "separable": ({"cold_selection_latency_ms": sep_ms, "rows_per_s": n_scored / (sep_ms * 1e-3),
                        "note": "density via the exact O(N*D) identity sum_j<u_i,u_j> = <u_i, sum_j u_j> "
                                "(canonical fp64, same selection); HBM-bound, not the MFMA path"}
@@ -725,7 +776,7 @@ def bench_dw(args, config, steps, warmup, warm_steps, world, rank, dev, dist, ba
         "cpu_baseline": None,
         "ranks": ranks,
     }
-    if rank == 0 and world == 1 and cpu and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and cpu and not args.no_cpu_baseline:
         from oracle import dal_oracle as O
 
         of = O.synthetic_forest(cfg["trees"], cfg["depth"], d, seed=1, dist=cfg["dist"])
@@ -781,9 +832,11 @@ def div_self_check(x_dev, lab_host64, lo, m, idx, sc, k, n_sample=4096):
             "note": "host numpy fp64 restatement (sequential norms and dots) on the bf16 values"}
 
 
-def bench_div(args, steps, warmup, world, rank, dev, dist, backend, cpu=12.0):
+def bench_div(args, steps, warmup, world, rank, dev, dist, backend, cpu=12.0, full=True, main=False):
     """Config 5: one step = max-cosine of every pool row to the labeled set
-    (bf16 MFMA, fp32 accumulate) + exact top-k of the least similar rows."""
+    (bf16 MFMA, fp32 accumulate) + exact top-k of the least similar rows.
+    full=False (a plain run): no host self-check, kernel-only timing or CPU
+    baseline; main=True: see bench_dw."""
     import torch
 
     from dal import _lib, parallel
@@ -814,38 +867,53 @@ def bench_div(args, steps, warmup, world, rank, dev, dist, backend, cpu=12.0):
     for _ in range(warmup):
         step()
     elapsed, (sel_idx, sel_sc) = _timed(step, steps, barrier)
+    if main:  # what a caller of the last timed step received (--dump-outputs)
+        LAST_OUTPUTS.clear()
+        LAST_OUTPUTS.update(indices=sel_idx.cpu().numpy(), selected_scores=sel_sc.cpu().numpy())
     check = div_self_check(x, upload(lab_host, dev).to(torch.bfloat16).float().cpu().numpy().astype(np.float64),
-                           lo, m, sel_idx, sel_sc, k) if world == 1 else None
+                           lo, m, sel_idx, sel_sc, k) if world == 1 and full else None
     if check is not None and not (check["selected_scores_equal_canonical_fp64"] and check["selection_sorted"]
                                   and check["no_sampled_row_beats_kth"]):
         raise SystemExit(f"bench self-check FAILED (config 5): {check}")
-    # kernel-only timing of the max-cosine launch on this rank
-    L = LabeledSet(lab, dev)
-    st = torch.zeros(1, dtype=torch.int32, device=dev)
-    out = torch.empty(hi - lo, dtype=torch.float32, device=dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
-    def launch():
-        _lib.call("dal_max_cosine_unit", _ptr(x), hi - lo, d, _ptr(L.unit16), L.m_pad, _ptr(out), _ptr(st),
-                  _stream(dev))
+    def kernel_ms():
+        """Kernel-only timing of the max-cosine launch on this rank."""
+        L = LabeledSet(lab, dev)
+        st = torch.zeros(1, dtype=torch.int32, device=dev)
+        out = torch.empty(hi - lo, dtype=torch.float32, device=dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
-    # back-to-back launches between two events (an event pair around each
-    # launch also times the host's submission of that launch), after 30
-    # untimed ones: the host-side self-check leaves the GPU idle and its clock
-    # takes tens of milliseconds to ramp back (first 5-launch window 1.69 ms
-    # vs 1.42-1.44 ms held, scripts/maxcos_window_probe.py)
-    reps = 20
-    for _ in range(30):
-        launch()
-    e0.record()
-    for _ in range(reps):
-        launch()
-    e1.record()
-    torch.cuda.synchronize()
-    kms = e0.elapsed_time(e1) / reps
-    elapsed, _ = _max_over_ranks([elapsed, kms], world, dist, tdev)
+        def launch():
+            _lib.call("dal_max_cosine_unit", _ptr(x), hi - lo, d, _ptr(L.unit16), L.m_pad, _ptr(out), _ptr(st),
+                      _stream(dev))
+
+        # back-to-back launches between two events (an event pair around each
+        # launch also times the host's submission of that launch), after 30
+        # untimed ones: the host-side self-check leaves the GPU idle and its clock
+        # takes tens of milliseconds to ramp back (first 5-launch window 1.69 ms
+        # vs 1.42-1.44 ms held, scripts/maxcos_window_probe.py)
+        reps = 20
+        for _ in range(30):
+            launch()
+        e0.record()
+        for _ in range(reps):
+            launch()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    kms = kernel_ms() if full else None
+    (elapsed,) = _max_over_ranks([elapsed], world, dist, tdev)
     flops = 2.0 * (hi - lo) * m * d
-    achieved = flops / (kms * 1e-3) / 1e12
+    achieved = flops / (kms * 1e-3) / 1e12 if kms else None
+    roofline = None
+    if full:
+        roofline = {"bound": "mfma", "kernel": "dal_max_cosine_unit (bf16 pool rows power-of-two scaled to fp16 in registers, folded fp16 unit labeled rows; v_mfma_f32_16x16x32_f16, max-only epilogue)",
+                    "achieved": achieved, "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": achieved / BF16_MFMA_PEAK_TFLOPS,
+                    "traffic": _traffic("5", "maxcos_bytes_per_launch", world), "launch_ms": kms,
+                    "algorithmic_flops_per_launch": flops, "pool_bytes_per_launch": (hi - lo) * d * 2,
+                    "hbm_frac_of_8TBs": (hi - lo) * d * 2 / (kms * 1e-3) / 8e12}
     res = {
         "metric": "pool rows scored/sec (diversity: max-cosine to labeled set + exact top-k)",
         "value": (n - m) * steps / elapsed, "unit": "rows/s", "n_gpus": world, "steps": steps,
@@ -855,16 +923,12 @@ def bench_div(args, steps, warmup, world, rank, dev, dist, backend, cpu=12.0):
         "data": DATA_NOTE,
         "config": {"workload": cfg["workload"], "pool_rows": n, "features": d, "labeled": m, "k": k,
                    "parallelism": f"row-shard dp{world}" if sharded else "single GPU"},
-        "roofline": {"bound": "mfma", "kernel": "dal_max_cosine_unit (bf16 pool rows power-of-two scaled to fp16 in registers, folded fp16 unit labeled rows; v_mfma_f32_16x16x32_f16, max-only epilogue)",
-                     "achieved": achieved, "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved / BF16_MFMA_PEAK_TFLOPS,
-                     "traffic": _traffic("5", "maxcos_bytes_per_launch", world), "launch_ms": kms,
-                     "algorithmic_flops_per_launch": flops, "pool_bytes_per_launch": (hi - lo) * d * 2,
-                     "hbm_frac_of_8TBs": (hi - lo) * d * 2 / (kms * 1e-3) / 8e12},
+        "full": bool(full),
+        "roofline": roofline,
         "self_check": check,
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and cpu and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and cpu and not args.no_cpu_baseline:
         xs = x[: 300_000].float().cpu().numpy()  # the bf16 values the GPU scores, as fp32
         res["cpu_baseline"] = cpu_baseline_div(xs, m, k, n, budget_s=float(cpu))
     return res
@@ -940,7 +1004,7 @@ def headline(out: dict) -> dict:
     cfg = out.get("config") or {}
     h["config"] = {k: cfg[k] for k in ("workload", "pool_rows", "features", "trees", "k", "labeled",
                                        "parallelism") if k in cfg}
-    for k in ("world_size", "backend", "sharded_path"):
+    for k in ("world_size", "backend", "sharded_path", "full"):
         h[k] = out.get(k)
     h["value"], h["ms_per_step"] = _r(out.get("value"), 6), _r(out.get("ms_per_step"), 6)
     h["warm_selection_latency_ms"] = _r(out.get("warm_selection_latency_ms"))
@@ -1096,15 +1160,26 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: config 4: 5, else 50)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps (default: config 4: 1, else 10)")
     ap.add_argument("--config", default="4", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the --extra configs, CPU baselines, "
+                         "accuracy block, self-checks, warm / separable paths, K2 / K3 rooflines, the forest fit")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (what its caller receives) as DIR/<name>.npy")
     ap.add_argument("--extra", default=None,
-                    help="comma list of extra configs reported under 'extra' (default: '2' with config 4)")
+                    help="with --full: comma list of extra configs reported under 'extra' "
+                         f"(default with config 4: {DEFAULT_EXTRA})")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--warm-steps", type=int, default=None)
+    ap.add_argument("--warm-steps", type=int, default=None, help="with --full: steps of the warm / separable runs")
     ap.add_argument("--trees", type=int, default=None, help="override the config's forest size (config 4: T=100)")
     ap.add_argument("--k", type=int, default=None, help="override the config's selection size (config 4: k=1000)")
-    ap.add_argument("--out", default=os.path.join(REPO, "gpurun_out", "bench_full.json"),
-                    help="file for the full result (every note and sub-field); '' to skip")
+    ap.add_argument("--out", default=None,
+                    help="file for the full result (every note and sub-field); '' to skip "
+                         "(default: build/bench_full.json with --full, none without)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, "build", "bench_full.json") if args.full else ""
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     main_cfg = resolve(f"{args.config}" + (f":T{args.trees}" if args.trees is not None else "")
                        + (f":k{args.k}" if args.k is not None else ""))[1]
     big = args.config in ("4",)
@@ -1113,7 +1188,7 @@ def main():
     warm_steps = args.warm_steps if args.warm_steps is not None else (5 if big else 20)
     extra = args.extra if args.extra is not None else (DEFAULT_EXTRA if args.config == "4" and
                                                         args.trees is None and args.k is None else "")
-    extra = [c for c in extra.split(",") if c and c != "none"]
+    extra = [c for c in extra.split(",") if c and c != "none"] if args.full else []
 
     import torch
     import torch.distributed as dist
@@ -1140,9 +1215,12 @@ def main():
             dist.init_process_group(backend, rank=rank, world_size=world)
 
     if main_cfg.get("mode") == "div":
-        out = bench_div(args, steps, warmup, world, rank, dev, dist, backend)
+        out = bench_div(args, steps, warmup, world, rank, dev, dist, backend, full=args.full, main=True)
     else:
-        out = bench_dw(args, args.config, steps, warmup, warm_steps, world, rank, dev, dist, backend, cfg=main_cfg)
+        out = bench_dw(args, args.config, steps, warmup, warm_steps, world, rank, dev, dist, backend, cfg=main_cfg,
+                       full=args.full, main=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, LAST_OUTPUTS)
     if extra:
         out["extra"] = {}
         for spec in extra:
@@ -1166,7 +1244,7 @@ def main():
             if variant:
                 out["extra"][label]["cpu_baseline_note"] = ("the host cost of this variant is the headline "
                                                             "line's O(N^2) Gram row-sum (cpu_baseline above)")
-    if world == 1 and CONFIGS[args.config].get("mode") != "div":
+    if args.full and world == 1 and CONFIGS[args.config].get("mode") != "div":
         out.setdefault("extra", {})["rf_train"] = bench_rf_train(dev)
     out["world_size"] = dist.get_world_size() if world > 1 or SHARDED else 1
     out["backend"] = dist.get_backend() if world > 1 or SHARDED else None

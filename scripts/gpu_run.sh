@@ -20,6 +20,9 @@
 #   pmcpy=TAG=CTRS=SCRIPT[=ARGS]  rocprofv3 --pmc CTRS of python SCRIPT ARGS -> gpurun_out/pmc_TAG/
 #   py=SCRIPT[=ARGS]      python SCRIPT ARGS                  -> gpurun_out/py_<n>.log
 #   trace=TAG=SCRIPT[=ARGS]  rocprofv3 --kernel-trace of python SCRIPT ARGS -> gpurun_out/trace_TAG/
+#
+# bench.py ARGS: a plain run times the headline steps only; add --full for the extra configs, the
+# CPU baselines, the self-checks and the warm / K2 / K3 figures (what the records in profiles/ hold).
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out

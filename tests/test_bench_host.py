@@ -119,6 +119,23 @@ def test_div_self_check_canonical_numpy():
     assert np.array_equal(got, ref[50:])
 
 
+def test_dump_outputs_float_arrays_and_fixed_sample(tmp_path):
+    """--dump-outputs: one float .npy per output (indices exact in float64);
+    arrays past the byte budget are cut to the same sorted sample every run."""
+    idx = np.array([2**40 + 1, 7, 1_999_999], dtype=np.int64)
+    sc = np.array([0.1, -2.5, 3.0])
+    bench.dump_outputs(str(tmp_path / "a"), {"indices": idx, "selected_scores": sc})
+    got = np.load(tmp_path / "a" / "indices.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.int64), idx)
+    assert np.array_equal(np.load(tmp_path / "a" / "selected_scores.npy"), sc)
+    big = np.arange(1000, dtype=np.float32)
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), {"big": big, "small": sc}, max_bytes=800)
+    b, c = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+    assert b.dtype == np.float32 and b.nbytes <= 400 and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and np.array_equal(np.load(tmp_path / "b" / "small.npy"), sc)
+
+
 def _canned_result():
     """The full result of a real default run (round 3, config 4 + extras)."""
     import json

@@ -144,7 +144,7 @@ def test_bench_self_launch_two_ranks_gloo(cuda, tmp_path):
     env = dict(os.environ, DAL_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--config", "2", "--steps", "3",
-                        "--warmup", "1", "--warm-steps", "2", "--no-cpu-baseline", "--extra", "none",
+                        "--warmup", "1", "--full", "--warm-steps", "2", "--no-cpu-baseline", "--extra", "none",
                         "--out", str(tmp_path / "full.json")],
                        env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
