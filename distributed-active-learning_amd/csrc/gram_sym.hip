@@ -17,22 +17,25 @@
 // the sharding).  The taker's rows are the A operand (register resident), Q's
 // the B operand (LDS-staged); the kernel keeps the tile's ROW sums (-> P's
 // rows).  The tile's column sums (-> Q's rows) are linear in P's rows,
-// sum_{i in P} <H_i, u~_j> = <sigma^H_P, u~_j>, so they are added in closed
+// sum_{i in P} <H_i, H_j> = <sigma^H_P, H_j>, so they are added in closed
 // form with the residual below (round 5; before, as sigma_P MFMAs and int64
 // column flushes per pair).
 //
-// Compensation and column sums.  The A side holds H only: the MFMAs form
-// T_ij = <H_i, u~_j> (two products per feature pair, H.H and H.L).  For a row
-// r of super block B, dal_gram_sym_residual adds in closed form
-//   row role (B takes Q):          sum_Q <L_r, sigma~_Q>   = <L_r, R_B>
-//   column role (P takes B, P!=B): sum_P <u~_r, sigma~_P>  = <u~_r, C_B>
-// (the column role: the pair's column sums <sigma^H_P, u~_r> plus the
-// remainder <sigma^L_P, u~_r>) with sigma~_Q the sum of u~ over Q's rows
-// (exact int64 in units of 2^-24) and R_B, C_B its sums over B's partners
-// (parity-class prefix sums).  d_i is then sum_j <u~_i, u~_j> with nothing
-// dropped; the MFMA work per algorithmic product is 2 fp16 products on half
-// the pairs, and each row's density is written only by its own rows' launches
-// (no cross-GPU sum).
+// Compensation and column sums.  Both MFMA operands hold H only: the MFMAs
+// form the fp16 Gram T_ij = <H_i, H_j> on the taken pairs, one product per
+// feature pair.  Every other term of <u~_i, u~_j> is linear in the columns and
+// is added exactly, in closed form, by dal_gram_sym_residual (the L.u~ terms
+// since round 3, the column sums since round 5, the H.L terms -- a second MFMA
+// per 32 features before -- since round 7).  With sigma^H_Q the sum of H over
+// super block Q, S^L the sum of L and S~ the sum of u~ over every row (exact
+// int64 in units of 2^-24), a row r of super block B receives
+//   <L_r, S~> + <H_r, S^L + CH_B>,  CH_B = sum of sigma^H_P over P != B taking B
+// (a parity-class prefix sum): <L_r, S~> is every L_r term, <H_r, S^L> every
+// H_r.L_j term, <H_r, CH_B> the H.H column sums of the pairs other super
+// blocks took.  d_i is then sum_j <u~_i, u~_j> with nothing dropped; the MFMA
+// work per algorithmic product is one fp16 product on half the pairs, and
+// each row's density is written only by its own rows' launches (no cross-GPU
+// sum).
 //
 // Exactness of the row sums (as the earlier kernels): chains are folded to
 // multiples of 2^-32 and added as integers (LDS fp64 below 2^53, int64
@@ -45,8 +48,9 @@
 // stages in a 2-deep LDS ring filled by global_load_lds_dwordx4 (source-side
 // XOR swizzle -> conflict-free ds_read_b128).  One accumulator chain per 16-row
 // tile carries its row sums through the MFMAs and is folded to the LDS row
-// accumulator every FOLD columns.  KS = 128 for d_pad % 128 == 0 (the H-only A
-// side frees the registers the L fragments held), else 64, or 32.
+// accumulator every FOLD columns.  A stage holds the H run of each column's
+// slice (the L run is not read here).  KS = 128 for d_pad % 128 == 0 (the
+// H-only A side frees the registers the L fragments held), else 64, or 32.
 #include <stdlib.h>
 
 #include <utility>
@@ -149,19 +153,34 @@ struct Cfg {
   static constexpr int WAVES = W;                   // 4: one super block per block; 8: two (P, P + 2)
   static constexpr int HALVES = W / 4;              // super blocks per block
   static constexpr int NT = 64 * W;                 // threads
-  static constexpr int ROWB = KS * 4;               // bytes per operand row of a slice (H + L)
-  static constexpr int SLOTS = ROWB / 16;           // 16-B slots per row
-  static constexpr int HI = KS / 8;                 // slots of the H part
+  static constexpr int ROWB = KS * 2;               // bytes per staged operand row of a slice (its H run)
+  static constexpr int SLOTS = ROWB / 16;           // 16-B slots per row: 4 / 8 / 16
   // three 4-wave blocks per CU at KS 64 (OCC3): 16 KiB stages so three fit the LDS
   static constexpr int OCC = W == 8 ? (KS == 64 ? DAL_GRAM_W8_OCC64 : 1)
                                     : KS == 32 ? DAL_GRAM_KS32_OCC : KS == 64 ? DAL_GRAM_KS64_OCC : 2;
   static constexpr int STAGE = W == 8 ? DAL_GRAM_STAGE8 : OCC >= 4 ? 8192 : OCC == 3 ? 16384 : 32768;  // bytes per LDS stage
   static constexpr int SC = STAGE / ROWB;           // columns per stage: 64 / 128 / 256
   static constexpr int SPP = 256 / SC;              // stages per 512 x 256 pair: 4 / 2 / 1
+  static_assert(SC >= 16 && SC <= 256, "a stage holds 16 to 256 whole columns");
   static constexpr int FOLD = KS == 128 ? DAL_GRAM_FOLD128 : DAL_GRAM_FOLD64;  // columns per row fold
   static constexpr int SPF = FOLD / SC;             // stages per fold group
   static constexpr int F4 = STAGE / 16;
-  static constexpr int SWZ = (SLOTS < 16 ? SLOTS : 16) - 1;
+  static constexpr int SWZ = SLOTS - 1;
+  // LDS image of a stage: slot s of stage row R sits at position s ^ swz(R) of
+  // the row.  ds_read_b128 serves four groups of 16 lanes, each holding every
+  // column row li = 0..15 once, li in {0-3, 12-15} at one lane group lq and li
+  // in {4-11} at lq ^ 1; its 64 banks are 16 slots (256 B).
+  //  16 slots per row (KS 128): one row per 256 B; slot ^ li is a permutation.
+  //   8 slots (KS 64): two rows per 256 B; slot ^ (li & 7) -- li and li ^ 8
+  //     share li & 7 but read lq and lq ^ 1 (two positions); li and li ^ 9 read
+  //     one position, on rows of different parity (the two halves of the 256 B).
+  //   4 slots (KS 32): four rows per 256 B, the rows li, li ^ 4, li ^ 8, li ^ 12
+  //     share the quarter: slot ^ g(li >> 2), g = 0, 3, 2, 1, gives them lq, lq
+  //     ^ 1 ^ 3, lq ^ 1 ^ 2, lq ^ 1 -- four different slots.
+  static constexpr int swz(int row) {
+    return SLOTS >= 8 ? row & SWZ : ((row >> 2) & 3) ^ (((row >> 2) & 1) << 1);
+  }
+  static_assert(SLOTS == 4 || SLOTS == 8 || SLOTS == 16, "swizzles for 4, 8 and 16 slots per row");
   static constexpr int PIECES = STAGE / (W * 1024);  // 1-KiB DMA pieces per wave per stage
   static constexpr int RT = 8;                      // 16-row tiles per wave (128 rows)
   static constexpr int LG = 4;
@@ -171,19 +190,24 @@ struct Cfg {
   // chain length -- a tighter density bound -- for 32 more VGPRs)
   static constexpr int NCH = KS == 128 ? DAL_GRAM_NCH128 : 1;
   // products summed by one row-chain element between two folds (the FOLD
-  // columns' tiles over NCH chains, 2 KS products per tile): the length
-  // dal_density_error_bound_sym_d charges the row side with
-  static constexpr int CHAIN = FOLD / 16 / NCH * 2 * KS;
+  // columns' tiles over NCH chains, KS products per tile: 512 at KS 32, 1,024
+  // at KS 64 and 128)
+  static constexpr int CHAIN = FOLD / 16 / NCH * KS;
+  // ... and the length dal_density_error_bound_sym_d charges the row side with:
+  // that of the two-product body (H.H and H.L) these kernels had before, twice
+  // CHAIN at the default folds.  The bound's values are part of the interface
+  // (pinned by the tests), so it keeps them and over-charges.
+  static constexpr int CHARGED = KS == 32 ? DAL_GRAM_CHAIN_MAX / 2 : DAL_GRAM_CHAIN_MAX;
   static_assert(SPF >= 1 && SPP % SPF == 0 && PIECES >= 1 && NKS >= 1, "bad slice");
   static_assert(W == 4 || (W == 8 && KS >= 64), "two super blocks per block: KS >= 64 only");
-  static_assert(CHAIN <= DAL_GRAM_CHAIN_MAX, "row chain longer than the density bound's worst case");
+  static_assert(CHAIN <= CHARGED, "row chain longer than the density bound charges");
 };
 // the 8-wave form folds like the 4-wave one (one bound per KS)
-static_assert(Cfg<128, 8>::CHAIN == Cfg<128, 4>::CHAIN, "block forms must share the chain length");
+static_assert(Cfg<128, 8>::CHAIN <= Cfg<128, 4>::CHARGED, "block forms share one bound");
 
 // Row sums of the taken pairs (the column sums of every pair are added in
 // closed form by dal_gram_sym_residual, see the header): for each pair (P,
-// J) the taker's rows accumulate <H_i, u~_j> over J's 256 columns.
+// J) the taker's rows accumulate <H_i, H_j> over J's 256 columns.
 template <int KS, int W>
 __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
     const uint16_t* __restrict__ urows, int srow0, int n_srb,
@@ -269,12 +293,15 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
 
   // DMA source offsets.  Piece q of wave w covers stage rows
   // Wr + q * RPP + lane / SLOTS (Wr = w * PIECES * RPP, RPP = 64 / SLOTS rows
-  // per piece), slot (lane % SLOTS) ^ (row & SWZ).  Wr (a multiple of
-  // PIECES * RPP), q * RPP and lane / SLOTS occupy disjoint bits, so row & SWZ
-  // = ((Wr + lane / SLOTS) & SWZ) ^ ((q * RPP) & SWZ): the offset is a per-lane
-  // value XOR a per-piece constant (bits 4.. of the byte offset, below the row
-  // part) plus the piece's row offset.
+  // per piece), slot (lane % SLOTS) ^ swz(row).  Wr (a multiple of
+  // PIECES * RPP), q * RPP and lane / SLOTS occupy disjoint bits, so at 8 and
+  // 16 slots swz(row) = row & SWZ = swz(Wr + lane / SLOTS) ^ swz(q * RPP): the
+  // offset is a per-lane value XOR a per-piece constant (bits 4.. of the byte
+  // offset, below the row part) plus the piece's row offset.  At 4 slots a
+  // piece is 16 rows and swz reads row bits 2-3 only: all in lane / SLOTS, the
+  // per-piece constant is 0.
   constexpr int RPP = 64 / C::SLOTS;
+  static_assert((RPP & (RPP - 1)) == 0 && (C::PIECES & (C::PIECES - 1)) == 0, "row parts must occupy disjoint bits");
   const unsigned rowbytes = static_cast<unsigned>(ldh * 2);
   const unsigned dst0 = __builtin_amdgcn_readfirstlane(
       static_cast<unsigned>(reinterpret_cast<uintptr_t>((AS3 float4*)(lds + wave * C::PIECES * 64))));
@@ -285,11 +312,11 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
         ucols + (static_cast<int64_t>(J - jcol0) * 256 + h * C::SC) * ldh + slice_off);
     const unsigned fl = fresh_lane();
     const unsigned lrow = fl / C::SLOTS + static_cast<unsigned>(wave * C::PIECES * RPP);
-    const unsigned vlane = lrow * rowbytes + (((fl % C::SLOTS) ^ (lrow & C::SWZ)) << 4);
+    const unsigned vlane = lrow * rowbytes + (((fl % C::SLOTS) ^ static_cast<unsigned>(C::swz(lrow))) << 4);
 #pragma unroll
     for (int q = 0; q < C::PIECES; ++q) {
       const unsigned dst = dst0 + static_cast<unsigned>(buf * C::STAGE + q * 1024);
-      const unsigned voff = (vlane ^ (static_cast<unsigned>((q * RPP) & C::SWZ) << 4)) +
+      const unsigned voff = (vlane ^ (static_cast<unsigned>(C::swz(q * RPP)) << 4)) +
                             static_cast<unsigned>(q * RPP) * rowbytes;
       unsigned keep;
       asm volatile(
@@ -320,23 +347,22 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
   };
   constexpr float kFold = 0x1p8f;  // units of 2^-24 -> multiples of 2^-32
 
-  // B-fragment LDS offsets (float4 units): slot (k + lq) ^ (li & SWZ) of
-  // column row li, k = c*LG (+ HI for the L half) a multiple of 4; the XOR
-  // splits into a lane part (low 2 bits) and a k part (k ^ (li & SWZ & ~3)),
-  // so two registers cover every k-step and half
-  const int b_base = li * C::SLOTS + (lq ^ (li & 3));
-  const int b_swz = li & C::SWZ & ~3;
-  auto b_off = [&](int c, bool lo_half) { return b_base + ((c * C::LG + (lo_half ? C::HI : 0)) ^ b_swz); };
+  // B-fragment LDS offsets (float4 units): slot (k + lq) ^ swz(li) of column
+  // row li (a stage's tiles start at multiples of 16 rows: swz(row) = swz(li)),
+  // k = c*LG a multiple of 4; the XOR splits into a lane part (low 2 bits) and
+  // a k part (k ^ (swz(li) & ~3)), so two registers cover every k-step
+  const int b_base = li * C::SLOTS + (lq ^ (C::swz(li) & 3));
+  const int b_swz = C::swz(li) & ~3;
+  auto b_off = [&](int c) { return b_base + ((c * C::LG) ^ b_swz); };
 
   f32x4 mc[C::NCH][C::RT];
   // one stage of SC columns; fresh = first stage of a fold group (the chains
   // restart).  B fragments go through two register sets: k-step i+1's are
   // read while k-step i's 16 MFMAs issue.
   auto compute = [&](int buf, bool fresh_stage) {
-    f16x8 bh[2], bl[2];
+    f16x8 bh[2];
     auto load_b = [&](int set, int c, int ct) {
-      bh[set] = __builtin_bit_cast(f16x8, lds[buf * C::F4 + ct * 16 * C::SLOTS + b_off(c, false)]);
-      bl[set] = __builtin_bit_cast(f16x8, lds[buf * C::F4 + ct * 16 * C::SLOTS + b_off(c, true)]);
+      bh[set] = __builtin_bit_cast(f16x8, lds[buf * C::F4 + ct * 16 * C::SLOTS + b_off(c)]);
     };
     load_b(0, 0, 0);
 #pragma unroll
@@ -355,13 +381,11 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
 #pragma unroll
         for (int rt = 0; rt < C::RT; ++rt)
           mc[ch][rt] = mfma16(ah[rt][c], bh[cur], (c == 0 && fresh) ? zero : mc[ch][rt]);
-#pragma unroll
-        for (int rt = 0; rt < C::RT; ++rt) mc[ch][rt] = mfma16(ah[rt][c], bl[cur], mc[ch][rt]);
       }
-      constexpr int NM = 2 * C::RT;  // MFMAs per k-step
+      constexpr int NM = C::RT;  // MFMAs per k-step
 #pragma unroll
       for (int c = 0; c < C::NKS; ++c) {
-        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // next k-step's B
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // next k-step's B
         __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);  // MFMA
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -459,91 +483,127 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
 }
 // ---------------------------------------------------------------------------
 // Residual of the compensation (see the header).  Three launches:
-//  1. per super block Q: sigma~_Q and sigma^L_Q, exact int64 in units of 2^-24
-//     (every H and L is a multiple of 2^-24 below 2^13);
-//  2. per feature: exclusive prefix sums over super blocks of each parity
-//     class and their totals, giving R_B and C_B for every requested B (for
-//     d_pad <= 64 and few super blocks the launch-3 blocks form their own R_B,
-//     C_B from sigma~ instead: one launch less, 21 us at configs 2 and 3);
+//  1. per super block Q: sigma^H_Q, and the pool total S^L of the L terms,
+//     exact int64 in units of 2^-24 (every H and L is a multiple of 2^-24 below
+//     2^13);
+//  2. per feature: exclusive prefix sums of sigma^H over super blocks of each
+//     parity class and their totals, giving S~ and D_B = S^L + CH_B for every
+//     requested B (for d_pad <= 64 and few super blocks the launch-3 blocks
+//     form them from sigma^H and S^L instead: one launch less, 21 us at
+//     configs 2 and 3);
 //  3. per row r of the requested super blocks: acc[r] += rint(2^8 *
-//     (<L_r, R_B> + <u~_r, C_B>)) with the dots in fp64 in a fixed order.
+//     (<L_r, S~> + <H_r, D_B>)) with the dots in fp64 in a fixed order.
+// Workspace (the sizes are part of the interface): sig = sigma^H [super
+// block][d_pad] int64; rb = d_pad words, S^L as int64 from launch 1, replaced
+// by S~ as fp64 by the scan (each feature by the one block that read it,
+// behind its barrier); cb = D_B [requested super block][d_pad] fp64.
 
-// One block per (super block, group of 256 16-byte chunk columns): the
-// super block's 512 operand rows are 512 x CPR 16-byte chunks (CPR = ldh / 8
-// per row: the H and L halves of every slice); thread t always reads chunk
+// One block per (group of super blocks, group of 256 16-byte chunk columns,
+// row slice): a super block's 512 operand rows are 512 x CPR 16-byte chunks
+// (CPR = ldh / 8 per row: the H and L halves of every slice); thread t reads chunk
 // column t % CPR (8 H or 8 L halves of one slice) of rows t / CPR, + 256 /
 // CPR, ... -- independent 16-B loads, 8 in flight -- summed exactly in int64,
 // then reduced over the threads of the same column in LDS.
+// A block walks qg consecutive super blocks: sigma^H of each goes out per
+// super block (addresses of its own); the L chunk columns stay in registers
+// over the whole walk and reach S^L with one add per block and feature -- S^L
+// is d_pad addresses for the whole pool, and one add per super block and row
+// slice (15,628 per address at config 4) made this kernel 2.85 ms, from 0.55.
 __global__ __launch_bounds__(256) void csym_sigma_kernel(const uint16_t* __restrict__ ops, int64_t ldh, int ks,
-                                                         int d_pad, long long* __restrict__ sig_u) {
+                                                         int d_pad, int ns, int qg, long long* __restrict__ sig_u,
+                                                         long long* __restrict__ sl) {
   __shared__ long long red[256][9];  // [thread][8 halves] (+1: bank spread)
-  const int Q = blockIdx.x;
   const int cpr = static_cast<int>(ldh / 8);      // chunks per row
   const int cols = cpr < 256 ? cpr : 256;          // chunk columns of this block
   const int col = blockIdx.y * 256 + threadIdx.x % cols;
   const int rstep = 256 / cols;                    // rows advanced per round
   const int r0 = threadIdx.x / cols;
-  // this block's rows of the super block: [rb, re) (gridDim.z row slices)
+  // this block's rows of each super block: [rb, re) (gridDim.z row slices)
   const int rb = kSB * static_cast<int>(blockIdx.z) / static_cast<int>(gridDim.z);
   const int re = kSB * (static_cast<int>(blockIdx.z) + 1) / static_cast<int>(gridDim.z);
-  // Summed in fp64, exactly: every term is a multiple of 2^-24 below 2^13 and
-  // a thread adds at most kSB of them (< 2^22), so every partial sum has at
-  // most 46 significant bits; converted to int64 units once at the end.
-  double acc[8] = {};
-  if (col < cpr && r0 < rstep) {
-    const uint4* base = reinterpret_cast<const uint4*>(ops + static_cast<int64_t>(Q) * kSB * ldh) + col;
-    for (int r = rb + r0; r < re; r += 8 * rstep) {
-      uint4 q[8];
+  // chunk column -> (slice, half, first feature): the row is [slice][H KS | L KS]
+  const int hpc = ks / 8;                          // chunks per half of a slice
+  const int slice = col / (2 * hpc), within = col % (2 * hpc);
+  const int f0 = slice * ks + (within % hpc) * 8;
+  const bool l_col = within >= hpc;
+  const bool finisher = threadIdx.x < cols && col < cpr;  // thread t < cols finishes chunk column t
+  const int q_end = (static_cast<int>(blockIdx.x) + 1) * qg < ns ? (static_cast<int>(blockIdx.x) + 1) * qg : ns;
+  long long lsum[8] = {};  // an L column's sums over the block's super blocks
+  for (int Q = static_cast<int>(blockIdx.x) * qg; Q < q_end; ++Q) {
+    // Summed in fp64, exactly: every term is a multiple of 2^-24 below 2^13 and
+    // a thread adds at most kSB of them (< 2^22), so every partial sum has at
+    // most 46 significant bits; converted to int64 units once at the end.
+    double acc[8] = {};
+    if (col < cpr && r0 < rstep) {
+      const uint4* base = reinterpret_cast<const uint4*>(ops + static_cast<int64_t>(Q) * kSB * ldh) + col;
+      for (int r = rb + r0; r < re; r += 8 * rstep) {
+        uint4 q[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) q[j] = r + j * rstep < re ? base[static_cast<int64_t>(r + j * rstep) * cpr] : uint4{};
+        for (int j = 0; j < 8; ++j)
+          q[j] = r + j * rstep < re ? base[static_cast<int64_t>(r + j * rstep) * cpr] : uint4{};
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const uint32_t w[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
+        for (int j = 0; j < 8; ++j) {
+          const uint32_t w[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          acc[2 * e] += static_cast<double>(
-              static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(w[e] & 0xFFFFu))));
-          acc[2 * e + 1] += static_cast<double>(
-              static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(w[e] >> 16))));
+          for (int e = 0; e < 4; ++e) {
+            acc[2 * e] += static_cast<double>(
+                static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(w[e] & 0xFFFFu))));
+            acc[2 * e + 1] += static_cast<double>(
+                static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(w[e] >> 16))));
+          }
         }
       }
     }
-  }
+    if (l_col) {  // (below 2^35 per super block: int64 holds any pool)
 #pragma unroll
-  for (int e = 0; e < 8; ++e) red[threadIdx.x][e] = static_cast<long long>(acc[e] * 16777216.0);
+      for (int e = 0; e < 8; ++e) lsum[e] += static_cast<long long>(acc[e] * 16777216.0);
+    }
+    if (Q > static_cast<int>(blockIdx.x) * qg) __syncthreads();  // the previous super block's sums are read
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[threadIdx.x][e] = static_cast<long long>(acc[e] * 16777216.0);
+    __syncthreads();
+    if (finisher && !l_col) {  // sigma^H_Q: sum over the rstep row phases (gridDim.z row slices per address)
+      long long v[8] = {};
+      for (int p = 0; p < rstep; ++p)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += red[p * cols + threadIdx.x][e];
+      long long* dst = sig_u + static_cast<int64_t>(Q) * d_pad + f0;
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (v[e] != 0) atomicAdd(reinterpret_cast<unsigned long long*>(dst + e), static_cast<unsigned long long>(v[e]));
+    }
+  }
   __syncthreads();
-  // thread t < cols finishes chunk column t: sum over the rstep row phases
-  if (threadIdx.x < cols && col < cpr) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) red[threadIdx.x][e] = lsum[e];
+  __syncthreads();
+  if (finisher && l_col) {
     long long v[8] = {};
     for (int p = 0; p < rstep; ++p)
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] += red[p * cols + threadIdx.x][e];
-    // chunk column -> (slice, half, first feature): the row is [slice][H KS | L KS]
-    const int hpc = ks / 8;                        // chunks per half of a slice
-    const int slice = col / (2 * hpc), within = col % (2 * hpc);
-    const int f0 = slice * ks + (within % hpc) * 8;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int64_t o = static_cast<int64_t>(Q) * d_pad + f0 + e;
-      atomicAdd(reinterpret_cast<unsigned long long*>(sig_u + o), static_cast<unsigned long long>(v[e]));
-    }
+    for (int e = 0; e < 8; ++e)
+      if (v[e] != 0) atomicAdd(reinterpret_cast<unsigned long long*>(sl + f0 + e), static_cast<unsigned long long>(v[e]));
   }
 }
 
-// block = 8 waves; lane = one of 64 features (blockIdx.x * 64 + lane), wave w
-// owns super blocks [w*ns/8, (w+1)*ns/8).  R_B, C_B written as fp64 for B in
-// [b0, b1).
+// block = kScanWaves waves; lane = one of 64 features (blockIdx.x * 64 +
+// lane), wave w owns super blocks [w*ns/kW, (w+1)*ns/kW).  sl: S^L (int64) in
+// the d_pad words that st receives S~ in (fp64) -- the same memory; every wave
+// reads its feature's S^L before the barrier, wave 0 writes S~ behind it.
+// D_B = S^L + CH_B written as fp64 for B in [b0, b1).
 #ifndef DAL_CSYM_SCAN_WAVES
 #define DAL_CSYM_SCAN_WAVES 16
 #endif
 constexpr int kScanWaves = DAL_CSYM_SCAN_WAVES;  // super-block ranges per feature (one wave each)
-constexpr int kScanBatch = 16;                   // sigma~ loads in flight per thread
+constexpr int kScanBatch = 16;                   // sigma^H loads in flight per thread
 #ifndef DAL_CSYM_FUSED_MAX
 #define DAL_CSYM_FUSED_MAX 65536  // super blocks x d_pad up to which the residual blocks skip the scan
 #endif
 __global__ __launch_bounds__(64 * kScanWaves) void csym_scan_kernel(const long long* __restrict__ sig_u, int ns,
-                                                                    int d_pad, int b0, int b1,
-                                                                    double* __restrict__ rb, double* __restrict__ cb) {
+                                                                    int d_pad, int b0, int b1, const long long* sl,
+                                                                    double* st, double* __restrict__ cb) {
   constexpr int kW = kScanWaves;
   __shared__ long long part[kW][2][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -551,11 +611,12 @@ __global__ __launch_bounds__(64 * kScanWaves) void csym_scan_kernel(const long l
   const bool live = f < d_pad;
   const int q0 = static_cast<int>(static_cast<int64_t>(ns) * w / kW);
   const int q1 = static_cast<int>(static_cast<int64_t>(ns) * (w + 1) / kW);
-  // u~ sums per parity class of the super block (even, odd); named
+  // sigma^H sums per parity class of the super block (even, odd); named
   // registers, not arrays indexed by q & 1 (those would live in scratch)
   // loads in batches of kScanBatch, all in flight before the adds (a wave walks
   // ns / kW super blocks: 244 at config 4)
   long long ue = 0, uo = 0;
+  const long long s_l = live ? sl[f] : 0;
   if (live) {
     for (int qb = q0; qb < q1; qb += kScanBatch) {
       long long v[kScanBatch];
@@ -585,6 +646,8 @@ __global__ __launch_bounds__(64 * kScanWaves) void csym_scan_kernel(const long l
     tuo += a1;
   }
   if (!live) return;
+  // S~ = the sum of H + L over every row
+  if (w == 0) st[f] = static_cast<double>(tue + tuo + s_l);
   for (int qb = q0; qb < q1; qb += kScanBatch) {
     long long v[kScanBatch];
 #pragma unroll
@@ -596,14 +659,12 @@ __global__ __launch_bounds__(64 * kScanWaves) void csym_scan_kernel(const long l
       // e* = exclusive prefix (super blocks < q) per class; b = q's class
       const bool odd = q & 1;
       if (q < q1 && q >= b0 && q < b1) {
-        // R_B = sum_{Q >= B, same class} + sum_{Q < B, other class} of sigma~
-        // (the super blocks B takes); C_B = sum_{P < B, same class} + sum_{P >
-        // B, other class} of sigma~ (the other super blocks that take B: their
-        // pairs' column sums for B's rows)
-        const long long R = odd ? (tuo - euo + eue) : (tue - eue + euo);
-        const long long Cc = odd ? (euo + tue - eue) : (eue + tuo - euo);
-        rb[static_cast<int64_t>(q - b0) * d_pad + f] = static_cast<double>(R);
-        cb[static_cast<int64_t>(q - b0) * d_pad + f] = static_cast<double>(Cc);
+        // CH_B = sum_{P < B, same class} + sum_{P > B, other class} of sigma^H
+        // (the other super blocks that take B: B takes itself, the later ones
+        // of its class and the earlier ones of the other, whose H.H row sums
+        // the MFMAs formed)
+        const long long ch = odd ? (euo + tue - eue) : (eue + tuo - euo);
+        cb[static_cast<int64_t>(q - b0) * d_pad + f] = static_cast<double>(ch + s_l);
       }
       eue += odd ? 0 : v[j];
       euo += odd ? v[j] : 0;
@@ -611,10 +672,11 @@ __global__ __launch_bounds__(64 * kScanWaves) void csym_scan_kernel(const long l
   }
 }
 
-// One thread per row: a block's 256 rows lie in one super block B, whose R_B
-// and C_B are staged in LDS once; each thread sums its row's features in
-// order, t = t + l_f R_f, t = t + (h_f + l_f) C_f for f = 0, 1, ... (fp64, no
-// FMA) -- a fixed order, so the bits are the same on every GPU count.  rows:
+// One thread per row: a block's 256 rows lie in one super block B; S~ and B's
+// D_B = S^L + CH_B are staged in LDS once; each thread sums its row's features
+// in order, t = t + l_f S~_f, t = t + h_f D_f for f = 0, 1, ... (fp64, no FMA;
+// sums of products only, S~ and D_B being formed as integers) -- a fixed
+// order, so the bits are the same on every GPU count.  rows:
 // the operand of the requested super blocks.  The rows reach the threads
 // through LDS, kResFeat features at a time: the block reads each row's H and L
 // runs of those features with coalesced 16-B loads (consecutive threads,
@@ -628,27 +690,28 @@ constexpr int kResFeat = 32;                 // features per LDS stage (divides 
 constexpr int kResQ = kResFeat / 4;          // 16-B chunks per row per stage: H kResFeat/8, L kResFeat/8
 constexpr int kResLd = kResQ + 1;            // LDS row stride in 16-B chunks (+1: the threads' rows spread over the banks)
 // kMode kResFused (d_pad 32 or 64, few super blocks): no scan launch -- every
-// block forms its own R_B and C_B from sigma~ (256 / d_pad thread groups over
-// the super blocks, exact int64 sums reduced in LDS; the same integers as the
-// scan's).  kResStaged: the scan's R_B, C_B staged in LDS (16 d_pad bytes).
+// block forms its own S~ and D_B from sigma^H and S^L (256 / d_pad thread
+// groups over the super blocks, exact int64 sums reduced in LDS; the same
+// integers as the scan's; st then still holds S^L as int64).  kResStaged: the
+// scan's S~, D_B staged in LDS (16 d_pad bytes).
 // kResGlobal (d_pad > kResLdsMaxFeat, where they would not fit beside the
 // tile): read in place from the scan's output, uniform addresses.
 constexpr int kResStaged = 0, kResFused = 1, kResGlobal = 2;
-constexpr int kResLdsMaxFeat = 1024;  // 16 KiB of R_B | C_B + the 36 KiB tile: within 64 KiB per block
+constexpr int kResLdsMaxFeat = 1024;  // 16 KiB of S~ | D_B + the 36 KiB tile: within 64 KiB per block
 template <int kMode>
 __global__ __launch_bounds__(kResRows) void csym_residual_kernel(const uint16_t* __restrict__ rows, int64_t ldh, int ks,
                                                                  int d_pad, int b0, int n_rows,
-                                                                 const double* __restrict__ rb,
+                                                                 const double* __restrict__ st,
                                                                  const double* __restrict__ cb,
                                                                  const long long* __restrict__ sig_u, int ns,
                                                                  long long* __restrict__ acc) {
-  extern __shared__ double rc[];  // [d_pad] R_B | [d_pad] C_B
+  extern __shared__ double rc[];  // [d_pad] S~ | [d_pad] D_B
   __shared__ uint4 tile[kResRows * kResLd];
   const int tid = threadIdx.x;
   const int64_t r0 = static_cast<int64_t>(blockIdx.x) * kResRows;  // (a multiple of 256: one super block)
   const int64_t B = r0 / kSB;                                       // relative to b0
   if constexpr (kMode == kResFused) {
-    // feature pairs (16-B loads of sigma~): 256 / (d_pad / 2) thread groups
+    // feature pairs (16-B loads of sigma^H): 256 / (d_pad / 2) thread groups
     // over the super blocks -- 8 (d_pad 64) or 16 (d_pad 32)
     __shared__ long long red[8][kResRows];
     const int qB = b0 + static_cast<int>(B);  // this block's super block
@@ -694,20 +757,21 @@ __global__ __launch_bounds__(kResRows) void csym_residual_kernel(const uint16_t*
           tue += red[4 * c + 2][g * hp + tid];
           tuo += red[4 * c + 3][g * hp + tid];
         }
-        const bool odd = qB & 1;  // R_B, C_B as in csym_scan_kernel
+        const bool odd = qB & 1;  // S~, CH_B as in csym_scan_kernel
         const int f = 2 * tid + c;
-        rc[f] = static_cast<double>(odd ? (tuo - euo + eue) : (tue - eue + euo));
-        rc[d_pad + f] = static_cast<double>(odd ? (euo + tue - eue) : (eue + tuo - euo));
+        const long long s_l = reinterpret_cast<const long long*>(st)[f];
+        rc[f] = static_cast<double>(tue + tuo + s_l);
+        rc[d_pad + f] = static_cast<double>((odd ? (euo + tue - eue) : (eue + tuo - euo)) + s_l);
       }
     }
   } else if constexpr (kMode == kResStaged) {
     for (int f = tid; f < d_pad; f += kResRows) {
-      rc[f] = rb[B * d_pad + f];
+      rc[f] = st[f];
       rc[d_pad + f] = cb[B * d_pad + f];
     }
   }
-  const double* __restrict__ Rv = kMode == kResGlobal ? rb + B * d_pad : rc;
-  const double* __restrict__ Cv = kMode == kResGlobal ? cb + B * d_pad : rc + d_pad;
+  const double* __restrict__ Sv = kMode == kResGlobal ? st : rc;
+  const double* __restrict__ Dv = kMode == kResGlobal ? cb + B * d_pad : rc + d_pad;
   const int live_rows = n_rows - r0 < kResRows ? static_cast<int>(n_rows - r0) : kResRows;
   const uint16_t* blk = rows + r0 * ldh;
   double t = 0.0;
@@ -741,13 +805,13 @@ __global__ __launch_bounds__(kResRows) void csym_residual_kernel(const uint16_t*
           const uint16_t lb = static_cast<uint16_t>(e & 1 ? lw[e >> 1] >> 16 : lw[e >> 1] & 0xFFFFu);
           const double h = static_cast<double>(static_cast<float>(__builtin_bit_cast(_Float16, hb)));
           const double l = static_cast<double>(static_cast<float>(__builtin_bit_cast(_Float16, lb)));
-          t = t + l * Rv[f];
-          t = t + (h + l) * Cv[f];
+          t = t + l * Sv[f];
+          t = t + h * Dv[f];
         }
       }
     }
   }
-  // R, C in units of 2^-24 x (split units); value = t * 2^-24 * 2^-24 ... in
+  // S~, D_B in units of 2^-24 x (split units); value = t * 2^-24 * 2^-24 ... in
   // fixed point (2^32): t * 2^-24 (operand units^2 = 2^24 x value) * 2^8
   if (tid < live_rows && t != 0.0)
     acc[static_cast<int64_t>(b0) * kSB + r0 + tid] += static_cast<long long>(__builtin_rint(t * 0x1p-16));
@@ -965,16 +1029,17 @@ int split_ks(int64_t d_pad) { return d_pad == 32 ? 32 : (d_pad % 128 == 0 ? 128 
 using namespace dal;
 
 namespace {
-// Row-side chain length of the kernel that runs d_pad (split_ks), 0 = the
-// longest over every KS.
+// Row-side chain length the bound charges the kernel that runs d_pad
+// (split_ks) with, 0 = the longest over every KS (Cfg::CHARGED: twice the
+// kernel's own Cfg::CHAIN at the default folds, never below it).
 int row_chain_products(int64_t d_pad) {
   if (d_pad <= 0) {
-    int m = Cfg<32, 4>::CHAIN;
-    m = Cfg<64, 4>::CHAIN > m ? Cfg<64, 4>::CHAIN : m;
-    return Cfg<128, 4>::CHAIN > m ? Cfg<128, 4>::CHAIN : m;
+    int m = Cfg<32, 4>::CHARGED;
+    m = Cfg<64, 4>::CHARGED > m ? Cfg<64, 4>::CHARGED : m;
+    return Cfg<128, 4>::CHARGED > m ? Cfg<128, 4>::CHARGED : m;
   }
   const int ks = split_ks(d_pad);
-  return ks == 32 ? Cfg<32, 4>::CHAIN : ks == 64 ? Cfg<64, 4>::CHAIN : Cfg<128, 4>::CHAIN;
+  return ks == 32 ? Cfg<32, 4>::CHARGED : ks == 64 ? Cfg<64, 4>::CHARGED : Cfg<128, 4>::CHARGED;
 }
 }  // namespace
 
@@ -983,15 +1048,18 @@ extern "C" double dal_density_error_bound_sym_d(int64_t n_cols, int64_t d_pad) {
   // density, per density entry (one column j of row i), u = 2^-23 (a
   // conservative unit roundoff for the MFMA's internal fp32 adds, counted as
   // sequential adds), products exact (f16 x f16), c = 1 + 2^-8 >= sum_d |h_i
-  // h_j| + |h_i l_j| over sum_d |u_i u_j| <= 1 (Cauchy-Schwarz on unit rows):
+  // h_j| over sum_d |u_i u_j| <= 1 (Cauchy-Schwarz on unit rows):
   //   row side   (the MFMA row sums of the taken pairs) NCH chains per row
-  //              tile between folds: Cfg<KS>::CHAIN products each (FOLD / 16 /
-  //              NCH tiles x 2 KS: 1,024 at KS 32, 2,048 at KS 64 and 128), the
+  //              tile between folds, charged Cfg<KS>::CHARGED products each
+  //              (1,024 at KS 32, 2,048 at KS 64 and 128: the chains of the
+  //              earlier H.H + H.L body; the H.H chains are Cfg<KS>::CHAIN =
+  //              FOLD / 16 / NCH tiles x KS, half as long, so this over-charges
+  //              -- the bound's values are part of the interface and stay), the
   //              add combining the two chains (KS 128) and 4 cross-lane adds:
-  //              gamma_(CHAIN + 5) * c
-  //   column side  none: every taken pair's column sums are the closed form
-  //              <u~_i, C_B> of dal_gram_sym_residual (exact int64 sums, an
-  //              fp64 dot), as is the row side's remainder <L_i, R_B>: below
+  //              gamma_(CHARGED + 5) * c
+  //   column side  none: every taken pair's column sums and the L terms are
+  //              the closed form <L_i, S~> + <H_i, S^L + CH_B> of
+  //              dal_gram_sym_residual (exact int64 sums, an fp64 dot): below
   //              2^-40 per column together
   //   split + fp32 unit rows  5 * 2^-22;  fixed-point roundings <= 2^-33 each
   const double u = 1.0 / 8388608.0;  // 2^-23
@@ -1072,30 +1140,36 @@ extern "C" int dal_gram_sym_residual(const uint16_t* ops, int64_t nb_active, int
   double* cb = reinterpret_cast<double*>(w + L.cb);
   const int ks = split_ks(d_pad);
   const int64_t ldh = 2 * d_pad;
-  if (hipMemsetAsync(sig_u, 0, static_cast<size_t>(na * d_pad) * 8, st) != hipSuccess) return DAL_ERR_HIP;
-  // rows of a super block over 4 blocks (more loads in flight: 196 super blocks at config 2)
+  // sigma^H and, behind it (the layout's padding between), the d_pad words of S^L
+  static_assert(sizeof(long long) == sizeof(double), "S^L and S~ share their words");
+  long long* sl = reinterpret_cast<long long*>(rb);
+  if (hipMemsetAsync(sig_u, 0, L.rb - L.sig_u + static_cast<size_t>(d_pad) * 8, st) != hipSuccess) return DAL_ERR_HIP;
+  // rows of a super block over 4 blocks (more loads in flight: 196 super blocks at config 2);
+  // super blocks per block: what leaves about four blocks per CU, at most 32
+  const int64_t ny = ceil_div(ldh / 8, 256);
+  const int64_t qg0 = na * ny * 4 / (4 * device_cus()), qg = qg0 < 1 ? 1 : qg0 > 32 ? 32 : qg0;
   hipLaunchKernelGGL(csym_sigma_kernel,
-                     dim3(static_cast<unsigned>(na), static_cast<unsigned>(ceil_div(ldh / 8, 256)), 4), dim3(256), 0,
-                     st, ops, ldh, ks, static_cast<int>(d_pad), sig_u);
+                     dim3(static_cast<unsigned>(ceil_div(na, qg)), static_cast<unsigned>(ny), 4), dim3(256), 0, st,
+                     ops, ldh, ks, static_cast<int>(d_pad), static_cast<int>(na), static_cast<int>(qg), sig_u, sl);
   DAL_RETURN_IF_LAUNCH_FAILED();
   const int64_t n_rows = ns * kSB;
   const dim3 grid(static_cast<unsigned>(ceil_div(n_rows, kResRows)));
   const size_t smem = static_cast<size_t>(2 * d_pad) * 8;
   const uint16_t* rows = ops + s0 * kSB * ldh;
-  if (d_pad <= 64 && na * d_pad <= DAL_CSYM_FUSED_MAX) {  // the blocks form R_B, C_B themselves
+  if (d_pad <= 64 && na * d_pad <= DAL_CSYM_FUSED_MAX) {  // the blocks form S~, D_B themselves
     hipLaunchKernelGGL(csym_residual_kernel<kResFused>, grid, dim3(kResRows), smem, st, rows, ldh, ks,
                        static_cast<int>(d_pad), static_cast<int>(s0), static_cast<int>(n_rows), rb, cb, sig_u,
                        static_cast<int>(na), reinterpret_cast<long long*>(acc));
   } else {
     hipLaunchKernelGGL(csym_scan_kernel, dim3(static_cast<unsigned>(ceil_div(d_pad, 64))), dim3(64 * kScanWaves), 0,
                        st, sig_u, static_cast<int>(na), static_cast<int>(d_pad), static_cast<int>(s0),
-                       static_cast<int>(s0 + ns), rb, cb);
+                       static_cast<int>(s0 + ns), sl, rb, cb);
     DAL_RETURN_IF_LAUNCH_FAILED();
     if (d_pad <= kResLdsMaxFeat) {
       hipLaunchKernelGGL(csym_residual_kernel<kResStaged>, grid, dim3(kResRows), smem, st, rows, ldh, ks,
                          static_cast<int>(d_pad), static_cast<int>(s0), static_cast<int>(n_rows), rb, cb, sig_u,
                          static_cast<int>(na), reinterpret_cast<long long*>(acc));
-    } else {  // wide pools: R_B, C_B read in place (they would not fit in LDS beside the tile)
+    } else {  // wide pools: S~, D_B read in place (they would not fit in LDS beside the tile)
       hipLaunchKernelGGL(csym_residual_kernel<kResGlobal>, grid, dim3(kResRows), 0, st, rows, ldh, ks,
                          static_cast<int>(d_pad), static_cast<int>(s0), static_cast<int>(n_rows), rb, cb, sig_u,
                          static_cast<int>(na), reinterpret_cast<long long*>(acc));

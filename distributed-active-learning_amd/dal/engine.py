@@ -507,7 +507,7 @@ def _gram_kind(gram) -> str:
 def gram_products(state: PoolState) -> int:
     """fp16 MFMA products per feature pair of the pool's Gram kernel (bench
     roofline: executed vs algorithmic flops)."""
-    return 2 if state.gram == "sym" else 1
+    return 1  # "sym": H.H alone since the H.L terms moved to the closed-form residual
 
 
 def _as_index(idx, device):

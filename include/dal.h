@@ -166,12 +166,14 @@ int dal_prep_split(const float* x, int64_t n, int64_t d, int64_t ldx, const uint
  * since ABI v8).  S = U U^T is symmetric: rows are grouped in 512-row super
  * blocks (pairs of 256-row blocks) and each unordered pair {P, Q} is
  * multiplied once.  P takes Q iff Q == P, or Q > P and P+Q even, or Q < P and
- * P+Q odd (global indices, so the bits do not depend on the sharding).  The
- * taker's side is H only: per 32 features two v_mfma_f32_16x16x32_f16 (H.H,
- * H.L) form the row sums of <H_i, H_j + L_j> over the taken pairs (-> acc
- * rows of P).  dal_gram_sym_residual adds everything else in closed form:
- * the taker's remainder <L_i, H_j + L_j> and the pair's column sums for Q's
- * rows (sum over the P taking Q of <u~_j, sum_{i in P} u~_i>) -- acc holds the
+ * P+Q odd (global indices, so the bits do not depend on the sharding).  Both
+ * MFMA operands are H only (the L halves of the operand are not read here):
+ * per 32 features one v_mfma_f32_16x16x32_f16 forms the row sums of the fp16
+ * Gram <H_i, H_j> over the taken pairs (-> acc rows of P).
+ * dal_gram_sym_residual adds everything else in closed form: every term with
+ * an L factor (<L_i, H_j + L_j> and <H_i, L_j>, over every column j) and the
+ * pair's H.H column sums for Q's rows (sum over the P taking Q of <H_j, sum_{i
+ * in P} H_i>) -- acc holds the
  * density only after BOTH (any order; integer adds), and each call writes
  * only the acc rows of ITS row blocks (no cross-GPU density sum).  rows: the
  * operand of global 256-row blocks [row_block0, row_block0 + n_row_blocks)
@@ -193,12 +195,11 @@ int dal_gram_rowsum_sym_skip(const uint16_t* rows, int64_t row_block0, int64_t n
                              int64_t* acc, int grid_blocks, dal_stream_t stream);
 /* The closed-form part of dal_gram_rowsum_sym's density for the rows of
  * global blocks [row_block0, row_block0 + n_row_blocks) (even), ADDED into acc
- * (global row index): acc[r] += rint(2^32 * (<L_r, R_B> + <H_r + L_r, C_B>)),
- * B = r's super block, R_B = sum over the super blocks B takes of their
- * (H + L) row sums (the taker side's remainder), C_B = the same sum over the
- * other super blocks that take B (their pairs' column sums for B's rows;
- * sigma~ since ABI v8) -- exact int64 sums in units of 2^-24, fp64 dots in a
- * fixed order.  ops: the
+ * (global row index): acc[r] += rint(2^32 * (<L_r, S~> + <H_r, S^L + CH_B>)),
+ * B = r's super block, S~ = the sum of H + L and S^L the sum of L over every
+ * active row, CH_B = the sum of the H row sums of the other super blocks that
+ * take B (their pairs' column sums for B's rows) -- exact int64 sums in units
+ * of 2^-24, fp64 dots of products in a fixed order.  ops: the
  * operand of EVERY active row (nb_active * 256 rows: the gathered operand on
  * several GPUs).  Three launches, O(N * D); workspace from
  * dal_gram_sym_residual_workspace_bytes (256-byte aligned). */
@@ -207,8 +208,9 @@ int dal_gram_sym_residual(const uint16_t* ops, int64_t nb_active, int64_t row_bl
                           int64_t d_pad, int64_t* acc, void* ws, size_t ws_bytes, dal_stream_t stream);
 double dal_density_error_bound_sym(int64_t n_cols);
 /* The same bound for the kernel that runs features padded to d_pad (ABI v8):
- * the row-side chain length depends on the slice width KS (1,024 products at
- * KS 32, 2,048 at KS 64 / 128); dal_density_error_bound_sym(n) ==
+ * the row-side chain length charged depends on the slice width KS (1,024
+ * products at KS 32, 2,048 at KS 64 / 128: twice what the H.H chains sum, the
+ * values are kept and over-charge); dal_density_error_bound_sym(n) ==
  * dal_density_error_bound_sym_d(n, 0) is the longest chain's, valid for any
  * d_pad. */
 double dal_density_error_bound_sym_d(int64_t n_cols, int64_t d_pad);

@@ -80,7 +80,8 @@ def main():
         parts = []
         for name in names:
             med = statistics.median(t[name])
-            parts.append(f"{name} {med:.4f} ms ({fl / med / 1e9 / 2500:.4f}; min {min(t[name]):.4f})")
+            parts.append(f"{name} {med:.4f} ms ({fl / med / 1e9 / 2500:.4f}; min {min(t[name]):.4f}, "
+                         f"max {max(t[name]):.4f})")
         print(f"{n} x {d}: " + " | ".join(parts) + ("  [" + "; ".join(notes) + "]" if notes else
                                                       "  [density bits identical]"), flush=True)
         _lib._lib = libs[names[0]]
