@@ -19,7 +19,10 @@
 // rows).  The tile's column sums (-> Q's rows) are linear in P's rows,
 // sum_{i in P} <H_i, H_j> = <sigma^H_P, H_j>, so they are added in closed
 // form with the residual below (round 5; before, as sigma_P MFMAs and int64
-// column flushes per pair).
+// column flushes per pair).  The rule, the order in which a block walks its
+// pairs and the launch's grid and column chunks are gram_schedule.hpp (plain
+// C++ shared by the kernel and the launcher; tests/test_gram_schedule.py
+// enumerates every block's walk on the CPU).
 //
 // Compensation and column sums.  Both MFMA operands hold H only: the MFMAs
 // form the fp16 Gram T_ij = <H_i, H_j> on the taken pairs, one product per
@@ -53,10 +56,8 @@
 // H-only A side frees the registers the L fragments held), else 64, or 32.
 #include <stdlib.h>
 
-#include <utility>
-#include <vector>
-
 #include "common.hpp"
+#include "gram_schedule.hpp"
 
 namespace dal {
 namespace {
@@ -235,61 +236,9 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
   const int G = gridDim.x, g = blockIdx.x;
   for (int e = tid; e < HV * kSB; e += C::NT) rowacc[e] = 0.0;
 
-  // Work = the pairs (P, J) over row super blocks P and 256-column blocks J in
-  // [j_lo, j_hi) minus [skip_lo, skip_hi), as segments (row unit, raw column
-  // range [rlo, rhi)) walked by a raw column cursor r (J = jmap(r)).  A row
-  // unit is one super block (W = 4) or two of the same parity, P and P + 2
-  // (W = 8: they take the same column blocks but near the diagonal, so one
-  // B stage feeds both; a half whose super block does not take J idles):
-  //  contig: block g owns the g-th 1/G of the unit-major raw grid (W = 4 only);
-  //  chunk:  unit u = (row unit u % n_ru, column chunk u / n_ru), dealt round-robin
-  //          (all blocks sweep the same column chunks together: L2 / MALL reuse).
-  const int n_ru = HV == 1 ? n_srb : 2 * ((n_srb + 3) / 4);
-  auto rowP = [&](int ru, int h) { return HV == 1 ? srow0 + ru : srow0 + 4 * (ru >> 1) + (ru & 1) + 2 * h; };
-  auto live = [&](int P) { return P < srow0 + n_srb && P < ns_active; };
-  const int sk_lo = skip_lo > j_lo ? skip_lo : j_lo, sk_hi = skip_hi < j_hi ? skip_hi : j_hi;
-  const int skl = contig && sk_hi > sk_lo ? sk_hi - sk_lo : 0;  // chunk mode skips through takes()
-  const int nje = j_hi - j_lo - skl;
-  const int nre0 = ns_active - srow0, nre = nre0 < n_srb ? (nre0 > 0 ? nre0 : 0) : n_srb;
-  const int64_t raw = static_cast<int64_t>(nre) * nje;
-  const int64_t ka = raw * g / G, kb = raw * (g + 1) / G;
-  const int n_seg = contig ? (kb > ka ? static_cast<int>((kb - 1) / nje - ka / nje) + 1 : 0) : n_ru * n_chunks;
-  const int seg_step = contig ? 1 : G;
-  auto seg_ru = [&](int u) { return contig ? static_cast<int>(ka / nje) + u : u % n_ru; };
-  auto seg_rlo = [&](int u) { return contig ? (u == 0 ? static_cast<int>(ka % nje) : 0) : (u / n_ru) * chunk_j; };
-  auto seg_rhi = [&](int u) {
-    if (contig) return u == n_seg - 1 ? static_cast<int>((kb - 1) % nje) + 1 : nje;
-    const int e = (u / n_ru + 1) * chunk_j;
-    return e < nje ? e : nje;
-  };
-  auto jmap = [&](int r) { return j_lo + r + (j_lo + r >= sk_lo ? skl : 0); };
-  auto takes = [&](int P, int J) -> bool {
-    const int Q = J >> 1;
-    if (J >= skip_lo && J < skip_hi) return false;
-    return Q == P || (Q > P && ((P + Q) & 1) == 0) || (Q < P && ((P + Q) & 1));
-  };
-  // the unit's super block h takes J (and exists)
-  auto takes_h = [&](int ru, int h, int J) { return live(rowP(ru, h)) && takes(rowP(ru, h), J); };
-  auto takes_u = [&](int ru, int J) { return takes_h(ru, 0, J) || (HV == 2 && takes_h(ru, HV - 1, J)); };
-  auto first_r = [&](int ru, int r, int rhi) -> int {
-    if constexpr (HV == 1) {
-      const int P = srow0 + ru;
-      if (P >= ns_active) return -1;
-      while (r < rhi && !takes(P, jmap(r))) ++r;
-    } else {
-      if (!live(rowP(ru, 0))) return -1;
-      while (r < rhi && !takes_u(ru, jmap(r))) ++r;
-    }
-    return r < rhi ? r : -1;
-  };
-  auto seek = [&](int u, int& r) {
-    while (u < n_seg) {
-      r = first_r(seg_ru(u), seg_rlo(u), seg_rhi(u));
-      if (r >= 0) break;
-      u += seg_step;
-    }
-    return u;
-  };
+  // the pairs this block multiplies and their order: gram_schedule.hpp
+  const GramSchedule<HV> sched(srow0, n_srb, j_lo, j_hi, skip_lo, skip_hi, ns_active, chunk_j, n_chunks, contig, G,
+                               g);
 
   // DMA source offsets.  Piece q of wave w covers stage rows
   // Wr + q * RPP + lane / SLOTS (Wr = w * PIECES * RPP, RPP = 64 / SLOTS rows
@@ -333,8 +282,8 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
   // group lq
   f16x8 ah[C::RT][C::NKS];
   auto load_a = [&](int ru) {
-    const int P = rowP(ru, half);
-    if (HV > 1 && !live(P)) return;  // (this half idles for the unit)
+    const int P = sched.rowP(ru, half);
+    if (HV > 1 && !sched.live(P)) return;  // (this half idles for the unit)
     const uint16_t* pb = urows + static_cast<int64_t>(P - srow0) * kSB * ldh + slice_off;
     const unsigned fl = fresh_lane();
     const unsigned lrow = static_cast<unsigned>((wave4 * 128 + (fl & 15)) * ldh + (fl >> 4) * 8);
@@ -416,8 +365,8 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
   };
   auto flush_rows = [&](int ru) {  // rowacc[h * 512 + r] -> row r of the unit's super block h
     for (int e = tid; e < HV * kSB; e += C::NT) {
-      const int P = rowP(ru, e / kSB);
-      if (live(P)) flush_one(rowacc[e], static_cast<int64_t>(P) * kSB + e % kSB);
+      const int P = sched.rowP(ru, e / kSB);
+      if (sched.live(P)) flush_one(rowacc[e], static_cast<int64_t>(P) * kSB + e % kSB);
     }
   };
   // every barrier waits for this wave's LDS adds and DMA first (hipcc may
@@ -428,25 +377,17 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
   };
   auto stage_sync = [&]() { block_sync(); };
 
-  int r = -1;
-  int unit = seek(contig ? 0 : g, r);
-  if (unit >= n_seg) return;
-  int ru = seg_ru(unit), rhi_u = seg_rhi(unit);
-  int J = jmap(r);
-  issue(0, J, 0);
-  load_a(ru);
+  GramCursor<HV> cur(sched);
+  if (!cur.start()) return;
+  issue(0, cur.J, 0);
+  load_a(cur.ru);
   int buf = 0;       // LDS stage buffer of the next stage to compute
   int flushRU = -1;  // row unit whose sums wait in rowacc
 
   while (true) {
-    int nr = first_r(ru, r + 1, rhi_u), n_unit = unit;
-    if (nr < 0) n_unit = seek(unit + seg_step, nr);
-    const bool has_next = n_unit < n_seg;
-    const int nru = has_next ? seg_ru(n_unit) : -1;
-    const bool new_rows = nru != ru;
-    const int nJ = has_next ? jmap(nr) : -1;
+    cur.peek();
     // this wave's super block takes J?  (a half whose super block does not idles)
-    const bool act = HV == 1 || takes_h(ru, half, J);
+    const bool act = cur.acts(half);
 
 #pragma unroll
     for (int s = 0; s < C::SPP; ++s) {
@@ -456,9 +397,9 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
         flushRU = -1;
       }
       if (s + 1 < C::SPP) {
-        issue(buf ^ 1, J, s + 1);
-      } else if (has_next) {
-        issue(buf ^ 1, nJ, 0);
+        issue(buf ^ 1, cur.J, s + 1);
+      } else if (cur.has_next) {
+        issue(buf ^ 1, cur.next_J, 0);
       }
       if (act) {  // (wave-uniform)
         compute(buf, s % C::SPF == 0);
@@ -467,16 +408,9 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
       buf ^= 1;
     }
 
-    if (new_rows) flushRU = ru;
-    if (!has_next) break;
-    unit = n_unit;
-    rhi_u = seg_rhi(unit);
-    if (new_rows) {
-      ru = nru;
-      load_a(ru);
-    }
-    r = nr;
-    J = nJ;
+    if (cur.rows_change) flushRU = cur.ru;
+    if (!cur.has_next) break;
+    if (cur.advance()) load_a(cur.ru);
   }
   block_sync();
   if (flushRU >= 0) flush_rows(flushRU);
@@ -825,39 +759,8 @@ int device_cus() {
   return cus;
 }
 
-// Number of column blocks J in [lo, hi) that super block I takes (O(1)).
-inline int64_t sb_pairs(int64_t I, int64_t lo, int64_t hi) {
-  auto same_parity = [](int64_t a, int64_t b, int64_t p) -> int64_t {
-    if (b <= a) return 0;
-    return (b - p + 1) / 2 - (a - p + 1) / 2;
-  };
-  int64_t n = (lo <= I && I < hi) ? 1 : 0;
-  n += same_parity(lo > I + 1 ? lo : I + 1, hi, I & 1);
-  n += same_parity(lo, hi < I ? hi : I, (I & 1) ^ 1);
-  return n;
-}
-
-// Pairs (P, J) for row super block P over 256-column blocks [a, b).
-inline int64_t pairs_range(int64_t P, int64_t a, int64_t b) {
-  if (b <= a) return 0;
-  auto takes = [P](int64_t Q) { return Q == P || (Q > P && ((P + Q) & 1) == 0) || (Q < P && ((P + Q) & 1)); };
-  const int64_t qa = a >> 1, qb = (b - 1) >> 1;
-  int64_t n = 2 * sb_pairs(P, qa, qb + 1);
-  if ((a & 1) && takes(qa)) --n;
-  if (!((b - 1) & 1) && takes(qb)) --n;
-  return n;
-}
-inline int64_t pairs_skip(int64_t P, int64_t a, int64_t b, int64_t skip_lo, int64_t skip_hi) {
-  const int64_t sa = a > skip_lo ? a : skip_lo, sb = b < skip_hi ? b : skip_hi;
-  return pairs_range(P, a, b) - pairs_range(P, sa, sb);
-}
-
-// Column-chunk count for the round-robin units: the fewest chunks, at least
-// min_chunks, whose most loaded block has at most 8 % more pairs than the best
-// balance found (exact pair counts; cached per shape).  More chunks = a
-// smaller column working set swept by every block together (MALL hits; 2M x
-// 256: 16 chunks 3.9 % faster than 1; 4 and 8: 0.6 % slower), fewer = fewer A
-// loads and row flushes.  KS 64 with a column operand of <= DAL_GRAM_SMALL_MB
+// The fewest column chunks choose_chunks (gram_schedule.hpp) may pick for the
+// round-robin units.  KS 64 with a column operand of <= DAL_GRAM_SMALL_MB
 // (in L2 + MALL whole) takes >= 2 chunks instead of the contiguous schedule:
 // 100k x 64 (25.6 MB) 1.6-4.7 % faster in two of three same-process runs
 // (+0.7 % in the third), the clock 1.83 -> 1.88-1.92 GHz; at KS 32 and 128 the
@@ -872,68 +775,6 @@ inline int64_t pairs_skip(int64_t P, int64_t a, int64_t b, int64_t skip_lo, int6
 #ifndef DAL_GRAM_MIN_CHUNKS_SMALL
 #define DAL_GRAM_MIN_CHUNKS_SMALL 2
 #endif
-// hv = super blocks per row unit (gram_csym_kernel W / 4); a two-super-block
-// unit costs the pairs of the busier one (they take the same column blocks but
-// near the diagonal).
-int64_t choose_chunks(int64_t srow0, int64_t n_srb, int64_t lo, int64_t hi, int64_t skip_lo, int64_t skip_hi,
-                      int64_t ns_active, int64_t G0, int hv, int64_t kMinChunks) {
-  struct Entry {
-    int64_t k[10];
-    int64_t nc;
-  };
-  static thread_local Entry cache[8] = {};
-  static thread_local int cache_next = 0;
-  const int64_t key[10] = {srow0, n_srb, lo, hi, skip_lo, skip_hi, ns_active, G0, hv, kMinChunks};
-  for (const Entry& e : cache) {
-    bool hit = e.nc > 0;
-    for (int i = 0; i < 10 && hit; ++i) hit = e.k[i] == key[i];
-    if (hit) return e.nc;
-  }
-  const int64_t n_ru = hv == 1 ? n_srb : 2 * ceil_div(n_srb, 4);
-  auto rowP = [&](int64_t ru, int h) { return hv == 1 ? srow0 + ru : srow0 + 4 * (ru >> 1) + (ru & 1) + 2 * h; };
-  const int64_t nj = hi - lo;
-  int64_t best_max = -1;
-  std::vector<int64_t> load;
-  std::vector<std::pair<int64_t, int64_t>> cand;
-  int tried = 0;
-  // chunk counts from 1 up (from kMinChunks when it is above 16 and the columns allow)
-  for (int64_t c = kMinChunks > 16 && nj >= kMinChunks ? kMinChunks : 1; c <= nj && tried < 32; ++c) {
-    const int64_t cbk = ceil_div(nj, c), ncc = ceil_div(nj, cbk);
-    if (c > 1 && cbk == ceil_div(nj, c - 1)) continue;
-    ++tried;
-    const int64_t units = n_ru * ncc, G = units < G0 ? units : G0;
-    load.assign(static_cast<size_t>(G), 0);
-    for (int64_t u = 0; u < units; ++u) {
-      const int64_t clo = lo + (u / n_ru) * cbk, chi = clo + cbk < hi ? clo + cbk : hi;
-      int64_t w = 0;
-      for (int h = 0; h < hv; ++h) {
-        const int64_t P = rowP(u % n_ru, h);
-        if (P >= ns_active || P >= srow0 + n_srb) continue;
-        const int64_t pw = pairs_skip(P, clo, chi, skip_lo, skip_hi);
-        w = pw > w ? pw : w;
-      }
-      load[static_cast<size_t>(u % G)] += w;
-    }
-    int64_t mx = 0;
-    for (int64_t v : load) mx = v > mx ? v : mx;
-    cand.emplace_back(ncc, mx);
-    if (best_max < 0 || mx < best_max) best_max = mx;
-  }
-  int64_t best_nc = -1;
-  for (int pass = 0; pass < 2 && best_nc < 0; ++pass)
-    for (const auto& c : cand)
-      if ((pass || c.first >= kMinChunks) && c.second * 100 <= best_max * 108) {
-        best_nc = c.first;
-        break;
-      }
-  if (best_nc < 0) best_nc = cand.back().first;
-  Entry& e = cache[cache_next];
-  cache_next = (cache_next + 1) % 8;
-  for (int i = 0; i < 10; ++i) e.k[i] = key[i];
-  e.nc = best_nc;
-  return best_nc;
-}
-
 // Two super blocks per block (8 waves, one block per CU: each B stage feeds
 // 1,024 rows, half the L2 -> LDS bytes per flop of the 4-wave form) for the
 // round-robin schedule at KS 128.
@@ -951,26 +792,15 @@ int launch_csym_w(const uint16_t* rows, int64_t srow0, int64_t n_srb, const uint
   const int G0r = W == 4 ? (grid_blocks > 0 ? grid_blocks * kOcc / 2 : kOcc * device_cus())
                          : (grid_blocks > 0 ? grid_blocks : 2 * device_cus()) * 4 / W * kOcc;
   const int G0 = G0r > 0 ? G0r : 1;  // (a one-block grid in the 8-wave form)
-  const int64_t nj = j_hi - j_lo;
-  int64_t cbk = nj, n_chunks = 1, G;
-  if (contig) {
-    const int64_t sl = skip_lo > j_lo ? skip_lo : j_lo, sh = skip_hi < j_hi ? skip_hi : j_hi;
-    const int64_t nre = ns_active - srow0 < n_srb ? ns_active - srow0 : n_srb;
-    const int64_t raw = (nre > 0 ? nre : 0) * (nj - (sh > sl ? sh - sl : 0));
-    if (raw <= 0) return DAL_OK;
-    G = raw < G0 ? raw : G0;
-  } else {
-    const int64_t nc = choose_chunks(srow0, n_srb, j_lo, j_hi, skip_lo, skip_hi, ns_active, G0, W / 4, min_chunks);
-    cbk = ceil_div(nj, nc);
-    n_chunks = ceil_div(nj, cbk);
-    const int64_t n_units = (W == 4 ? n_srb : 2 * ceil_div(n_srb, 4)) * n_chunks;
-    G = n_units < G0 ? n_units : G0;
-  }
-  hipLaunchKernelGGL((gram_csym_kernel<KS, W>), dim3(static_cast<unsigned>(G)), dim3(64 * W), 0, stream, rows,
+  if (!GramSchedule<W / 4>::form_ok(contig)) return DAL_ERR_ARG;
+  const GramLaunch L =
+      plan_launch<W / 4>(srow0, n_srb, j_lo, j_hi, skip_lo, skip_hi, ns_active, G0, contig, min_chunks);
+  if (L.G <= 0) return DAL_OK;
+  hipLaunchKernelGGL((gram_csym_kernel<KS, W>), dim3(static_cast<unsigned>(L.G)), dim3(64 * W), 0, stream, rows,
                      static_cast<int>(srow0), static_cast<int>(n_srb), cols, static_cast<int>(jcol0),
                      static_cast<int>(j_lo), static_cast<int>(j_hi), static_cast<int>(skip_lo),
-                     static_cast<int>(skip_hi), static_cast<int>(ns_active), ldh, slice_off, static_cast<int>(cbk),
-                     static_cast<int>(n_chunks), reinterpret_cast<unsigned long long*>(acc), contig);
+                     static_cast<int>(skip_hi), static_cast<int>(ns_active), ldh, slice_off, L.chunk_j, L.n_chunks,
+                     reinterpret_cast<unsigned long long*>(acc), contig);
   DAL_RETURN_IF_LAUNCH_FAILED();
   return DAL_OK;
 }

@@ -7,8 +7,8 @@ all-gather), then every other column in one launch with its own shard as the
 skip range (dal/parallel.py ShardedSelector.exchange_density ->
 engine.PoolState.gram_accumulate).  Which (row super block P, 256-column block
 J) pairs a launch computes is the kernel's orientation rule,
-csrc/gram_sym.hip ``takes()``: P takes J (Q = J / 2) iff Q == P, or Q > P with
-P + Q even, or Q < P with P + Q odd, and J outside the skip range.  This file
+csrc/gram_schedule.hpp ``sb_takes()`` / ``GramSchedule::takes()``: P takes J
+(Q = J / 2) iff Q == P, or Q > P with P + Q even, or Q < P with P + Q odd, and J outside the skip range.  This file
 restates that rule and the two launches' ranges, checks that the ranks
 together take every unordered super-block pair exactly once, and bounds the
 per-rank pair counts (the work: every pair is the same 512 x 256 x D MFMA
@@ -28,7 +28,7 @@ CONFIGS = {"config3": 284_807, "config4": 2_000_000, "config2": 100_000}
 
 
 def takes(P, J, skip_lo=0, skip_hi=0):
-    """csrc/gram_sym.hip takes(): vectorised over arrays P (rows) x J (columns)."""
+    """csrc/gram_schedule.hpp GramSchedule::takes(): vectorised over arrays P (rows) x J (columns)."""
     P = np.asarray(P)[:, None]
     J = np.asarray(J)[None, :]
     Q = J >> 1
