@@ -132,6 +132,11 @@ SIGNATURES = {
     "dal_sort_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
     "dal_gram_entries": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "dal_cosine_pairs_error_bound": (c_double, [c_int64]),
+    "dal_cosine_pairs": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                 c_void_p, c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dal_cosine_pairs_resolve": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                         c_void_p, c_void_p]),
     "dal_rf_find_splits": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p,
                                    c_void_p, c_void_p, c_void_p]),
     "dal_rf_train_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32]),

@@ -4,16 +4,156 @@ The reference transposes the normalised pool so that points become columns
 (:34-37) and calls ``RowMatrix.columnSimilarities()`` (:38): the exact cosine
 of every pair i < j (threshold 0, no diagonal).  Returned here as COO arrays
 (i, j, value), the fields of the reference's MatrixEntry records.
+
+With a ``threshold`` the call returns only the pairs whose canonical fp64
+cosine reaches it (MLlib's ``columnSimilarities(threshold)``, exact here
+instead of sampled): an fp16 MFMA filter over the upper triangle of block
+pairs with a rigorous error bound, then the candidates inside the bound
+re-decided in canonical fp64.  The N x N matrix is never stored, so this form
+runs at pool scale.
 """
 from __future__ import annotations
 
+import math
+
 from .cosine_similarity import cosine_entries
 
+# Initial candidate capacity of a thresholded call without ``max_pairs``
+# (None: min(N (N - 1) / 2, max(2^20, 8 N))); the call retries once with the
+# count the first pass reported.
+PAIRS_INITIAL_CAP = None
 
-def column_similarities(pool, device=None):
-    """(i, j, cos(x_i, x_j)) for every pair i < j, row-major order."""
+
+def _split_operand(state):
+    """The pool's two-term fp16 split (the filter reads its H runs)."""
     import torch
 
+    from . import _lib
+    from .engine import _ptr, _stream
+
+    if state.gram == "sym":
+        return state.gram_operand()
+    if state._split is None:  # an "f32" pool: split its fp32 unit rows once
+        u, _ = state.normalized()
+        state._split = torch.empty((state.n_pad, 2 * state.d_pad), dtype=torch.int16, device=state.device)
+        _lib.call("dal_split_f16", _ptr(u), state.n_pad, state.d_pad, state.d_pad, _ptr(state._split),
+                  _stream(state.device))
+    return state._split
+
+
+def cosine_pair_candidates(state, threshold: float, cap: int, row_blocks=None, col_blocks=None):
+    """One filter call (dal_cosine_pairs) on a pool state: (keys int64 [cap],
+    approx fp32 [cap], count int64 [1], status int32 [1]) device tensors,
+    nothing synchronised.  keys[c] = (i << 32) | j for c < min(count, cap), in
+    no particular order.  row_blocks / col_blocks: (first, end) ranges of
+    256-row blocks (default: the whole pool); calls whose ranges tile the
+    blocks cover every pair exactly once."""
+    import torch
+
+    from . import _lib
+    from .engine import _ptr, _stream
+
+    dev = state.device
+    op = _split_operand(state)
+    nb = state.n_pad // 256
+    r_lo, r_hi = (0, nb) if row_blocks is None else (int(row_blocks[0]), int(row_blocks[1]))
+    c_lo, c_hi = (0, nb) if col_blocks is None else (int(col_blocks[0]), int(col_blocks[1]))
+    keys = torch.empty(max(int(cap), 1), dtype=torch.int64, device=dev)
+    approx = torch.empty(max(int(cap), 1), dtype=torch.float32, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    flags = _ptr(state.flags) if state.excluded.size else 0
+    if r_hi > r_lo and c_hi > c_lo:
+        _lib.call("dal_cosine_pairs", _ptr(op) + r_lo * 256 * 2 * state.d_pad * 2, r_lo, r_hi - r_lo, _ptr(op), 0,
+                  c_lo, min(c_hi, (state.n + 511) // 512 * 2), state.n, state.d_pad, flags, float(threshold),
+                  int(cap), _ptr(keys), _ptr(approx), _ptr(count), _ptr(status), _stream(dev))
+    return keys, approx, count, status
+
+
+def cosine_pair_values(state, keys, n_cand: int):
+    """Canonical fp64 cosines of the first ``n_cand`` candidate keys
+    (dal_cosine_pairs_resolve)."""
+    import torch
+
+    from . import _lib
+    from .engine import _ptr, _stream
+
+    values = torch.empty(int(n_cand), dtype=torch.float64, device=state.device)
+    if n_cand:
+        _lib.call("dal_cosine_pairs_resolve", _ptr(state.x), state.n, state.d, state.d, _ptr(state.norms()),
+                  _ptr(keys), int(n_cand), _ptr(values), _stream(state.device))
+    return values
+
+
+def _column_similarities_threshold(pool, threshold, device, max_pairs):
+    import torch
+
+    from ._lib import DAL_FLAG_CAND_OVERFLOW
+    from .engine import as_pool_state
+
+    try:
+        tau = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f"threshold must be a finite float in (-1, 1], not {threshold!r}") from None
+    if not math.isfinite(tau) or tau <= -1.0 or tau > 1.0:
+        raise ValueError(f"threshold must be a finite float in (-1, 1], not {threshold!r}")
+    if max_pairs is not None and int(max_pairs) < 0:
+        raise ValueError("max_pairs must be >= 0")
+    state = as_pool_state(pool, device=device)
+    if state.row_base or state.n_total != state.n:
+        raise ValueError("column_similarities(threshold=) needs the whole pool, not a row shard")
+    n = state.n
+    all_pairs = n * (n - 1) // 2
+    if max_pairs is not None:
+        cap = min(int(max_pairs), all_pairs)
+    elif PAIRS_INITIAL_CAP is not None:
+        cap = min(int(PAIRS_INITIAL_CAP), all_pairs)
+    else:
+        cap = min(all_pairs, max(1 << 20, 8 * n))
+    _split_operand(state)  # (raises the zero-norm flag into state.status)
+    if all_pairs == 0:
+        state.check_status()
+        return (torch.empty(0, dtype=torch.int64, device=state.device),
+                torch.empty(0, dtype=torch.int64, device=state.device),
+                torch.empty(0, dtype=torch.float64, device=state.device))
+    for attempt in range(2):
+        keys, _, count, status = cosine_pair_candidates(state, tau, cap)
+        n_cand, st, st_pool = torch.cat([count, status.to(torch.int64), state.status.to(torch.int64)]).tolist()
+        state.check_status(st_pool)
+        if not (st & DAL_FLAG_CAND_OVERFLOW):
+            break
+        if max_pairs is not None and n_cand > int(max_pairs):
+            raise RuntimeError(f"column_similarities: {n_cand} candidate pairs exceed max_pairs={int(max_pairs)}; "
+                               f"pass max_pairs >= {n_cand}")
+        if attempt:
+            raise RuntimeError(f"column_similarities: candidate count changed between passes ({n_cand} > {cap})")
+        cap = n_cand
+    values = cosine_pair_values(state, keys, n_cand)
+    keep = values >= tau
+    kept_keys, order = torch.sort(keys[:n_cand][keep])
+    return kept_keys >> 32, kept_keys & 0xFFFFFFFF, values[keep][order]
+
+
+def column_similarities(pool, threshold=None, device=None, max_pairs=None):
+    """(i, j, cos(x_i, x_j)) for every pair i < j, row-major order.
+
+    threshold=None: every pair, from the dense fp32 matrix (small N).
+
+    threshold=tau, a finite float in (-1, 1]: exactly the pairs whose canonical
+    fp64 cosine (u = x / ||x|| in fp64, sequential sum over the features,
+    multiply then add) is >= tau, as (i int64, j int64, value float64) device
+    tensors sorted by (i, j); ``value`` is that canonical cosine.  ``pool`` may
+    be an array or a PoolState (its split operand and norms are reused; rows
+    of its excluded set appear neither as i nor as j).  ``max_pairs`` bounds
+    the filter's candidate count (the returned pairs plus those within about
+    2^-10 below tau): exceeding it raises RuntimeError naming the needed count;
+    without it the call sizes its buffers itself and retries once."""
+    import torch
+
+    if threshold is not None:
+        return _column_similarities_threshold(pool, threshold, device, max_pairs)
+    if max_pairs is not None:
+        raise ValueError("max_pairs applies to a thresholded call")
     S = cosine_entries(pool, device=device)
     n = S.shape[0]
     ij = torch.triu_indices(n, n, offset=1, device=S.device)
@@ -239,4 +379,5 @@ def diversity_select(pool, labeled_idx, k: int, candidates=None, device=None, ro
     return Selection(scores=mx[cand], indices=out_idx, selected_scores=out_sc)
 
 
-__all__ = ["column_similarities", "max_cosine", "diversity_select", "LabeledSet"]
+__all__ = ["column_similarities", "cosine_pair_candidates", "cosine_pair_values", "max_cosine", "diversity_select",
+           "LabeledSet"]

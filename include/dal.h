@@ -569,6 +569,39 @@ int dal_rf_train(const float* x, int64_t n, int64_t d, int64_t ldx, const uint8_
 int dal_gram_entries(const float* u, int64_t n_pad, int64_t d_pad, int64_t ld, float* out,
                      dal_stream_t stream);
 
+/* ---- thresholded cosine pairs ---------------------------------------------
+ * similarity.py:34-38 with a threshold (MLlib's columnSimilarities(threshold),
+ * exact here): every pair i < j whose canonical fp64 cosine is >= threshold.
+ *
+ * dal_cosine_pairs is the filter: a symmetric fp16 MFMA product of the H runs
+ * of the split operand (dal_prep_split; rows = the operand of 256-row blocks
+ * row_block0 .., cols = the operand whose first row is block col_block0) over
+ * the block pairs P <= Q with P in [row_block0, row_block0 + n_row_blocks) and
+ * Q in [j_lo, j_hi), global block indices: calls whose ranges tile the blocks
+ * cover the upper triangle with no pair twice.  An entry is kept when its
+ * filter value (fp32, |value - canonical cosine| <=
+ * dal_cosine_pairs_error_bound(d_pad), about 2^-10) is >= threshold - bound
+ * (compared against an fp32 threshold rounded down), i < j < n_total, and
+ * neither row carries DAL_ROW_EXCLUDED in row_flags (nullable, indexed by
+ * global row) -- a superset of the answer.  Candidate c < cap is written as
+ * keys[c] = (i << 32) | j, approx[c] = the filter value, in no particular
+ * order; *count (zeroed by the caller) is advanced by every candidate, also
+ * past cap, where nothing is written and DAL_FLAG_CAND_OVERFLOW is set:
+ * *count is then the capacity to retry with.
+ *
+ * dal_cosine_pairs_resolve writes values[c] = the canonical cosine of
+ * candidate c: u = x / norm64 per element in fp64, sum_f u_if * u_jf over the
+ * d features in ascending f, multiply then add, no FMA (the oracle's
+ * max_cosine_canonical definition; symmetric in (i, j) bit for bit).
+ * Membership is values[c] >= threshold in fp64. */
+double dal_cosine_pairs_error_bound(int64_t d_pad);
+int dal_cosine_pairs(const uint16_t* rows, int64_t row_block0, int64_t n_row_blocks, const uint16_t* cols,
+                     int64_t col_block0, int64_t j_lo, int64_t j_hi, int64_t n_total, int64_t d_pad,
+                     const uint8_t* row_flags, double threshold, int64_t cap, uint64_t* keys, float* approx,
+                     unsigned long long* count, int32_t* dev_status, dal_stream_t stream);
+int dal_cosine_pairs_resolve(const float* x, int64_t n, int64_t d, int64_t ldx, const double* norm64,
+                             const uint64_t* keys, int64_t n_cand, double* values, dal_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
