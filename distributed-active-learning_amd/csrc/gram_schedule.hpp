@@ -38,7 +38,9 @@ DAL_HD bool sb_takes(I P, I Q) {
 //  contig: block g owns the g-th 1/G of the unit-major raw grid (HV = 1 only:
 //          form_ok);
 //  chunk:  unit u = (row unit u % n_ru, column chunk u / n_ru), dealt round-robin
-//          (all blocks sweep the same column chunks together: L2 / MALL reuse).
+//          (all blocks sweep the same column chunks together: L2 / MALL reuse);
+//          the kernel takes the units beyond each block's first from a counter
+//          instead, over every feature slice in one launch (GramClaimCursor).
 template <int HV>
 struct GramSchedule {
   static_assert(HV == 1 || HV == 2, "one or two super blocks per row unit");
@@ -159,6 +161,101 @@ struct GramCursor {
   }
   // half h's super block takes the current J?  (a half whose super block does not idles)
   DAL_HD bool acts(int h) const { return HV == 1 || s.takes_h(ru, h, J); }
+};
+
+// A block's walk over units it is handed one at a time (the kernel's walk
+// since round 10).  A unit index names (feature slice, segment): the chunk
+// form counts (slice * n_chunks + column chunk) * n_ru + row unit over every
+// slice of the launch -- slice slowest, chunk next, so blocks that take
+// consecutive indices sweep one column chunk together -- and the contiguous
+// form counts the block's own segments of its one slice.  The cursor never
+// decides which unit comes next: the block enters first_unit(), and whoever
+// drives the walk hands over each later unit with claimed(), one unit ahead --
+// from a counter shared by the launch's blocks (any order of the indices
+// first_unit() .. total() - 1, each once over the launch, visits every pair
+// once), or static_next() for the fixed deal of GramCursor.  An index at or
+// beyond total() ends the walk; claimed() refuses a unit without a pair
+// (claim again).  peek / advance / acts are GramCursor's.  new_unit: the
+// current pair (after peek(): the announced one) is the first of its unit, so
+// the unit behind it is to be claimed before the next peek().
+// A unit index is taken apart once, when it is handed over (claimed() keeps
+// the unit's slice, row unit, first taken column and end): peek() and
+// advance() divide nothing, and the kernel holds few scalars beside the
+// schedule's.
+template <int HV>
+struct GramClaimCursor {
+  const GramSchedule<HV>& s;
+  int n_slices;             // feature slices of the launch (contig: 1)
+  // the claimed unit behind the current one: its index (>= total(): none) and,
+  // if there is one (c_r >= 0), its slice, row unit, first taken raw column and end
+  int v_next = -1, c_slice = -1, c_ru = -1, c_r = -1, c_rhi = 0;
+  // the current pair
+  int slice = 0, ru = -1, r = -1, rhi_u = 0, J = -1;
+  // set by peek(): the next pair's raw column and column block (-1 without a next pair)
+  int next_r = -1, next_J = -1;
+  bool has_next = false, rows_change = false, new_unit = false;
+
+  DAL_HD GramClaimCursor(const GramSchedule<HV>& sched, int n_slices_)
+      : s(sched), n_slices(sched.contig ? 1 : n_slices_) {}
+  DAL_HD int total() const { return s.contig ? s.n_seg : n_slices * s.n_units(); }
+  DAL_HD int first_unit() const { return s.first_seg(); }
+  DAL_HD int static_next(int u) const { return u + s.seg_step(); }
+  // Hand over unit u as the one behind the current pair's.  false: u holds no
+  // pair (nothing taken, skipped columns, rows past the pool) -- hand over
+  // another one.  u >= total(): no unit follows.
+  DAL_HD bool claimed(int u) {
+    v_next = u;
+    c_r = -1;
+    if (u >= total()) return true;
+    const int sg = s.contig ? u : u % s.n_units();
+    c_slice = s.contig ? 0 : u / s.n_units();
+    c_ru = s.seg_ru(sg);
+    c_rhi = s.seg_rhi(sg);
+    c_r = s.first_r(c_ru, s.seg_rlo(sg), c_rhi);
+    return c_r >= 0;
+  }
+  // to the first pair of the unit handed over (the block's first); false: there is none
+  DAL_HD bool start() {
+    if (c_r < 0) return false;
+    open();
+    new_unit = true;
+    return true;
+  }
+  DAL_HD int next_slice() const { return new_unit ? c_slice : slice; }
+  DAL_HD int next_ru() const { return new_unit ? c_ru : ru; }
+  DAL_HD void peek() {
+    next_r = s.first_r(ru, r + 1, rhi_u);
+    new_unit = next_r < 0;
+    has_next = true;
+    rows_change = false;
+    if (new_unit) {
+      has_next = c_r >= 0;
+      next_r = c_r;
+      // (another slice of the same rows restarts them too: one flag serves the A reload and the flush)
+      rows_change = !has_next || c_ru != ru || c_slice != slice;
+    }
+    next_J = has_next ? s.jmap(next_r) : -1;
+  }
+  // to the pair peek() announced (has_next); true: the rows (row unit or slice) changed
+  DAL_HD bool advance() {
+    if (new_unit) {
+      open();
+    } else {
+      r = next_r;
+      J = next_J;
+    }
+    return rows_change;
+  }
+  DAL_HD bool acts(int h) const { return HV == 1 || s.takes_h(ru, h, J); }
+
+ private:
+  DAL_HD void open() {
+    slice = c_slice;
+    ru = c_ru;
+    rhi_u = c_rhi;
+    r = c_r;
+    J = s.jmap(r);
+  }
 };
 
 // ---------------------------------------------------------------------------
@@ -283,13 +380,15 @@ inline int64_t choose_chunks(int64_t srow0, int64_t n_srb, int64_t lo, int64_t h
 
 // The launch: its column chunks (chunk form: choose_chunks with at least
 // min_chunks) and its grid -- the G0 blocks the device holds, or fewer when
-// there are fewer pairs (contig) or units (chunk) to deal.  G == 0: no work.
+// there are fewer pairs (contig) or units (chunk, over the launch's n_slices
+// feature slices) to deal.  G == 0: no work.
 struct GramLaunch {
   int chunk_j, n_chunks, G;
+  int units;  // chunk form: the launch's units over its slices (contig: 0)
 };
 template <int HV>
 GramLaunch plan_launch(int64_t srow0, int64_t n_srb, int64_t j_lo, int64_t j_hi, int64_t skip_lo, int64_t skip_hi,
-                       int64_t ns_active, int64_t G0, int contig, int64_t min_chunks) {
+                       int64_t ns_active, int64_t G0, int contig, int64_t min_chunks, int64_t n_slices = 1) {
   int64_t cbk = j_hi - j_lo, n_chunks = 1;
   if (!contig)
     column_chunks(j_hi - j_lo,
@@ -298,8 +397,9 @@ GramLaunch plan_launch(int64_t srow0, int64_t n_srb, int64_t j_lo, int64_t j_hi,
   const GramSchedule<HV> s(static_cast<int>(srow0), static_cast<int>(n_srb), static_cast<int>(j_lo),
                            static_cast<int>(j_hi), static_cast<int>(skip_lo), static_cast<int>(skip_hi),
                            static_cast<int>(ns_active), static_cast<int>(cbk), static_cast<int>(n_chunks), contig);
-  const int64_t work = contig ? s.raw() : s.n_units();
-  return {static_cast<int>(cbk), static_cast<int>(n_chunks), static_cast<int>(work < G0 ? (work > 0 ? work : 0) : G0)};
+  const int64_t work = contig ? s.raw() : s.n_units() * n_slices;
+  return {static_cast<int>(cbk), static_cast<int>(n_chunks), static_cast<int>(work < G0 ? (work > 0 ? work : 0) : G0),
+          contig ? 0 : static_cast<int>(work)};
 }
 
 }  // namespace dal

@@ -24,6 +24,16 @@
 // C++ shared by the kernel and the launcher; tests/test_gram_schedule.py
 // enumerates every block's walk on the CPU).
 //
+// Launches and units (round 10).  The round-robin column-chunk form runs ONE
+// launch per density call: its units are (feature slice, column chunk, row
+// unit), slice slowest, and a block takes unit g first and every later unit
+// from a device counter (g_claim; GramClaimCursor in gram_schedule.hpp,
+// walked on the CPU by tests/test_gram_claim_schedule.py), so a fast block
+// takes more units and the launch ends within one unit of its last block --
+// before, units were dealt u = g + k G and each slice was a launch with a tail
+// of its own.  The contiguous form (small column operands) keeps its static
+// shares and one launch per slice, walked through the same cursor.
+//
 // Compensation and column sums.  Both MFMA operands hold H only: the MFMAs
 // form the fp16 Gram T_ij = <H_i, H_j> on the taken pairs, one product per
 // feature pair.  Every other term of <u~_i, u~_j> is linear in the columns and
@@ -55,6 +65,8 @@
 // slice (the L run is not read here).  KS = 128 for d_pad % 128 == 0 (the
 // H-only A side frees the registers the L fragments held), else 64, or 32.
 #include <stdlib.h>
+
+#include <mutex>
 
 #include "common.hpp"
 #include "gram_schedule.hpp"
@@ -206,6 +218,17 @@ struct Cfg {
 // the 8-wave form folds like the 4-wave one (one bound per KS)
 static_assert(Cfg<128, 8>::CHAIN <= Cfg<128, 4>::CHARGED, "block forms share one bound");
 
+// Unit counters of the chunk-form launches (see the pair loop): next = units
+// claimed beyond the G the blocks enter by themselves, done = blocks that
+// left.  Library-owned (the interface has no workspace for them), zero at load
+// and left zero by every launch's last block.  One slot per launch in flight:
+// claim_slot_of hands them out on the host.
+struct ClaimSlot {
+  unsigned next, done;
+};
+constexpr int kClaimSlots = 64;
+__device__ ClaimSlot g_claim[kClaimSlots];
+
 // Row sums of the taken pairs (the column sums of every pair are added in
 // closed form by dal_gram_sym_residual, see the header): for each pair (P,
 // J) the taker's rows accumulate <H_i, H_j> over J's 256 columns.
@@ -213,12 +236,13 @@ template <int KS, int W>
 __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
     const uint16_t* __restrict__ urows, int srow0, int n_srb,
     const uint16_t* __restrict__ ucols, int jcol0, int j_lo, int j_hi, int skip_lo, int skip_hi,
-    int ns_active, int64_t ldh, int slice_off, int chunk_j, int n_chunks,
-    unsigned long long* __restrict__ acc_out, int contig) {
+    int ns_active, int64_t ldh, int slice_off, int n_slices, int chunk_j, int n_chunks,
+    unsigned long long* __restrict__ acc_out, int contig, int claim_slot) {
   using C = Cfg<KS, W>;
   constexpr int HV = C::HALVES;
   __shared__ __attribute__((aligned(16))) float4 lds[2 * C::F4];
   __shared__ double rowacc[HV * kSB];
+  __shared__ int claim_lds[2];  // a claimed unit index, lane 0 -> the block (two words: see claim_begin)
 
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -254,11 +278,16 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
   const unsigned rowbytes = static_cast<unsigned>(ldh * 2);
   const unsigned dst0 = __builtin_amdgcn_readfirstlane(
       static_cast<unsigned>(reinterpret_cast<uintptr_t>((AS3 float4*)(lds + wave * C::PIECES * 64))));
-  // stage h of 256-column block J into LDS buffer buf.  Inline asm so the
-  // compiler does not track the DMA on vmcnt (block_sync waits for it).
-  auto issue = [&](int buf, int J, int h) {
+  // stage h of 256-column block J of feature slice `slice` into LDS buffer
+  // buf.  Inline asm so the compiler does not track the DMA on vmcnt
+  // (block_sync waits for it).
+  auto issue = [&](int buf, int J, int h, int slice) {
+    // (the cursor's values are uniform, but the compiler may hold them in
+    // vector registers when the scalar ones run out: the asm needs scalars)
+    J = __builtin_amdgcn_readfirstlane(J);
+    slice = __builtin_amdgcn_readfirstlane(slice);
     const char* sbase = reinterpret_cast<const char*>(
-        ucols + (static_cast<int64_t>(J - jcol0) * 256 + h * C::SC) * ldh + slice_off);
+        ucols + (static_cast<int64_t>(J - jcol0) * 256 + h * C::SC) * ldh + slice_off + slice * 2 * KS);
     const unsigned fl = fresh_lane();
     const unsigned lrow = fl / C::SLOTS + static_cast<unsigned>(wave * C::PIECES * RPP);
     const unsigned vlane = lrow * rowbytes + (((fl % C::SLOTS) ^ static_cast<unsigned>(C::swz(lrow))) << 4);
@@ -281,10 +310,10 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
   // (P = this wave's super block of the unit), features of k-step c and lane
   // group lq
   f16x8 ah[C::RT][C::NKS];
-  auto load_a = [&](int ru) {
+  auto load_a = [&](int ru, int slice) {
     const int P = sched.rowP(ru, half);
     if (HV > 1 && !sched.live(P)) return;  // (this half idles for the unit)
-    const uint16_t* pb = urows + static_cast<int64_t>(P - srow0) * kSB * ldh + slice_off;
+    const uint16_t* pb = urows + static_cast<int64_t>(P - srow0) * kSB * ldh + slice_off + slice * 2 * KS;
     const unsigned fl = fresh_lane();
     const unsigned lrow = static_cast<unsigned>((wave4 * 128 + (fl & 15)) * ldh + (fl >> 4) * 8);
     const unsigned tstep = static_cast<unsigned>(16 * ldh);
@@ -377,29 +406,87 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
   };
   auto stage_sync = [&]() { block_sync(); };
 
-  GramCursor<HV> cur(sched);
-  if (!cur.start()) return;
-  issue(0, cur.J, 0);
-  load_a(cur.ru);
+  // Units.  The block enters unit g; every later one comes from the launch's
+  // counter (claim_slot >= 0: G + the counter's value, so the blocks take the
+  // remaining units in the order they finish -- a block's speed decides its
+  // share, and the launch ends within one unit of the last block), or from
+  // the fixed deal (claim_slot < 0: the contiguous form, no unit beyond the
+  // blocks' first, or no free counter).
+  // A claim is one lane's agent-scope add; its value reaches the block through
+  // claim_lds at the next barrier.  Two words take the claims in turn: between
+  // the block's reads of a word and lane 0's next write to it lies the barrier
+  // of the claim between them.  The counter words are touched by agent-scope
+  // atomics only (no other data is handed between blocks), so no fence is
+  // needed.
+  GramClaimCursor<HV> cur(sched, n_slices);
+  const bool dyn = claim_slot >= 0;
+  int claim_par = 0;  // word of claim_lds of the next claim
+  auto claim_begin = [&]() {
+    if (dyn && tid == 0)
+      claim_lds[claim_par] =
+          G + static_cast<int>(__hip_atomic_fetch_add(&g_claim[claim_slot].next, 1u, __ATOMIC_RELAXED,
+                                                      __HIP_MEMORY_SCOPE_AGENT));
+  };
+  auto claim_end = [&](int last) {  // last: the unit handed over before; (behind a barrier after claim_begin)
+    const int u = dyn ? __builtin_amdgcn_readfirstlane(claim_lds[claim_par]) : cur.static_next(last);
+    claim_par ^= 1;
+    return u;
+  };
+  // hand the cursor the claim begun before the last barrier; a unit without a
+  // pair is skipped by claiming again
+  auto claim_take = [&]() {
+    while (!cur.claimed(claim_end(cur.v_next))) {
+      claim_begin();
+      if (dyn) block_sync();
+    }
+  };
+  // The last block to leave (every claim of the launch has returned by then)
+  // zeroes the counter: the next launch that uses the slot finds it ready, in
+  // stream order and under graph replay, without a memset.
+  auto leave = [&]() {
+    if (dyn && tid == 0) {
+      const unsigned before =
+          __hip_atomic_fetch_add(&g_claim[claim_slot].done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (before + 1 == static_cast<unsigned>(G)) {
+        __hip_atomic_store(&g_claim[claim_slot].next, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&g_claim[claim_slot].done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  };
+  if (!cur.claimed(cur.first_unit())) {  // (unit g is empty)
+    claim_begin();
+    if (dyn) block_sync();
+    claim_take();
+  }
+  if (!cur.start()) {
+    leave();
+    return;
+  }
+  issue(0, cur.J, 0, cur.slice);
+  load_a(cur.ru, cur.slice);
+  claim_begin();  // read behind the next barrier, as after every advance() into a new unit
   int buf = 0;       // LDS stage buffer of the next stage to compute
   int flushRU = -1;  // row unit whose sums wait in rowacc
 
   while (true) {
-    cur.peek();
     // this wave's super block takes J?  (a half whose super block does not idles)
     const bool act = cur.acts(half);
 
 #pragma unroll
     for (int s = 0; s < C::SPP; ++s) {
       stage_sync();
-      if (s == 0 && flushRU >= 0) {
-        flush_rows(flushRU);
-        flushRU = -1;
+      if (s == 0) {
+        if (cur.new_unit) claim_take();
+        cur.peek();
+        if (flushRU >= 0) {
+          flush_rows(flushRU);
+          flushRU = -1;
+        }
       }
       if (s + 1 < C::SPP) {
-        issue(buf ^ 1, cur.J, s + 1);
+        issue(buf ^ 1, cur.J, s + 1, cur.slice);
       } else if (cur.has_next) {
-        issue(buf ^ 1, cur.next_J, 0);
+        issue(buf ^ 1, cur.next_J, 0, cur.next_slice());
       }
       if (act) {  // (wave-uniform)
         compute(buf, s % C::SPF == 0);
@@ -410,10 +497,12 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
 
     if (cur.rows_change) flushRU = cur.ru;
     if (!cur.has_next) break;
-    if (cur.advance()) load_a(cur.ru);
+    if (cur.advance()) load_a(cur.ru, cur.slice);
+    if (cur.new_unit) claim_begin();
   }
   block_sync();
   if (flushRU >= 0) flush_rows(flushRU);
+  leave();
 }
 // ---------------------------------------------------------------------------
 // Residual of the compensation (see the header).  Three launches:
@@ -782,10 +871,35 @@ int device_cus() {
 #define DAL_GRAM_WAVES8 1
 #endif
 
+// The counter slot of a chunk-form launch on `stream`, -1: none (the launch
+// then deals its units statically; the bits are the same).  Two launches may
+// share a slot only if they cannot be in flight together, and launches on one
+// stream run in order, so every stream keeps a slot of its own for the life
+// of the process: at most kClaimSlots streams get one, whatever the host
+// threads that launch on them.  g_claim exists once per device and a stream
+// belongs to one device, so devices need no slots of their own.
+// hipStreamPerThread is one handle for a stream per host thread and gets
+// none.  (A graph replays with the slot of the stream it was captured on: do
+// not replay it beside launches on that stream.)
+int claim_slot_of(hipStream_t stream) {
+  static std::mutex mu;
+  static hipStream_t owner[kClaimSlots];
+  static int n_owners = 0;
+  if (stream == hipStreamPerThread) return -1;
+  std::lock_guard<std::mutex> lock(mu);
+  for (int i = 0; i < n_owners; ++i)
+    if (owner[i] == stream) return i;
+  if (n_owners == kClaimSlots) return -1;
+  owner[n_owners] = stream;
+  return n_owners++;
+}
+
+// n_slices feature slices from slice_off on in one launch (chunk form; the
+// contiguous form takes one slice per launch).
 template <int KS, int W>
 int launch_csym_w(const uint16_t* rows, int64_t srow0, int64_t n_srb, const uint16_t* cols, int64_t jcol0,
                   int64_t j_lo, int64_t j_hi, int64_t skip_lo, int64_t skip_hi, int64_t ns_active, int64_t ldh,
-                  int slice_off, int64_t* acc, int grid_blocks, int contig, int64_t min_chunks,
+                  int slice_off, int n_slices, int64_t* acc, int grid_blocks, int contig, int64_t min_chunks,
                   hipStream_t stream) {
   // grid_blocks counts 4-wave blocks (two per CU); 8-wave blocks are one per CU
   constexpr int kOcc = Cfg<KS, W>::OCC;
@@ -794,13 +908,16 @@ int launch_csym_w(const uint16_t* rows, int64_t srow0, int64_t n_srb, const uint
   const int G0 = G0r > 0 ? G0r : 1;  // (a one-block grid in the 8-wave form)
   if (!GramSchedule<W / 4>::form_ok(contig)) return DAL_ERR_ARG;
   const GramLaunch L =
-      plan_launch<W / 4>(srow0, n_srb, j_lo, j_hi, skip_lo, skip_hi, ns_active, G0, contig, min_chunks);
+      plan_launch<W / 4>(srow0, n_srb, j_lo, j_hi, skip_lo, skip_hi, ns_active, G0, contig, min_chunks, n_slices);
   if (L.G <= 0) return DAL_OK;
+  if (contig && n_slices != 1) return DAL_ERR_ARG;
+  // units beyond the G the blocks enter by themselves are claimed from a counter (none left: no counter)
+  const int slot = !contig && L.units > L.G ? claim_slot_of(stream) : -1;
   hipLaunchKernelGGL((gram_csym_kernel<KS, W>), dim3(static_cast<unsigned>(L.G)), dim3(64 * W), 0, stream, rows,
                      static_cast<int>(srow0), static_cast<int>(n_srb), cols, static_cast<int>(jcol0),
                      static_cast<int>(j_lo), static_cast<int>(j_hi), static_cast<int>(skip_lo),
-                     static_cast<int>(skip_hi), static_cast<int>(ns_active), ldh, slice_off, L.chunk_j, L.n_chunks,
-                     reinterpret_cast<unsigned long long*>(acc), contig);
+                     static_cast<int>(skip_hi), static_cast<int>(ns_active), ldh, slice_off, n_slices, L.chunk_j,
+                     L.n_chunks, reinterpret_cast<unsigned long long*>(acc), contig, slot);
   DAL_RETURN_IF_LAUNCH_FAILED();
   return DAL_OK;
 }
@@ -814,7 +931,7 @@ int launch_csym_w(const uint16_t* rows, int64_t srow0, int64_t n_srb, const uint
 template <int KS>
 int launch_csym(const uint16_t* rows, int64_t srow0, int64_t n_srb, const uint16_t* cols, int64_t jcol0,
                 int64_t j_lo, int64_t j_hi, int64_t skip_lo, int64_t skip_hi, int64_t ns_active, int64_t ldh,
-                int slice_off, int64_t* acc, int grid_blocks, hipStream_t stream) {
+                int n_slices, int64_t* acc, int grid_blocks, hipStream_t stream) {
   // contiguous equal shares of the pair grid per block for a small column
   // operand (<= 32 MB at KS 32 / 128), else round-robin column chunks whose
   // blocks sweep the same column stages together (a small KS-64 operand in as
@@ -824,12 +941,23 @@ int launch_csym(const uint16_t* rows, int64_t srow0, int64_t n_srb, const uint16
   const bool small = col_bytes <= (int64_t{DAL_GRAM_SMALL_MB} << 20);
   const int contig = col_bytes <= (int64_t{DAL_GRAM_CONTIG_MB} << 20) && !(KS == 64 && DAL_GRAM_KS64_CHUNKED);
   const int64_t min_chunks = small ? DAL_GRAM_MIN_CHUNKS_SMALL : DAL_GRAM_MIN_CHUNKS;
-  if constexpr ((KS == 128 && DAL_GRAM_WAVES8) || (KS == 64 && DAL_GRAM_W8_KS64))
-    if (!contig)
-      return launch_csym_w<KS, 8>(rows, srow0, n_srb, cols, jcol0, j_lo, j_hi, skip_lo, skip_hi, ns_active, ldh,
-                                  slice_off, acc, grid_blocks, contig, min_chunks, stream);
-  return launch_csym_w<KS, 4>(rows, srow0, n_srb, cols, jcol0, j_lo, j_hi, skip_lo, skip_hi, ns_active, ldh,
-                              slice_off, acc, grid_blocks, contig, min_chunks, stream);
+  // the chunk form covers every slice in one launch, the contiguous form one slice per launch
+  const int per_launch = contig ? 1 : n_slices;
+  for (int s0 = 0; s0 < n_slices; s0 += per_launch) {
+    const int so = s0 * 2 * KS;  // halves: slice s starts at s * 2 * KS
+    int rc;
+    if constexpr ((KS == 128 && DAL_GRAM_WAVES8) || (KS == 64 && DAL_GRAM_W8_KS64))
+      if (!contig) {
+        rc = launch_csym_w<KS, 8>(rows, srow0, n_srb, cols, jcol0, j_lo, j_hi, skip_lo, skip_hi, ns_active, ldh, so,
+                                  per_launch, acc, grid_blocks, contig, min_chunks, stream);
+        if (rc != DAL_OK) return rc;
+        continue;
+      }
+    rc = launch_csym_w<KS, 4>(rows, srow0, n_srb, cols, jcol0, j_lo, j_hi, skip_lo, skip_hi, ns_active, ldh, so,
+                              per_launch, acc, grid_blocks, contig, min_chunks, stream);
+    if (rc != DAL_OK) return rc;
+  }
+  return DAL_OK;
 }
 
 struct ResidualLayout {
@@ -918,22 +1046,16 @@ extern "C" int dal_gram_rowsum_sym_skip(const uint16_t* rows, int64_t row_block0
   hipStream_t st = as_stream(stream);
   const int ks = split_ks(d_pad);
   const int64_t ldh = 2 * d_pad;
-  for (int64_t off = 0; off < d_pad; off += ks) {
-    const int so = static_cast<int>(2 * off);  // halves: slice s starts at s * 2 * KS
-    const int64_t s0 = row_block0 / 2, ns = n_row_blocks / 2, na = nb_active / 2;
-    int rc;
-    if (ks == 32)
-      rc = launch_csym<32>(rows, s0, ns, cols, col_block0, j_lo, j_hi, skip_lo, skip_hi, na, ldh, so, acc,
+  const int n_slices = static_cast<int>(d_pad / ks);
+  const int64_t s0 = row_block0 / 2, ns = n_row_blocks / 2, na = nb_active / 2;
+  if (ks == 32)
+    return launch_csym<32>(rows, s0, ns, cols, col_block0, j_lo, j_hi, skip_lo, skip_hi, na, ldh, n_slices, acc,
                            grid_blocks, st);
-    else if (ks == 64)
-      rc = launch_csym<64>(rows, s0, ns, cols, col_block0, j_lo, j_hi, skip_lo, skip_hi, na, ldh, so, acc,
+  if (ks == 64)
+    return launch_csym<64>(rows, s0, ns, cols, col_block0, j_lo, j_hi, skip_lo, skip_hi, na, ldh, n_slices, acc,
                            grid_blocks, st);
-    else
-      rc = launch_csym<128>(rows, s0, ns, cols, col_block0, j_lo, j_hi, skip_lo, skip_hi, na, ldh, so, acc,
-                            grid_blocks, st);
-    if (rc != DAL_OK) return rc;
-  }
-  return DAL_OK;
+  return launch_csym<128>(rows, s0, ns, cols, col_block0, j_lo, j_hi, skip_lo, skip_hi, na, ldh, n_slices, acc,
+                          grid_blocks, st);
 }
 
 extern "C" int dal_gram_rowsum_sym(const uint16_t* rows, int64_t row_block0, int64_t n_row_blocks,

@@ -66,10 +66,14 @@ def stamped(lib, launch, max_blocks):
     a = a[(a[:, 1] > 0) & (a[:, 3] > a[:, 1])]
     clk = (a[:, 2] - a[:, 0]) / (a[:, 3] - a[:, 1]) * 100e6
     span_us = (a[:, 3].max() - a[:, 1].min()) / 100.0
+    end_us = (a[:, 3] - a[:, 1].min()) / 100.0  # block end times from the first block's entry
     return dict(warm_launches=n, launch_ms=e0.elapsed_time(e1) / 10, blocks=int(a.shape[0]),
                 clock_ghz_median=float(np.median(clk)) / 1e9, clock_ghz_p10=float(np.percentile(clk, 10)) / 1e9,
                 clock_ghz_p90=float(np.percentile(clk, 90)) / 1e9,
-                block_us_median=float(np.median(a[:, 3] - a[:, 1])) / 100.0, stamped_span_us=span_us)
+                block_us_median=float(np.median(a[:, 3] - a[:, 1])) / 100.0, stamped_span_us=span_us,
+                end_us_p10=float(np.percentile(end_us, 10)), end_us_p50=float(np.median(end_us)),
+                end_us_p90=float(np.percentile(end_us, 90)), end_us_max=float(end_us.max()),
+                end_median_over_span=float(np.median(end_us)) / span_us)
 
 
 def gram_workload(lib, n, d, dist):
