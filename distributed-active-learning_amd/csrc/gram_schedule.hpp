@@ -32,9 +32,10 @@ DAL_HD bool sb_takes(I P, I Q) {
 // (P, J) over row super blocks P and 256-column blocks J in [j_lo, j_hi) minus
 // [skip_lo, skip_hi), as segments (row unit, raw column range [rlo, rhi))
 // walked by a raw column cursor r (J = jmap(r)).  A row unit is one super
-// block (HV = 1) or two of the same parity, P and P + 2 (HV = 2: they take
-// the same column blocks but near the diagonal, so one B stage feeds both; a
-// half whose super block does not take J idles):
+// block (HV = 1) or HV of the same parity out of 2 HV consecutive ones, P,
+// P + 2, ... (HV = 2, 4: they take the same column blocks but near the
+// diagonal, so one B stage feeds all; a part whose super block does not take J
+// idles):
 //  contig: block g owns the g-th 1/G of the unit-major raw grid (HV = 1 only:
 //          form_ok);
 //  chunk:  unit u = (row unit u % n_ru, column chunk u / n_ru), dealt round-robin
@@ -43,7 +44,7 @@ DAL_HD bool sb_takes(I P, I Q) {
 //          instead, over every feature slice in one launch (GramClaimCursor).
 template <int HV>
 struct GramSchedule {
-  static_assert(HV == 1 || HV == 2, "one or two super blocks per row unit");
+  static_assert(HV == 1 || HV == 2 || HV == 4, "one, two or four super blocks per row unit");
   // the contiguous form indexes its segments by super block, not by row unit
   static constexpr bool form_ok(int contig) { return HV == 1 || !contig; }
 
@@ -59,7 +60,7 @@ struct GramSchedule {
                       int chunk_j_, int n_chunks_, int contig_, int G_ = 1, int g_ = 0)
       : srow0(srow0_), n_srb(n_srb_), j_lo(j_lo_), j_hi(j_hi_), skip_lo(skip_lo_), skip_hi(skip_hi_),
         ns_active(ns_active_), chunk_j(chunk_j_), n_chunks(n_chunks_), contig(contig_), G(G_), g(g_) {
-    n_ru = HV == 1 ? n_srb : 2 * ((n_srb + 3) / 4);
+    n_ru = HV == 1 ? n_srb : 2 * ((n_srb + 2 * HV - 1) / (2 * HV));
     sk_lo = skip_lo > j_lo ? skip_lo : j_lo;
     const int sk_hi = skip_hi < j_hi ? skip_hi : j_hi;
     skl = contig && sk_hi > sk_lo ? sk_hi - sk_lo : 0;
@@ -76,7 +77,9 @@ struct GramSchedule {
   DAL_HD int first_seg() const { return contig ? 0 : g; }
   DAL_HD int seg_step() const { return contig ? 1 : G; }
 
-  DAL_HD int rowP(int ru, int h) const { return HV == 1 ? srow0 + ru : srow0 + 4 * (ru >> 1) + (ru & 1) + 2 * h; }
+  DAL_HD int rowP(int ru, int h) const {
+    return HV == 1 ? srow0 + ru : srow0 + 2 * HV * (ru >> 1) + (ru & 1) + 2 * h;
+  }
   DAL_HD bool live(int P) const { return P < srow0 + n_srb && P < ns_active; }
   DAL_HD int seg_ru(int u) const { return contig ? static_cast<int>(ka / nje) + u : u % n_ru; }
   DAL_HD int seg_rlo(int u) const {
@@ -94,7 +97,11 @@ struct GramSchedule {
   }
   // the unit's super block h takes J (and exists)
   DAL_HD bool takes_h(int ru, int h, int J) const { return live(rowP(ru, h)) && takes(rowP(ru, h), J); }
-  DAL_HD bool takes_u(int ru, int J) const { return takes_h(ru, 0, J) || (HV == 2 && takes_h(ru, HV - 1, J)); }
+  DAL_HD bool takes_u(int ru, int J) const {
+    for (int h = 0; h < HV; ++h)
+      if (takes_h(ru, h, J)) return true;
+    return false;
+  }
   // the first raw column in [r, rhi) the unit takes, -1: none
   DAL_HD int first_r(int ru, int r, int rhi) const {
     if constexpr (HV == 1) {
@@ -164,7 +171,8 @@ struct GramCursor {
 };
 
 // A block's walk over units it is handed one at a time (the kernel's walk
-// since round 10).  A unit index names (feature slice, segment): the chunk
+// since round 10).  A unit index names (feature slice, segment) -- the wide
+// form (HV = 4) passes its 64-feature sub-slices as the slices --: the chunk
 // form counts (slice * n_chunks + column chunk) * n_ru + row unit over every
 // slice of the launch -- slice slowest, chunk next, so blocks that take
 // consecutive indices sweep one column chunk together -- and the contiguous
@@ -297,7 +305,7 @@ inline void column_chunks(int64_t nj, int64_t nc, int64_t* chunk_j, int64_t* n_c
 
 // The most pairs any block of a G0-block grid multiplies with nc requested
 // column chunks (a two-super-block unit costs the pairs of the busier one:
-// they take the same column blocks but near the diagonal).
+// they take the same column blocks but near the diagonal; so of four).
 template <int HV>
 int64_t chunked_max_load(int64_t srow0, int64_t n_srb, int64_t lo, int64_t hi, int64_t skip_lo, int64_t skip_hi,
                          int64_t ns_active, int64_t G0, int64_t nc, int64_t* n_chunks) {
@@ -358,8 +366,9 @@ inline int64_t choose_chunks(int64_t srow0, int64_t n_srb, int64_t lo, int64_t h
     if (c > 1 && (nj + c - 1) / c == (nj + c - 2) / (c - 1)) continue;  // the same chunks as c - 1
     ++tried;
     int64_t ncc;
-    const int64_t mx = hv == 1 ? chunked_max_load<1>(srow0, n_srb, lo, hi, skip_lo, skip_hi, ns_active, G0, c, &ncc)
-                               : chunked_max_load<2>(srow0, n_srb, lo, hi, skip_lo, skip_hi, ns_active, G0, c, &ncc);
+    const int64_t mx = hv == 1   ? chunked_max_load<1>(srow0, n_srb, lo, hi, skip_lo, skip_hi, ns_active, G0, c, &ncc)
+                       : hv == 2 ? chunked_max_load<2>(srow0, n_srb, lo, hi, skip_lo, skip_hi, ns_active, G0, c, &ncc)
+                                 : chunked_max_load<4>(srow0, n_srb, lo, hi, skip_lo, skip_hi, ns_active, G0, c, &ncc);
     cand.emplace_back(ncc, mx);
     if (best_max < 0 || mx < best_max) best_max = mx;
   }

@@ -25,10 +25,11 @@
 // enumerates every block's walk on the CPU).
 //
 // Launches and units (round 10).  The round-robin column-chunk form runs ONE
-// launch per density call: its units are (feature slice, column chunk, row
-// unit), slice slowest, and a block takes unit g first and every later unit
-// from a device counter (g_claim; GramClaimCursor in gram_schedule.hpp,
-// walked on the CPU by tests/test_gram_claim_schedule.py), so a fast block
+// launch per density call: its units are (feature slice -- in the wide form
+// below, 64-feature sub-slice --, column chunk, row unit), slice slowest, and a
+// block takes unit g first and every later unit from a device counter
+// (g_claim; GramClaimCursor in gram_schedule.hpp, walked on the CPU by
+// tests/test_gram_claim_schedule.py and test_gram_schedule_wide.py), so a fast block
 // takes more units and the launch ends within one unit of its last block --
 // before, units were dealt u = g + k G and each slice was a launch with a tail
 // of its own.  The contiguous form (small column operands) keeps its static
@@ -55,15 +56,24 @@
 // atomics); the residual is an fp64 dot in a fixed order rounded to 2^-32.
 // The density bits are identical for any grid, column split or GPU count.
 //
-// MI355X design: block = 4 waves x 128 rows (one super block; at KS 128 with
-// the round-robin schedule 8 waves, two super blocks P and P + 2 sharing each
-// B stage), A fragments (8 row tiles x KS features of H) in registers; B
-// stages in a 2-deep LDS ring filled by global_load_lds_dwordx4 (source-side
-// XOR swizzle -> conflict-free ds_read_b128).  One accumulator chain per 16-row
-// tile carries its row sums through the MFMAs and is folded to the LDS row
-// accumulator every FOLD columns.  A stage holds the H run of each column's
-// slice (the L run is not read here).  KS = 128 for d_pad % 128 == 0 (the
-// H-only A side frees the registers the L fragments held), else 64, or 32.
+// MI355X design: block = 4 waves x 128 rows (one super block), A fragments (8
+// row tiles x KS features of H) in registers; B stages in a 2-deep LDS ring
+// filled by global_load_lds_dwordx4 (source-side XOR swizzle -> conflict-free
+// ds_read_b128).  One accumulator chain per 16-row tile (KS 128: per tile and
+// 64-feature half) carries its row sums through the MFMAs and is folded to
+// the LDS row accumulator every FOLD columns.  A stage holds the H run of each
+// column's slice (the L run is not read here).  KS = 128 for d_pad % 128 == 0
+// (the H-only A side frees the registers the L fragments held), else 64, or 32.
+//
+// The wide form (round 11; KS 128 with the round-robin schedule, the flagship
+// shape): 8 waves x 256 rows, four super blocks P, P + 2, P + 4, P + 6 share
+// each B stage.  The same 128 A registers hold 16 row tiles x 64 features, so
+// the block walks every slice as two 64-feature sub-slices (the operand keeps
+// its KS-128 layout; a staged column row is the 128 B of one half of its H
+// run, the 8-slot swizzle of KS 64).  One 32 KiB stage is a whole 256-column
+// pair and feeds 512 MFMAs per wave; a B fragment read feeds 16.  Against two
+// super blocks per block (rounds 4-10) the staged bytes, B reads, barriers
+// and DMA issue per MFMA halve.
 #include <stdlib.h>
 
 #include <mutex>
@@ -85,36 +95,22 @@ __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
-// One step of a reduce-scatter over the 16 lanes of a DPP row: lanes whose
-// select bit is clear keep v[k] (k < H) summed with their partner's, lanes
-// whose bit is set keep v[k + H]; CTRL is a DPP permutation pairing each lane
-// with a lane of the opposite bit (row_mirror, row_half_mirror, quad swaps).
-template <int H, int CTRL, int N = 32>
-__device__ __forceinline__ void rs_step(float (&v)[N], bool hi) {
-#pragma unroll
-  for (int k = 0; k < H; ++k) {
-    const float keep = hi ? v[k + H] : v[k];
-    const float send = hi ? v[k] : v[k + H];
-    v[k] = keep + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), CTRL,
-                                                                        0xF, 0xF, false));
-  }
-}
-
-// Reduce-scatter of N values over the 16 lanes of a DPP row (N = 16: lane li
-// ends with the 16-lane sum of value li; N = 8: of value li & 7).
-template <int N>
-__device__ __forceinline__ void row_sum_scatter(float (&v)[N], int li) {
-  if constexpr (N >= 16) {
-    rs_step<N / 2, 0x140, N>(v, li & 8);
-  } else {
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-      v[k] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v[k]), 0x140, 0xF,
-                                                                   0xF, false));
-  }
-  rs_step<N >= 16 ? 4 : N / 2, 0x141, N>(v, li & 4);
-  rs_step<N >= 16 ? 2 : N / 4, 0x4E, N>(v, li & 2);
-  rs_step<N >= 16 ? 1 : N / 8, 0xB1, N>(v, li & 1);
+// One step of a reduce-scatter over the wave's four 16-lane rows: a and b
+// exchange the halves the other keeps (v_permlane32_swap: a's lanes 32-63 with
+// b's lanes 0-31; v_permlane16_swap: a's odd rows with b's even rows) and are
+// added, so every lane ends with a's or b's sum over the two rows -- one swap
+// and one add per two values, no select.  Inline asm: hipcc's builtins for
+// the two swaps return the first register in both halves of their result
+// (ROCm 7; the sum came out as a + a).  The s_nop covers the wait states
+// between a VALU write of an operand, or an earlier swap, and the swap, which
+// the compiler does not track through the asm.
+template <bool kRows32>
+__device__ __forceinline__ float swap_add(float a, float b) {
+  if constexpr (kRows32)
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+  else
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+  return a + b;
 }
 
 // Lane id recomputed at the point of use (asm volatile: never hoisted out of
@@ -127,18 +123,10 @@ __device__ __forceinline__ unsigned fresh_lane() {
 }
 
 #ifndef DAL_GRAM_PRIO8
-#define DAL_GRAM_PRIO8 1  // 8-wave kernel: s_setprio 1 for waves 4-7 (> 0) or 0-3 (< 0)
+#define DAL_GRAM_PRIO8 1  // 8-wave kernels: s_setprio 1 for waves 4-7 (> 0) or 0-3 (< 0), 0: none
 #endif
 #ifndef DAL_GRAM_KS64_OCC
 #define DAL_GRAM_KS64_OCC 4  // KS 64: 4-wave blocks per CU (3: 16 KiB stages, 100k x 64 -3.2 % vs 2; row sums only, 128 VGPRs: 4 blocks on 8 KiB stages 100k x 64 -0.7 %, 200k x 64 -0.5 % vs 3)
-#endif
-#ifndef DAL_GRAM_NCH128
-// row-sum chains per row tile at KS 128 (240 VGPRs, no spill; KS <= 64 keep 1).
-// Two chains fold every 256 columns (once per pair) at the chain length one
-// chain has folding every 128: the same density bound, half the folds
-// (2M x 256 1190.7 -> 1173.4 ms, 1M x 128 -2.6 %, 200k x 256 -1.8 %; one
-// chain with the 256-column fold -- a bound twice as wide -- 1169.7 ms)
-#define DAL_GRAM_NCH128 2
 #endif
 #ifndef DAL_GRAM_FOLD64
 #define DAL_GRAM_FOLD64 256  // columns per row fold at KS <= 64
@@ -161,12 +149,22 @@ __device__ __forceinline__ unsigned fresh_lane() {
 #ifndef DAL_GRAM_KS32_OCC
 #define DAL_GRAM_KS32_OCC 5  // KS 32: 4-wave blocks per CU (3: 16 KiB stages; >= 4: 8 KiB stages. Config 3: 2 -> 3 -> 4 blocks 3.944 -> 3.827 -> 3.745 ms; row sums only (94 VGPRs): 4 -> 5 blocks 3.430 -> 3.391 ms)
 #endif
-template <int KS, int W = 4>
+template <int KS, int W = 4, int HVS = W / 4>
 struct Cfg {
-  static constexpr int WAVES = W;                   // 4: one super block per block; 8: two (P, P + 2)
-  static constexpr int HALVES = W / 4;              // super blocks per block
+  static constexpr int WAVES = W;                   // 4: one super block per block; 8: two (P, P + 2) or four
+  static constexpr int HALVES = HVS;                // super blocks per block
+  // the wide form: 8 waves hold four super blocks (P, P + 2, P + 4, P + 6), 256
+  // rows per wave, over sub-slices of half the slice's features -- the same
+  // A registers as 128 rows x KS features, twice the rows per staged B byte
+  static constexpr bool WIDE = HVS == 4;
+  static constexpr int KW = WIDE ? KS / 2 : KS;     // features of the resident A fragments and of a staged row
+  static constexpr int NSUB = KS / KW;              // sub-slices per slice
+  static constexpr int WPS = W / HVS;               // waves per super block: 4, or 2
+  static constexpr int RPW = kSB / WPS;             // rows per wave: 128, or 256
   static constexpr int NT = 64 * W;                 // threads
-  static constexpr int ROWB = KS * 2;               // bytes per staged operand row of a slice (its H run)
+  static constexpr int ROWB = KW * 2;               // bytes per staged operand row of a sub-slice (its H run)
+  // halves from the launch's first slice to sub-slice q: the operand keeps H run | L run per KS-slice
+  static constexpr int sub_off(int q) { return (q / NSUB) * 2 * KS + (q % NSUB) * KW; }
   static constexpr int SLOTS = ROWB / 16;           // 16-B slots per row: 4 / 8 / 16
   // three 4-wave blocks per CU at KS 64 (OCC3): 16 KiB stages so three fit the LDS
   static constexpr int OCC = W == 8 ? (KS == 64 ? DAL_GRAM_W8_OCC64 : 1)
@@ -195,28 +193,33 @@ struct Cfg {
   }
   static_assert(SLOTS == 4 || SLOTS == 8 || SLOTS == 16, "swizzles for 4, 8 and 16 slots per row");
   static constexpr int PIECES = STAGE / (W * 1024);  // 1-KiB DMA pieces per wave per stage
-  static constexpr int RT = 8;                      // 16-row tiles per wave (128 rows)
+  static constexpr int RT = RPW / 16;               // 16-row tiles per wave
   static constexpr int LG = 4;
-  static constexpr int NKS = KS / 32;               // k-steps of v_mfma_f32_16x16x32_f16
+  static constexpr int NKS = KW / 32;               // k-steps of v_mfma_f32_16x16x32_f16 per column tile
   static constexpr int NCT = SC / 16;               // column tiles per stage
-  // row-sum chains per row tile (column tiles dealt round-robin; 2 halve the
-  // chain length -- a tighter density bound -- for 32 more VGPRs)
-  static constexpr int NCH = KS == 128 ? DAL_GRAM_NCH128 : 1;
+  // Row-sum chains per row tile.  KS 128: one chain per 64-feature half of the
+  // slice (k-steps 2h, 2h + 1 of every column tile, tiles in column order),
+  // each folded on its own -- the 4-wave form keeps both in registers, the wide
+  // form meets them as its two sub-slices: every KS-128 form sums the same
+  // products in the same order, so their bits agree.
+  static constexpr int NCH = KW == 128 ? 2 : 1;
   // products summed by one row-chain element between two folds (the FOLD
-  // columns' tiles over NCH chains, KS products per tile: 512 at KS 32, 1,024
-  // at KS 64 and 128)
-  static constexpr int CHAIN = FOLD / 16 / NCH * KS;
+  // columns' tiles, KW / NCH products per tile: 512 at KS 32, 1,024 at KS 64
+  // and 128)
+  static constexpr int CHAIN = FOLD / 16 * (KW / NCH);
   // ... and the length dal_density_error_bound_sym_d charges the row side with:
   // that of the two-product body (H.H and H.L) these kernels had before, twice
   // CHAIN at the default folds.  The bound's values are part of the interface
   // (pinned by the tests), so it keeps them and over-charges.
   static constexpr int CHARGED = KS == 32 ? DAL_GRAM_CHAIN_MAX / 2 : DAL_GRAM_CHAIN_MAX;
   static_assert(SPF >= 1 && SPP % SPF == 0 && PIECES >= 1 && NKS >= 1, "bad slice");
-  static_assert(W == 4 || (W == 8 && KS >= 64), "two super blocks per block: KS >= 64 only");
+  static_assert(W == 4 || (W == 8 && KS >= 64), "several super blocks per block: KS >= 64 only");
+  static_assert(!WIDE || (W == 8 && KS == 128), "the wide form: 8 waves at KS 128");
+  static_assert(NKS % NCH == 0 && KW / NCH == 64 / (KS == 32 ? 2 : 1), "a chain is 64 features of every tile (KS 32: 32)");
   static_assert(CHAIN <= CHARGED, "row chain longer than the density bound charges");
 };
-// the 8-wave form folds like the 4-wave one (one bound per KS)
-static_assert(Cfg<128, 8>::CHAIN <= Cfg<128, 4>::CHARGED, "block forms share one bound");
+// the wide form's chains are the 4-wave form's (one bound, one set of bits per KS)
+static_assert(Cfg<128, 8, 4>::CHAIN == Cfg<128, 4>::CHAIN, "the KS-128 forms define the same chains");
 
 // Unit counters of the chunk-form launches (see the pair loop): next = units
 // claimed beyond the G the blocks enter by themselves, done = blocks that
@@ -232,13 +235,13 @@ __device__ ClaimSlot g_claim[kClaimSlots];
 // Row sums of the taken pairs (the column sums of every pair are added in
 // closed form by dal_gram_sym_residual, see the header): for each pair (P,
 // J) the taker's rows accumulate <H_i, H_j> over J's 256 columns.
-template <int KS, int W>
-__global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
+template <int KS, int W, int HVS>
+__global__ __launch_bounds__(64 * W, (Cfg<KS, W, HVS>::OCC)) void gram_csym_kernel(
     const uint16_t* __restrict__ urows, int srow0, int n_srb,
     const uint16_t* __restrict__ ucols, int jcol0, int j_lo, int j_hi, int skip_lo, int skip_hi,
     int ns_active, int64_t ldh, int slice_off, int n_slices, int chunk_j, int n_chunks,
     unsigned long long* __restrict__ acc_out, int contig, int claim_slot) {
-  using C = Cfg<KS, W>;
+  using C = Cfg<KS, W, HVS>;
   constexpr int HV = C::HALVES;
   __shared__ __attribute__((aligned(16))) float4 lds[2 * C::F4];
   __shared__ double rowacc[HV * kSB];
@@ -246,7 +249,7 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
 
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  const int half = wave >> 2, wave4 = wave & 3;  // the block's super block of this wave, wave within it
+  const int half = wave / C::WPS, wave4 = wave % C::WPS;  // the block's super block of this wave, wave within it
   // 8-wave block: the two waves of a SIMD (w, w + 4) run the same program in
   // lockstep; a static priority for one half settles their VALU arbitration
   // once instead of by age at every segment (MI355X_MICROARCH.md, two waves per
@@ -254,7 +257,7 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
   // 1265.0; deferring waves 4-7's last column epilogue of each stage into the
   // next one, a stagger, 1274.5)
   if constexpr (W == 8 && DAL_GRAM_PRIO8 != 0) {
-    if (DAL_GRAM_PRIO8 > 0 ? half == 1 : half == 0) __builtin_amdgcn_s_setprio(1);
+    if (DAL_GRAM_PRIO8 > 0 ? wave >= 4 : wave < 4) __builtin_amdgcn_s_setprio(1);
   }
   const int li = lane & 15, lq = lane >> 4;
   const int G = gridDim.x, g = blockIdx.x;
@@ -287,7 +290,7 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
     J = __builtin_amdgcn_readfirstlane(J);
     slice = __builtin_amdgcn_readfirstlane(slice);
     const char* sbase = reinterpret_cast<const char*>(
-        ucols + (static_cast<int64_t>(J - jcol0) * 256 + h * C::SC) * ldh + slice_off + slice * 2 * KS);
+        ucols + (static_cast<int64_t>(J - jcol0) * 256 + h * C::SC) * ldh + slice_off + C::sub_off(slice));
     const unsigned fl = fresh_lane();
     const unsigned lrow = fl / C::SLOTS + static_cast<unsigned>(wave * C::PIECES * RPP);
     const unsigned vlane = lrow * rowbytes + (((fl % C::SLOTS) ^ static_cast<unsigned>(C::swz(lrow))) << 4);
@@ -306,16 +309,16 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
     }
   };
 
-  // resident A fragments: H of rows P*512 + wave4*128 + rt*16 + (lane & 15)
+  // resident A fragments: H of rows P*512 + wave4*RPW + rt*16 + (lane & 15)
   // (P = this wave's super block of the unit), features of k-step c and lane
-  // group lq
+  // group lq (the MFMA's N side; the staged column tile is its M side)
   f16x8 ah[C::RT][C::NKS];
   auto load_a = [&](int ru, int slice) {
     const int P = sched.rowP(ru, half);
     if (HV > 1 && !sched.live(P)) return;  // (this half idles for the unit)
-    const uint16_t* pb = urows + static_cast<int64_t>(P - srow0) * kSB * ldh + slice_off + slice * 2 * KS;
+    const uint16_t* pb = urows + static_cast<int64_t>(P - srow0) * kSB * ldh + slice_off + C::sub_off(slice);
     const unsigned fl = fresh_lane();
-    const unsigned lrow = static_cast<unsigned>((wave4 * 128 + (fl & 15)) * ldh + (fl >> 4) * 8);
+    const unsigned lrow = static_cast<unsigned>((wave4 * C::RPW + (fl & 15)) * ldh + (fl >> 4) * 8);
     const unsigned tstep = static_cast<unsigned>(16 * ldh);
 #pragma unroll
     for (int rt = 0; rt < C::RT; ++rt)
@@ -346,10 +349,11 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
 #pragma unroll
     for (int ct = 0; ct < C::NCT; ++ct) {
       __builtin_amdgcn_sched_barrier(0);
-      const bool fresh = fresh_stage && ct < C::NCH;
-      const int ch = ct % C::NCH;
+      const bool fresh = fresh_stage && ct == 0;
 #pragma unroll
       for (int c = 0; c < C::NKS; ++c) {
+        constexpr int KPC = C::NKS / C::NCH;  // k-steps per chain
+        const int ch = c / KPC;
         const int i = ct * C::NKS + c, cur = i & 1;
         if (c + 1 < C::NKS)
           load_b(cur ^ 1, c + 1, ct);
@@ -358,7 +362,7 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
         const f32x4 zero = {};
 #pragma unroll
         for (int rt = 0; rt < C::RT; ++rt)
-          mc[ch][rt] = mfma16(ah[rt][c], bh[cur], (c == 0 && fresh) ? zero : mc[ch][rt]);
+          mc[ch][rt] = mfma16(bh[cur], ah[rt][c], (c % KPC == 0 && fresh) ? zero : mc[ch][rt]);
       }
       constexpr int NM = C::RT;  // MFMAs per k-step
 #pragma unroll
@@ -369,23 +373,37 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  // chains -> LDS row accumulator (exact integer fp64 adds).  A 4-step DPP
-  // reduce-scatter over the 16 column lanes leaves each lane 2 fully summed
-  // rows, added by all 64 lanes at distinct LDS addresses.
+  // chains -> LDS row accumulator (exact integer fp64 adds).  The column tile
+  // is the MFMA's M side, so lane (li, lq) holds row li of the row tile at the
+  // tile's columns 4 lq .. 4 lq + 3: the 16 columns of a row are summed in the
+  // lane, (m0 + m1) + (m2 + m3), and over the four lane rows, (x0 + x2) + (x1 +
+  // x3), by a two-step reduce-scatter of eight tiles' sums that leaves each
+  // lane 2 fully summed rows, added by all 64 lanes at distinct LDS addresses
+  // (round 11; before, the rows were the M side and the 16 columns one DPP
+  // row: 30 DPP adds and 60 selects per 8 tiles, 2.5 % of the launch).
+  // Every chain is reduced and rounded on its own, eight row tiles at a time
+  // (the wide form's 16 tiles in two rounds), so a row's integer does not
+  // depend on which form held its chain.
   auto fold_rows = [&]() {
-    float v[32];
 #pragma unroll
-    for (int rt = 0; rt < C::RT; ++rt)
+    for (int ch = 0; ch < C::NCH; ++ch)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) v[rt * 4 + q] = C::NCH == 1 ? mc[0][rt][q] : mc[0][rt][q] + mc[C::NCH - 1][rt][q];
-    rs_step<16, 0x140>(v, li & 8);  // row_mirror: lane i <-> 15 - i
-    rs_step<8, 0x141>(v, li & 4);   // row_half_mirror: i <-> i ^ 7
-    rs_step<4, 0x4E>(v, li & 2);    // quad_perm [2,3,0,1]
-    rs_step<2, 0xB1>(v, li & 1);    // quad_perm [1,0,3,2]
-    const int rt = ((li >> 1) & 1) | (((li >> 2) & 1) << 1) | (((li >> 3) & 1) << 2);
-    const int row = wave * 128 + rt * 16 + 4 * lq + 2 * (li & 1);
-    atomicAdd(&rowacc[row], static_cast<double>(__builtin_rintf(v[0] * kFold)));
-    atomicAdd(&rowacc[row + 1], static_cast<double>(__builtin_rintf(v[1] * kFold)));
+      for (int t0 = 0; t0 < C::RT; t0 += 8) {
+        float x[8];
+#pragma unroll
+        for (int rt = 0; rt < 8; ++rt) {
+          const f32x4 m = mc[ch][t0 + rt];
+          x[rt] = (m[0] + m[1]) + (m[2] + m[3]);
+        }
+        // lanes 0-31 keep tiles 0-3, lanes 32-63 tiles 4-7; then even rows keep k, odd rows k + 2
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = swap_add<true>(x[k], x[k + 4]);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) x[k] = swap_add<false>(x[k], x[k + 2]);
+        const int row = wave * C::RPW + (t0 + 2 * (lq & 1) + 4 * (lq >> 1)) * 16 + li;
+        atomicAdd(&rowacc[row], static_cast<double>(__builtin_rintf(x[0] * kFold)));
+        atomicAdd(&rowacc[row + 16], static_cast<double>(__builtin_rintf(x[1] * kFold)));
+      }
   };
   auto flush_one = [&](double& slot, int64_t out_row) {
     const double v = slot;
@@ -418,7 +436,7 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W>::OCC)) void gram_csym_kernel(
   // of the claim between them.  The counter words are touched by agent-scope
   // atomics only (no other data is handed between blocks), so no fence is
   // needed.
-  GramClaimCursor<HV> cur(sched, n_slices);
+  GramClaimCursor<HV> cur(sched, n_slices * C::NSUB);  // (the wide form's units count sub-slices)
   const bool dyn = claim_slot >= 0;
   int claim_par = 0;  // word of claim_lds of the next claim
   auto claim_begin = [&]() {
@@ -864,9 +882,9 @@ int device_cus() {
 #ifndef DAL_GRAM_MIN_CHUNKS_SMALL
 #define DAL_GRAM_MIN_CHUNKS_SMALL 2
 #endif
-// Two super blocks per block (8 waves, one block per CU: each B stage feeds
-// 1,024 rows, half the L2 -> LDS bytes per flop of the 4-wave form) for the
-// round-robin schedule at KS 128.
+// The wide form (8 waves, one block per CU, four super blocks per block: each
+// B stage feeds 2,048 rows, a quarter of the L2 -> LDS bytes per flop of the
+// 4-wave form) for the round-robin schedule at KS 128; 0: the 4-wave form.
 #ifndef DAL_GRAM_WAVES8
 #define DAL_GRAM_WAVES8 1
 #endif
@@ -896,24 +914,25 @@ int claim_slot_of(hipStream_t stream) {
 
 // n_slices feature slices from slice_off on in one launch (chunk form; the
 // contiguous form takes one slice per launch).
-template <int KS, int W>
+template <int KS, int W, int HVS = W / 4>
 int launch_csym_w(const uint16_t* rows, int64_t srow0, int64_t n_srb, const uint16_t* cols, int64_t jcol0,
                   int64_t j_lo, int64_t j_hi, int64_t skip_lo, int64_t skip_hi, int64_t ns_active, int64_t ldh,
                   int slice_off, int n_slices, int64_t* acc, int grid_blocks, int contig, int64_t min_chunks,
                   hipStream_t stream) {
   // grid_blocks counts 4-wave blocks (two per CU); 8-wave blocks are one per CU
-  constexpr int kOcc = Cfg<KS, W>::OCC;
+  using C = Cfg<KS, W, HVS>;
+  constexpr int kOcc = C::OCC;
   const int G0r = W == 4 ? (grid_blocks > 0 ? grid_blocks * kOcc / 2 : kOcc * device_cus())
                          : (grid_blocks > 0 ? grid_blocks : 2 * device_cus()) * 4 / W * kOcc;
   const int G0 = G0r > 0 ? G0r : 1;  // (a one-block grid in the 8-wave form)
-  if (!GramSchedule<W / 4>::form_ok(contig)) return DAL_ERR_ARG;
-  const GramLaunch L =
-      plan_launch<W / 4>(srow0, n_srb, j_lo, j_hi, skip_lo, skip_hi, ns_active, G0, contig, min_chunks, n_slices);
+  if (!GramSchedule<HVS>::form_ok(contig)) return DAL_ERR_ARG;
+  const GramLaunch L = plan_launch<HVS>(srow0, n_srb, j_lo, j_hi, skip_lo, skip_hi, ns_active, G0, contig, min_chunks,
+                                        n_slices * C::NSUB);
   if (L.G <= 0) return DAL_OK;
   if (contig && n_slices != 1) return DAL_ERR_ARG;
   // units beyond the G the blocks enter by themselves are claimed from a counter (none left: no counter)
   const int slot = !contig && L.units > L.G ? claim_slot_of(stream) : -1;
-  hipLaunchKernelGGL((gram_csym_kernel<KS, W>), dim3(static_cast<unsigned>(L.G)), dim3(64 * W), 0, stream, rows,
+  hipLaunchKernelGGL((gram_csym_kernel<KS, W, HVS>), dim3(static_cast<unsigned>(L.G)), dim3(64 * W), 0, stream, rows,
                      static_cast<int>(srow0), static_cast<int>(n_srb), cols, static_cast<int>(jcol0),
                      static_cast<int>(j_lo), static_cast<int>(j_hi), static_cast<int>(skip_lo),
                      static_cast<int>(skip_hi), static_cast<int>(ns_active), ldh, slice_off, n_slices, L.chunk_j,
@@ -948,8 +967,10 @@ int launch_csym(const uint16_t* rows, int64_t srow0, int64_t n_srb, const uint16
     int rc;
     if constexpr ((KS == 128 && DAL_GRAM_WAVES8) || (KS == 64 && DAL_GRAM_W8_KS64))
       if (!contig) {
-        rc = launch_csym_w<KS, 8>(rows, srow0, n_srb, cols, jcol0, j_lo, j_hi, skip_lo, skip_hi, ns_active, ldh, so,
-                                  per_launch, acc, grid_blocks, contig, min_chunks, stream);
+        // KS 128: the wide form (four super blocks per block over 64-feature sub-slices)
+        rc = launch_csym_w<KS, 8, KS == 128 ? 4 : 2>(rows, srow0, n_srb, cols, jcol0, j_lo, j_hi, skip_lo, skip_hi,
+                                                     ns_active, ldh, so, per_launch, acc, grid_blocks, contig,
+                                                     min_chunks, stream);
         if (rc != DAL_OK) return rc;
         continue;
       }
@@ -1012,8 +1033,8 @@ extern "C" double dal_density_error_bound_sym_d(int64_t n_cols, int64_t d_pad) {
   //              (1,024 at KS 32, 2,048 at KS 64 and 128: the chains of the
   //              earlier H.H + H.L body; the H.H chains are Cfg<KS>::CHAIN =
   //              FOLD / 16 / NCH tiles x KS, half as long, so this over-charges
-  //              -- the bound's values are part of the interface and stay), the
-  //              add combining the two chains (KS 128) and 4 cross-lane adds:
+  //              -- the bound's values are part of the interface and stay), 3
+  //              adds in the lane and 2 across lanes over a row's 16 columns:
   //              gamma_(CHARGED + 5) * c
   //   column side  none: every taken pair's column sums and the L terms are
   //              the closed form <L_i, S~> + <H_i, S^L + CH_B> of

@@ -1,7 +1,9 @@
 """Instruction counts of the gfx950 code objects in a libdal.so build (A/B
 and ablation builds: did a change keep every MFMA? how many VALU / LDS ops?).
 
-usage: python scripts/isa_stats.py LIB.so [LIB.so ...] [--kernel SUBSTR]"""
+usage: python scripts/isa_stats.py LIB.so [LIB.so ...] [--kernel SUBSTR]
+(default SUBSTR gram_csym_kernel: <32|64|128, 4, 1> and the wide form <128, 8,
+4>, whose pair loop holds 512 MFMAs and 32 ds_read_b128 of B per wave)"""
 import os
 import re
 import shutil
