@@ -42,6 +42,11 @@ DAL_RF_MAX_SPLITS = 255
 DAL_RF_MAX_SPLIT_SAMPLE = 16384
 DAL_RF_MAX_DEPTH = 10
 DAL_RF_SPLIT_LDS_BYTES = 163840
+DAL_MC_MAX_CLASSES = 32
+DAL_MC_MAX_TREES = 255
+DAL_MC_LEAST_CONFIDENCE = 0
+DAL_MC_MARGIN = 1
+DAL_MC_ENTROPY = 2
 
 # name -> (restype, argtypes); every symbol of include/dal.h
 SIGNATURES = {
@@ -84,6 +89,10 @@ SIGNATURES = {
                                          c_int32,
                                          c_int32, c_void_p, c_void_p, c_int, c_double, c_void_p, c_double,
                                          c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dal_forest_multiclass_max_classes": (c_int, []),
+    "dal_forest_score_multiclass": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32,
+                                            c_int32, c_int32, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p]),
     "dal_density_separable": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]),
     "dal_topk_workspace_bytes": (c_size_t, [c_int64, c_int64]),

@@ -58,7 +58,13 @@ def select(pool, unlabeled_idx, forest: Forest, k: int, beta: float = 1.0, exclu
                   (PoolState.density_fixed()); by default the pool's cached one
     mode          "gram" (default, the reference's algorithm on MFMA) or
                   "separable" (exact O(N*D) identity; same selection)
+
+    Binary forests only: the reference's one-sided entropy is a binary score,
+    so a multiclass forest (``forest.n_classes`` > 2) raises ValueError.
     """
+    if getattr(forest, "n_classes", 2) > 2:
+        raise ValueError("density weighting is binary only: the forest has "
+                         f"{forest.n_classes} classes (use dal.uncertainty_sampling.select)")
     if isinstance(excluded_idx, str):
         if excluded_idx != L0:
             raise ValueError(f"excluded_idx must be index-like, None or {L0!r}")

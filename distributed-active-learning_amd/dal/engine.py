@@ -19,11 +19,12 @@ import numpy as np
 from . import _lib
 from ._lib import (DAL_ASCENDING, DAL_CANON_CHUNK, DAL_DENSITY_EXACT, DAL_DENSITY_FIXED,
                    DAL_DENSITY_NONE, DAL_DESCENDING, DAL_FIXED_SCALE, DAL_FLAG_CAND_OVERFLOW,
-                   DAL_FLAG_SAMPLE_MISS, DAL_FLAG_ZERO_NORM, DAL_ROW_CANDIDATE, DAL_ROW_EXCLUDED,
+                   DAL_FLAG_SAMPLE_MISS, DAL_FLAG_ZERO_NORM, DAL_MC_ENTROPY, DAL_MC_LEAST_CONFIDENCE,
+                   DAL_MC_MARGIN, DAL_MC_MAX_TREES, DAL_ROW_CANDIDATE, DAL_ROW_EXCLUDED,
                    DAL_SORT_CAP_PAYLOAD, DAL_STEP_RESET_STATUS,
                    DAL_STEP_WS_CLEAN, call)
 from .forest import Forest
-from .luts import ASCENDING, lut as make_lut
+from .luts import ASCENDING, MULTICLASS_ASCENDING, lut as make_lut, multiclass_lut
 
 
 def _torch():
@@ -64,18 +65,22 @@ class Selection:
     indices         int64 [k]: selected global row indices, best first
     selected_scores fp64 [k]: their scores (canonical fp64 for density weighting)
     votes           int32 [U]: forest votes for class 1 of every unlabeled row
+                    (None for a multiclass step)
+    counts          uint8 [U, C]: per-class forest votes of every unlabeled row
+                    (a multiclass step; None otherwise)
 
-    ``scores`` / ``votes`` may be given as (per-row tensor, positions): they are
+    ``scores`` / ``votes`` / ``counts`` may be given as (per-row tensor, positions): they are
     gathered into unlabeled order on first access (the per-row arrays are
     complete in HBM when the step returns; the gather is only a re-layout, so
     a caller that reads just the selection pays no extra launches).
     """
 
-    def __init__(self, scores, indices, selected_scores, votes=None):
+    def __init__(self, scores, indices, selected_scores, votes=None, counts=None):
         self._scores = scores
         self.indices = indices
         self.selected_scores = selected_scores
         self._votes = votes
+        self._counts = counts
 
     @staticmethod
     def _gathered(v):
@@ -94,11 +99,17 @@ class Selection:
         self._votes = self._gathered(self._votes)
         return self._votes
 
+    @property
+    def counts(self):
+        self._counts = self._gathered(self._counts)
+        return self._counts
+
     def _detach(self):
         """Materialise the per-row arrays now (their source buffers are about
         to be reused: a warm-step graph replay)."""
         self._scores = self._gathered(self._scores)
         self._votes = self._gathered(self._votes)
+        self._counts = self._gathered(self._counts)
 
     def __iter__(self):
         """Unpacks as the reference-shaped triple (scores, indices, selected_scores)."""
@@ -590,6 +601,40 @@ def forest_score(state: PoolState, forest: Forest, lut_dev, flags, order: int, d
     return votes, scores, keys, keys_hi
 
 
+MULTICLASS_KINDS = {"least_confidence": DAL_MC_LEAST_CONFIDENCE, "margin": DAL_MC_MARGIN,
+                    "entropy": DAL_MC_ENTROPY}
+
+
+def device_multiclass_lut(strategy: str, n_trees: int, device):
+    """The multiclass fp64 LUT on the device, uploaded once per (strategy, T, device)."""
+    torch = _torch()
+    key = ("multiclass", strategy, int(n_trees), str(device))
+    if key not in _LUT_CACHE:
+        _LUT_CACHE[key] = torch.from_numpy(multiclass_lut(strategy, n_trees)).to(device)
+    return _LUT_CACHE[key]
+
+
+def forest_score_multiclass(state: PoolState, forest: Forest, lut_dev, flags, order: int, kind: int):
+    """Launch dal_forest_score_multiclass over the shard; returns (counts
+    uint8 [n, C], pred uint8 [n], scores, keys).  flags None: every row is a
+    candidate."""
+    torch = _torch()
+    forest.check_features(state.d)
+    forest.check_classes()
+    if forest.n_trees > DAL_MC_MAX_TREES:
+        raise ValueError(f"a multiclass forest may hold at most {DAL_MC_MAX_TREES} trees, not {forest.n_trees}")
+    inner, leaf = forest.device(state.device)
+    n, C = state.n, int(forest.n_classes)
+    counts = torch.empty((n, C), dtype=torch.uint8, device=state.device)
+    pred = torch.empty(n, dtype=torch.uint8, device=state.device)
+    scores = torch.empty(n, dtype=torch.float64, device=state.device)
+    keys = torch.empty(n, dtype=torch.int64, device=state.device)
+    call("dal_forest_score_multiclass", _ptr(state.x), n, state.d, state.d, _ptr(inner), _ptr(leaf),
+         forest.n_trees, forest.depth, C, _ptr(lut_dev), int(kind), 0 if flags is None else _ptr(flags), int(order),
+         _ptr(counts), _ptr(pred), _ptr(scores), _ptr(keys), _stream(state.device))
+    return counts, pred, scores, keys
+
+
 def _fprep(forest: Forest, state: PoolState, xb) -> int:
     """Address of the forest prepared for the blocked kernel (0 without xb)."""
     if xb is None:
@@ -809,6 +854,27 @@ def uncertainty_step(state: PoolState, unlabeled_idx, forest: Forest, k: int,
     sel_scores = scores[idx - state.row_base]
     state.check_status()
     return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, votes=(votes, loc))
+
+
+def multiclass_step(state: PoolState, unlabeled_idx, forest: Forest, k: int,
+                    strategy: str = "least_confidence") -> Selection:
+    """One uncertainty iteration over a C-class forest: per-class votes and
+    the C-class score (dal_forest_score_multiclass), then the top-k of the
+    keys.  The Selection carries ``counts`` ([U, C] uint8); ``votes`` is None."""
+    if strategy not in MULTICLASS_KINDS:
+        raise ValueError(f"strategy must be one of {tuple(MULTICLASS_KINDS)}")
+    flags, unl, n_cand = state.row_flags(unlabeled_idx)
+    if n_cand == 0:
+        raise ValueError("unlabeled set is empty (the reference loop breaks here)")
+    kk = min(int(k), n_cand)
+    loc = state.local_positions(unl)
+    order = DAL_ASCENDING if MULTICLASS_ASCENDING[strategy] else DAL_DESCENDING
+    lut_dev = device_multiclass_lut(strategy, forest.n_trees, state.device)
+    counts, _, scores, keys = forest_score_multiclass(state, forest, lut_dev, flags, order,
+                                                      MULTICLASS_KINDS[strategy])
+    idx, _ = topk_keys(keys, kk, state.row_base)
+    sel_scores = scores[idx - state.row_base]
+    return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, counts=(counts, loc))
 
 
 def density_step(state: PoolState, unlabeled_idx, forest: Forest, k: int, beta: float = 1.0,

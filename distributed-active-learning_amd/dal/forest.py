@@ -11,6 +11,7 @@ class label.
 Layout (per tree, complete binary heap of the forest's maximum depth D):
   inner[t][h] = (feature:int32, threshold:fp32 bits)   h < 2^D - 1
   leaf[t][l]  = class in {0,1}                          l < 2^D
+                (a multiclass forest, n_classes = C > 2: class id in {0..C-1})
 Shallower leaves are padded with always-left splits (threshold = +inf) whose
 whole subtree carries the leaf's class, so every root-to-leaf walk is exactly
 D steps (wave-uniform trip count on the GPU).  Thresholds are rounded toward
@@ -27,7 +28,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import DAL_MAX_TREE_DEPTH
+from ._lib import DAL_MAX_TREE_DEPTH, DAL_MC_MAX_CLASSES
 
 _POS_INF_BITS = np.array([np.inf], dtype=np.float32).view(np.int32)[0]
 
@@ -44,12 +45,16 @@ def threshold_to_f32(t64: np.ndarray) -> np.ndarray:
 
 @dataclass
 class Forest:
-    """A binary-classification forest of hard-voting trees (votes for class 1)."""
+    """A forest of hard-voting trees: binary (n_classes = 2, votes for class
+    1) or multiclass (leaf bytes are class ids in {0..n_classes-1};
+    ``classes_`` optionally holds the label of each class id)."""
 
     inner: np.ndarray  # int32 [T, 2^D - 1, 2]
     leaf: np.ndarray  # uint8 [T, 2^D]
     depth: int
     _dev: dict = field(default_factory=dict, repr=False)
+    n_classes: int = 2
+    classes_: np.ndarray = None
 
     @property
     def n_trees(self) -> int:
@@ -64,6 +69,18 @@ class Forest:
         lo, hi = self._dev["range"]
         if lo < 0 or hi >= d:
             raise ValueError(f"forest tests feature {lo if lo < 0 else hi}, outside the pool's {d} features")
+
+    def check_classes(self):
+        """Raise unless 2 <= n_classes <= DAL_MC_MAX_CLASSES and every leaf is
+        a class id below n_classes: the multiclass score kernel counts such a
+        leaf for no class."""
+        C = int(self.n_classes)
+        if not 2 <= C <= DAL_MC_MAX_CLASSES:
+            raise ValueError(f"n_classes must lie in [2, {DAL_MC_MAX_CLASSES}], not {C}")
+        if "leaf_max" not in self._dev:
+            self._dev["leaf_max"] = int(self.leaf.max()) if self.leaf.size else 0
+        if self._dev["leaf_max"] >= C:
+            raise ValueError(f"forest has a leaf of class {self._dev['leaf_max']}, outside its {C} classes")
 
     def device(self, device):
         """(inner, leaf) as device tensors, uploaded once per device."""
@@ -103,10 +120,16 @@ class Forest:
 
     # ------------------------------------------------------------ builders
     @classmethod
-    def from_nodes(cls, feature, threshold, left, right, value, roots) -> "Forest":
+    def from_nodes(cls, feature, threshold, left, right, value, roots, n_classes: int = 2,
+                   classes_=None) -> "Forest":
         """Flattened node arrays (global node ids): feature < 0 marks a leaf
         whose class is value[node]; internal nodes go to left[node] when
-        x[feature] <= threshold[node] (fp64), else right[node]."""
+        x[feature] <= threshold[node] (fp64), else right[node].  n_classes 2:
+        a leaf is class 1 when value[node] is non-zero; above 2 it is the
+        class id value[node], which must lie in [0, n_classes)."""
+        n_classes = int(n_classes)
+        if not 2 <= n_classes <= DAL_MC_MAX_CLASSES:
+            raise ValueError(f"n_classes must lie in [2, {DAL_MC_MAX_CLASSES}], not {n_classes}")
         feature = np.asarray(feature, dtype=np.int64)
         threshold = np.asarray(threshold, dtype=np.float64)
         left = np.asarray(left, dtype=np.int64)
@@ -141,7 +164,12 @@ class Forest:
             while stack:
                 nd, h, lv = stack.pop()
                 if feature[nd] < 0:
-                    cls_ = np.uint8(1 if value[nd] else 0)
+                    if n_classes == 2:
+                        cls_ = np.uint8(1 if value[nd] else 0)
+                    else:
+                        if not 0 <= value[nd] < n_classes:
+                            raise ValueError(f"leaf class {int(value[nd])} outside [0, {n_classes})")
+                        cls_ = np.uint8(value[nd])
                     # pad the subtree below heap position h with the leaf class
                     span = 1 << (D - lv)
                     first_leaf = (h + 1) * span - 1 - n_inner
@@ -151,12 +179,17 @@ class Forest:
                 inner[t, h, 1] = thr32[nd]
                 stack.append((int(left[nd]), 2 * h + 1, lv + 1))
                 stack.append((int(right[nd]), 2 * h + 2, lv + 1))
-        return cls(inner=inner, leaf=leaf, depth=D)
+        return cls(inner=inner, leaf=leaf, depth=D, n_classes=n_classes,
+                   classes_=None if classes_ is None else np.asarray(classes_))
 
     @classmethod
-    def from_sklearn(cls, rf, positive_label=1) -> "Forest":
+    def from_sklearn(cls, rf, positive_label=1, multiclass: bool = False) -> "Forest":
         """From a fitted ``sklearn.ensemble.RandomForestClassifier``: each tree
-        votes 1 when its leaf's majority class equals ``positive_label``."""
+        votes 1 when its leaf's majority class equals ``positive_label``.
+        multiclass=True: a leaf is the arg-max index of ``tree_.value`` (the
+        class id; ``classes_`` = rf.classes_ maps it back to the label, so
+        labels need not be contiguous) and n_classes = len(rf.classes_),
+        at least 2."""
         classes = np.asarray(rf.classes_)
         feat, thr, lft, rgt, val, roots = [], [], [], [], [], []
         base = 0
@@ -166,23 +199,33 @@ class Forest:
             cl = np.asarray(tr.children_left)
             cr = np.asarray(tr.children_right)
             is_leaf = cl < 0
-            lab = classes[np.argmax(tr.value[:, 0, :], axis=1)]
+            cid = np.argmax(tr.value[:, 0, :], axis=1)
+            lab = classes[cid]
             feat.append(np.where(is_leaf, -1, tr.feature))
             thr.append(np.where(is_leaf, 0.0, tr.threshold))
             lft.append(np.where(is_leaf, -1, cl + base))
             rgt.append(np.where(is_leaf, -1, cr + base))
-            val.append(np.where(is_leaf, (lab == positive_label).astype(np.int64), 0))
+            val.append(np.where(is_leaf, cid.astype(np.int64) if multiclass
+                                else (lab == positive_label).astype(np.int64), 0))
             base += tr.node_count
-        return cls.from_nodes(np.concatenate(feat), np.concatenate(thr), np.concatenate(lft),
-                              np.concatenate(rgt), np.concatenate(val), np.array(roots))
+        nodes = (np.concatenate(feat), np.concatenate(thr), np.concatenate(lft), np.concatenate(rgt),
+                 np.concatenate(val), np.array(roots))
+        if multiclass:
+            f = cls.from_nodes(*nodes, n_classes=max(2, classes.size), classes_=classes)
+            f.check_classes()  # (a two-class forest keeps from_nodes' non-zero rule: ids 0 and 1)
+            return f
+        return cls.from_nodes(*nodes)
 
     @classmethod
-    def from_mllib_debug_string(cls, text: str) -> "Forest":
+    def from_mllib_debug_string(cls, text: str, n_classes=None) -> "Forest":
         """Parse MLlib's ``RandomForestModel.toDebugString()`` (Spark 2.1
         ``Node.subtreeToString``): ``Tree k:`` headers, ``If (feature f <= t)`` /
         ``Else (feature f > t)`` for continuous splits, ``Predict: c`` at leaves.
         Categorical splits are rejected (the reference uses
-        ``categoricalFeaturesInfo={}``, uncertainty_sampling.py:73)."""
+        ``categoricalFeaturesInfo={}``, uncertainty_sampling.py:73).
+        n_classes None: the binary mapping (``Predict: 1.0`` is class 1, any
+        other label class 0); else ``Predict: c`` is class id int(c) of a
+        forest of n_classes (trainClassifier's numClasses)."""
         import re
 
         lines = [ln.strip() for ln in text.splitlines() if ln.strip()]
@@ -217,7 +260,7 @@ class Forest:
                 pos += 1
                 nd = new_node()
                 if ln.startswith("Predict:"):
-                    val[nd] = 1 if float(ln.split(":", 1)[1]) == 1.0 else 0
+                    val[nd] = _mllib_class(float(ln.split(":", 1)[1]), n_classes)
                     return nd
                 m = if_re.match(ln)
                 if not m:
@@ -232,14 +275,23 @@ class Forest:
                 return nd
 
             roots.append(parse())
-        return cls.from_nodes(feat, thr, lft, rgt, val, roots)
+        return cls._from_mllib_nodes(feat, thr, lft, rgt, val, roots, n_classes)
 
     @classmethod
-    def from_mllib_saved(cls, path: str) -> "Forest":
+    def _from_mllib_nodes(cls, feat, thr, lft, rgt, val, roots, n_classes) -> "Forest":
+        if n_classes is None:
+            return cls.from_nodes(feat, thr, lft, rgt, val, roots)
+        f = cls.from_nodes(feat, thr, lft, rgt, val, roots, n_classes=int(n_classes))
+        f.check_classes()
+        return f
+
+    @classmethod
+    def from_mllib_saved(cls, path: str, n_classes=None) -> "Forest":
         """Read an MLlib ``RandomForestModel.save(sc, path)`` directory: Parquet
         ``NodeData`` rows (treeId, nodeId, predict{predict, prob}, impurity,
         isLeaf, split{feature, threshold, featureType, categories}, leftNodeId,
-        rightNodeId, infoGain) under ``path/data``; continuous splits only."""
+        rightNodeId, infoGain) under ``path/data``; continuous splits only.
+        n_classes: as from_mllib_debug_string."""
         import glob
         import os
 
@@ -266,7 +318,7 @@ class Forest:
                     thr.append(0.0)
                     lft.append(-1)
                     rgt.append(-1)
-                    val.append(1 if float(r["predict"]["predict"]) == 1.0 else 0)
+                    val.append(_mllib_class(float(r["predict"]["predict"]), n_classes))
                 else:
                     sp = r["split"]
                     if int(sp.get("featureType", 0)) != 0:
@@ -277,14 +329,20 @@ class Forest:
                     rgt.append(gid[int(r["rightNodeId"])])
                     val.append(0)
             roots.append(gid[min(nodes)])  # MLlib root node id = 1 (smallest)
-        return cls.from_nodes(feat, thr, lft, rgt, val, roots)
+        return cls._from_mllib_nodes(feat, thr, lft, rgt, val, roots, n_classes)
 
     @classmethod
     def synthetic(cls, n_trees: int, depth: int, n_features: int, seed: int = 1,
-                  dist: str = "uniform") -> "Forest":
+                  dist: str = "uniform", n_classes: int = 2, skew: float = 0.0) -> "Forest":
         """BASELINE.json synthetic forest: T complete depth-``depth`` trees,
         feature ~ U{0..D-1}, threshold ~ U(0,1) (or N(0,1)) as fp32, leaf
-        class ~ Bernoulli(0.5) -- the same draw order as the test oracle."""
+        class ~ Bernoulli(0.5) -- the same draw order as the test oracle.
+        n_classes = C: leaf class ~ U{0..C-1}; skew > 0: class 0 with
+        probability ``skew`` instead (one more uniform draw per tree, after
+        the classes).  The defaults make the same draws as before."""
+        n_classes = int(n_classes)
+        if not 2 <= n_classes <= DAL_MC_MAX_CLASSES:
+            raise ValueError(f"n_classes must lie in [2, {DAL_MC_MAX_CLASSES}], not {n_classes}")
         rng = np.random.default_rng(seed)
         n_inner, n_leaf = (1 << depth) - 1, 1 << depth
         inner = np.zeros((n_trees, n_inner, 2), dtype=np.int32)
@@ -295,8 +353,20 @@ class Forest:
                 th = rng.random(n_inner).astype(np.float32)
             else:
                 th = rng.standard_normal(n_inner).astype(np.float32)
-            lv = rng.integers(0, 2, size=n_leaf)
+            lv = rng.integers(0, n_classes, size=n_leaf)
+            if skew > 0.0:
+                lv = np.where(rng.random(n_leaf) < skew, 0, lv)
             inner[t, :, 0] = f
             inner[t, :, 1] = th.view(np.int32)
             leaf[t] = lv
-        return cls(inner=inner, leaf=leaf, depth=depth)
+        return cls(inner=inner, leaf=leaf, depth=depth, n_classes=n_classes)
+
+
+def _mllib_class(label: float, n_classes) -> int:
+    """A leaf's class from MLlib's ``Predict: c``: the binary mapping
+    (c == 1.0) when n_classes is None, else the class id int(c)."""
+    if n_classes is None:
+        return 1 if label == 1.0 else 0
+    if label != int(label) or not 0 <= int(label) < int(n_classes):
+        raise ValueError(f"leaf label {label} is not a class id in [0, {int(n_classes)})")
+    return int(label)

@@ -92,13 +92,26 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
              verbose: bool = False, trainer="gpu") -> LoopResult:
     """Run the AL loop.  strategy: "uncertainty" (uncertainty_sampling.py),
     "density" (density_weighting.py, E = L0 = range(window_size)) or "random".
-    trainer: see train_forest.
+    trainer: see train_forest.  Labels of more than two values: "uncertainty"
+    scores the C-class forest (Forest.from_sklearn(rf, multiclass=True)) and
+    needs trainer="sklearn" or a callable; "density" and trainer="gpu" are
+    binary and raise ValueError.
 
     ``select_fn(strategy, pool, unlabeled, model, k) -> indices`` can replace
     the GPU step (tests use the oracle); by default the dal GPU path runs.
     """
     from .forest import Forest
 
+    # more than two label values: multiclass uncertainty sampling (per-class
+    # votes, dal.engine.multiclass_step) over a scikit-learn or caller-trained
+    # forest; the GPU trainer and density weighting are binary
+    multiclass = np.unique(np.asarray(y)).size > 2
+    if multiclass and strategy == "density":
+        raise ValueError("strategy='density' is binary only: y holds more than two label values "
+                         "(use strategy='uncertainty')")
+    if multiclass and trainer == "gpu":
+        raise ValueError("trainer='gpu' (dal.random_forest) trains binary forests only: y holds more than "
+                         "two label values (use trainer='sklearn' or a callable)")
     n = X.shape[0]
     labeled = list(range(min(window_size, n)))
     unlabeled = np.arange(len(labeled), n, dtype=np.int64)
@@ -137,7 +150,8 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
         elif select_fn is not None:
             chosen = np.asarray(select_fn(strategy, X, unlabeled, rf, k))
         else:
-            forest = rf.forest if isinstance(rf, GpuForestModel) else Forest.from_sklearn(rf)
+            forest = rf.forest if isinstance(rf, GpuForestModel) else \
+                Forest.from_sklearn(rf, multiclass=True) if multiclass else Forest.from_sklearn(rf)
             if strategy == "uncertainty":
                 from .uncertainty_sampling import select
                 sel = select(state, unlabeled, forest, k)

@@ -46,3 +46,27 @@ def lut(strategy: str, n_trees: int) -> np.ndarray:
     else:
         raise ValueError(f"unknown strategy {strategy!r}; expected one of {STRATEGIES}")
     return np.array(vals, dtype=np.float64)
+
+
+# Multiclass forests (C classes, n_c = trees voting class c): one table of
+# T + 1 entries per strategy, indexed on the GPU by
+#   least_confidence  lc[max_c n_c],               lc[v] = v / T          (ascending)
+#   margin            mg[n_(1) - n_(2)],           mg[m] = m / T          (ascending)
+#   entropy           sum over c, in class order, of h[n_c],
+#                     h[0] = 0.0, h[v] = -(v/T) * log2(v/T)               (descending)
+# h[T] is -0.0 and the class-ordered sum starts at +0.0, so no score is NaN.
+# New definitions: at C = 2 they are not the binary tables above.
+MULTICLASS_ASCENDING = {"least_confidence": True, "margin": True, "entropy": False}
+
+
+def multiclass_lut(strategy: str, n_trees: int) -> np.ndarray:
+    T = int(n_trees)
+    if T < 1:
+        raise ValueError("n_trees must be >= 1")
+    if strategy in ("least_confidence", "margin"):
+        vals = [v / T for v in range(T + 1)]
+    elif strategy == "entropy":
+        vals = [0.0] + [-(v / T) * _log2(v / T) for v in range(1, T + 1)]
+    else:
+        raise ValueError(f"unknown strategy {strategy!r}; expected one of {STRATEGIES}")
+    return np.array(vals, dtype=np.float64)

@@ -322,6 +322,8 @@ class ShardedSelector:
                              torch.full((k,), -1, dtype=torch.int64, device=st.device),
                              torch.full((k,), float("nan"), dtype=torch.float64, device=st.device))
 
+        if mode == "dw" and forest.n_classes > 2:
+            raise ValueError(f"density weighting is binary only: the forest has {forest.n_classes} classes")
         if st.n == 0:
             return empty()
         flags, unl, _ = st.row_flags(unlabeled_idx)
@@ -352,6 +354,15 @@ class ShardedSelector:
                                                    xb=xb)
                 i, s, kk_keys = dw_select_local(st, flags, votes, klo, khi, lut_dev, kk, beta, colsum,
                                                 cap_scale=self.cap_scale, sync=False)
+        elif forest.n_classes > 2:  # multiclass uncertainty: the C-class kernel, the same merge
+            from .engine import MULTICLASS_KINDS, device_multiclass_lut, forest_score_multiclass
+            from .luts import MULTICLASS_ASCENDING
+
+            order = DAL_ASCENDING if MULTICLASS_ASCENDING[strategy] else DAL_DESCENDING
+            lut_dev = device_multiclass_lut(strategy, forest.n_trees, st.device)
+            _, _, sc, kys = forest_score_multiclass(st, forest, lut_dev, flags, order, MULTICLASS_KINDS[strategy])
+            i, kk_keys = topk_keys(kys, kk, st.row_base)
+            s = sc[i - st.row_base]
         else:
             order = DAL_ASCENDING if ASCENDING[strategy] else DAL_DESCENDING
             lut_dev = device_lut(strategy, forest.n_trees, st.device)

@@ -172,13 +172,21 @@ def train_classifier(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: in
 
 def predict(forest: Forest, X, device=None):
     """RandomForestModel.predict (majority vote of the trees' hard labels;
-    ties -> class 0) on the GPU: (labels uint8 [n], votes int32 [n])."""
+    ties -> class 0) on the GPU: (labels uint8 [n], votes int32 [n]).  A
+    multiclass forest (n_classes > 2) returns (pred uint8 [n], counts uint8
+    [n, C]): pred is the class id with the most trees, ties to the lowest id
+    (``forest.classes_[pred]`` is the label where the forest carries labels)."""
     import torch
 
     from . import engine
-    from ._lib import DAL_ASCENDING
+    from ._lib import DAL_ASCENDING, DAL_MC_LEAST_CONFIDENCE
 
     state = X if isinstance(X, engine.PoolState) else engine.PoolState(X, device=device)
+    if forest.n_classes > 2:
+        lut = engine.device_multiclass_lut("least_confidence", forest.n_trees, state.device)
+        counts, pred, _, _ = engine.forest_score_multiclass(state, forest, lut, None, DAL_ASCENDING,
+                                                            DAL_MC_LEAST_CONFIDENCE)
+        return pred, counts
     lut = engine.device_lut("least_confidence", forest.n_trees, state.device)
     votes, _, _, _ = engine.forest_score(state, forest, lut, state.flags, DAL_ASCENDING)
     return (2 * votes > forest.n_trees).to(torch.uint8), votes

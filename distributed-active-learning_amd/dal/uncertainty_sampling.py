@@ -12,7 +12,7 @@ Ties (frequent: only T+1 distinct scores) go to the lower pool index.
 """
 from __future__ import annotations
 
-from .engine import PoolState, Selection, as_pool_state, uncertainty_step
+from .engine import PoolState, Selection, as_pool_state, multiclass_step, uncertainty_step
 from .forest import Forest
 from .luts import STRATEGIES
 
@@ -27,10 +27,17 @@ def select(pool, unlabeled_idx, forest: Forest, k: int, strategy: str = "least_c
     k              batch size (``window_size``; clamped to the unlabeled count)
     strategy       "least_confidence" (reference), "margin" or "entropy"
     Returns Selection(scores[U], indices[k], selected_scores[k], votes[U]).
+
+    A multiclass forest (``forest.n_classes`` > 2, at most 32 classes and 255
+    trees) is scored by the C-class forms of the three strategies
+    (dal.luts.multiclass_lut): the Selection then carries ``counts`` [U, C]
+    and ``votes`` is None.
     """
     if strategy not in STRATEGIES:
         raise ValueError(f"strategy must be one of {STRATEGIES}")
     state = as_pool_state(pool, device=device)
+    if forest.n_classes > 2:
+        return multiclass_step(state, unlabeled_idx, forest, k, strategy)
     return uncertainty_step(state, unlabeled_idx, forest, k, strategy)
 
 

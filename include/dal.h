@@ -281,6 +281,37 @@ int dal_forest_score_blocked(const float* x, const float* xb, const void* fprep,
                              int32_t* votes, double* scores, uint64_t* keys, uint64_t* keys_hi,
                              dal_stream_t stream);
 
+/* ---- (a5-a10, C classes) per-class forest votes + uncertainty score ------
+ * New symbols only: dal_abi_version() stays 10, and a caller probes for the
+ * feature with dal_forest_multiclass_max_classes() (32; absent from older
+ * libraries).  The forest is dal_forest_score's complete-heap SoA with leaf
+ * bytes holding class ids in {0..n_classes-1}, 2 <= n_classes <= 32,
+ * 1 <= n_trees <= 255.  n_c(i) = the number of trees whose leaf for row i is
+ * class c (sum_c n_c = T); counts[i][c] = n_c(i) (nullable), pred[i] = the
+ * smallest c with maximal n_c (nullable).  lut: fp64[T+1] (dal.luts.
+ * multiclass_lut), and by score_kind
+ *   DAL_MC_LEAST_CONFIDENCE  scores[i] = lut[max_c n_c]
+ *   DAL_MC_MARGIN            scores[i] = lut[n_(1) - n_(2)], largest minus
+ *                            second-largest count (integer subtraction)
+ *   DAL_MC_ENTROPY           scores[i] = ((0.0 + lut[n_0]) + lut[n_1]) + ...,
+ *                            sequential fp64 adds in class order
+ * keys[i] = the score key for ``order``, DAL_KEY_NONE when the row is not
+ * DAL_ROW_CANDIDATE (row_flags NULL: every row is a candidate); select with
+ * dal_topk.  A leaf byte >= n_classes is counted for no class (the forest is
+ * device data and is not read back; dal.forest.Forest.check_classes checks it
+ * before upload).  Uncertainty only: no density, no blocked copy, no plan. */
+#define DAL_MC_MAX_CLASSES 32
+#define DAL_MC_MAX_TREES 255
+#define DAL_MC_LEAST_CONFIDENCE 0
+#define DAL_MC_MARGIN 1
+#define DAL_MC_ENTROPY 2
+int dal_forest_multiclass_max_classes(void);
+int dal_forest_score_multiclass(const float* x, int64_t n, int64_t d, int64_t ldx,
+                                const int32_t* inner, const uint8_t* leaf, int32_t n_trees, int32_t depth,
+                                int32_t n_classes, const double* lut, int score_kind,
+                                const uint8_t* row_flags, int order, uint8_t* counts, uint8_t* pred,
+                                double* scores, uint64_t* keys, dal_stream_t stream);
+
 /* ---- (a11) top-k: sortBy(score).take(k) --------------------------------
  * Replaces uncertainty_sampling.py:106,109 / density_weighting.py:168,172.
  * The k smallest keys, ties -> lower index; out_idx = idx_base + row, sorted
