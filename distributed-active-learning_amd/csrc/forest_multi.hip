@@ -24,6 +24,16 @@
 // cross-lane sum of a row's tpr partial words (plain 32-bit adds).  The
 // staging code is a copy of forest.hip's, not shared: the binary kernels'
 // code generation does not move.
+//
+// The density-weighted form (template parameter DW; dal_forest_score_
+// multiclass_dw) is the C-class reading of density_weighting.py:148-167's e*d
+// product: the same walk, counters and staging, and a row-leader epilogue that
+// multiplies the class entropy by density^beta and writes the interval keys
+// of the binary kernel's density mode, plus the row's entropy and its own
+// index, so that dal_dw_select (lut = entropy, votes = index) re-ranks it
+// unchanged.  The DW = false kernels are the code they were without it.
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace dal {
@@ -53,6 +63,45 @@ struct McArgs {
   int cstore;  // bytes per store of a row's counts: 4, 2 or 1 (by C and the buffer's alignment)
 };
 
+// The density-weighted form (DW): the entropy score times density^beta with
+// interval keys, as the binary kernel's density mode (forest.hip).  Its
+// arguments extend McArgs, so the uncertainty form's kernels take the struct
+// they always took.
+struct McDwArgs : McArgs {
+  const void* density;  // int64 fixed point (DAL_DENSITY_FIXED) or fp64 bits (DAL_DENSITY_EXACT), one word per row
+  int dkind;
+  double derr;
+  double beta;
+  double* entropy;
+  int32_t* row_index;
+  uint64_t* keys_hi;  // nullable
+};
+
+// Copies of forest.hip's helpers (not shared: the binary kernels' code
+// generation does not move).  pow stays out of line, and the launcher picks
+// the kernel by beta: the beta == 1 kernels (POW false) hold no call at all --
+// a call that is never taken still cost them 1 % (config 4, T = 10) to 3 %
+// (T = 100) and 8 bytes of scratch per lane.
+__device__ __attribute__((noinline)) double mc_density_pow_general(double d, double beta) { return pow(d, beta); }
+template <bool POW>
+__device__ __forceinline__ double mc_density_pow(double d, double beta) {
+  if constexpr (POW) return mc_density_pow_general(d, beta);
+  return d;
+}
+
+// |d^beta - d'^beta| bound for |d - d'| <= derr.
+__device__ __attribute__((noinline)) double mc_density_pow_err_general(double d, double derr, double beta) {
+  const double p = pow(fabs(d), beta);
+  const double hi = pow(fabs(d) + derr, beta);
+  const double lo = pow(fmax(fabs(d) - derr, 0.0), beta);
+  return fmax(fabs(hi - p), fabs(p - lo)) * (1.0 + 1e-12) + fabs(p) * 1e-14;
+}
+template <bool POW>
+__device__ __forceinline__ double mc_density_pow_err(double d, double derr, double beta) {
+  if constexpr (POW) return mc_density_pow_err_general(d, derr, beta);
+  return derr;
+}
+
 // One vote for class c: 1 << 8 (c & 3) added to word c >> 2.  The loop is
 // unrolled over the CW words (a runtime-indexed register array would live in
 // scratch); a class >= 4 CW matches no word and is dropped.  (A bit extract
@@ -72,11 +121,12 @@ __device__ __forceinline__ int vote_field(const unsigned (&w)[CW], int c) {  // 
 }
 
 // Counts, prediction, score and key of tile `tile` (R rows from LDS or global
-// memory).  fl_pre: the row leader's flags, loaded with the tile.
-template <int CW, bool X_LDS>
-__device__ __forceinline__ void score_tile_multi(const McArgs& A, const float* xs, int xstride, int64_t tile, int R,
+// memory).  fl_pre: the row leader's flags, loaded with the tile; DW: dens_pre,
+// its density word, loaded with them.
+template <int CW, bool X_LDS, bool DW, bool POW, class Args>
+__device__ __forceinline__ void score_tile_multi(const Args& A, const float* xs, int xstride, int64_t tile, int R,
                                                  int tpr, const int2* inner, const uint8_t* leaf, uint8_t fl_pre,
-                                                 const double* lut_s) {
+                                                 long long dens_pre, const double* lut_s) {
   const int n_inner = (1 << A.depth) - 1;
   const int n_leaf = 1 << A.depth;
   const int tid = threadIdx.x;
@@ -142,7 +192,7 @@ __device__ __forceinline__ void score_tile_multi(const McArgs& A, const float* x
     }
   }
   double s;
-  if (A.kind == DAL_MC_ENTROPY) {
+  if (DW || A.kind == DAL_MC_ENTROPY) {
     s = 0.0;
 #pragma unroll
     for (int c = 0; c < 4 * CW; ++c)
@@ -169,17 +219,44 @@ __device__ __forceinline__ void score_tile_multi(const McArgs& A, const float* x
     }
   }
   if (A.pred) A.pred[row] = static_cast<uint8_t>(arg);
-  A.scores[row] = s;
-  A.keys[row] = (fl_pre & DAL_ROW_CANDIDATE) ? score_key(s, A.order) : DAL_KEY_NONE;
+  if constexpr (DW) {
+    // the binary kernel's density epilogue (forest.hip) on the class entropy
+    // e (never NaN, >= +0.0): s = e d^beta, descending, and for the GEMM
+    // density the interval s -+ e err(d^beta) as two keys
+    const double e = s;
+    double d = A.dkind == DAL_DENSITY_FIXED ? from_fixed(dens_pre) : __builtin_bit_cast(double, dens_pre);
+    if (fl_pre & DAL_ROW_EXCLUDED) d = __builtin_nan("");
+    s = e * mc_density_pow<POW>(d, A.beta);
+    double err = 0.0;
+    if (A.dkind == DAL_DENSITY_FIXED && e != 0.0 && d == d) {
+      err = e * mc_density_pow_err<POW>(d, A.derr, A.beta);
+      // keep the interval ends distinct from s after rounding
+      err = fmax(err, fabs(s) * 4.5e-16);
+    }
+    unsigned long long klo = DAL_KEY_NONE, khi = DAL_KEY_NONE;
+    if (fl_pre & DAL_ROW_CANDIDATE) {
+      klo = score_key(pessimistic(s, err, DAL_DESCENDING), DAL_DESCENDING);
+      khi = score_key(optimistic(s, err, DAL_DESCENDING), DAL_DESCENDING);
+    }
+    A.entropy[row] = e;
+    A.row_index[row] = static_cast<int32_t>(row);  // (n <= INT32_MAX, checked by the entry)
+    A.scores[row] = s;
+    A.keys[row] = klo;
+    if (A.keys_hi) A.keys_hi[row] = khi;
+  } else {
+    A.scores[row] = s;
+    A.keys[row] = (fl_pre & DAL_ROW_CANDIDATE) ? score_key(s, A.order) : DAL_KEY_NONE;
+  }
 }
 
 // One block per tile (grid = tiles), or PERSIST (LDS-DMA staging only; grid =
 // the blocks resident at once, walking tiles blockIdx.x, + gridDim.x, ...): the
 // forest and the LUT are copied into LDS once per block instead of once per
 // tile.  LDS: [R staged rows | LUT, T + 1 doubles | forest nodes, leaves].
-template <int CW, bool X_LDS, bool F_LDS, bool PERSIST>
-__global__ __launch_bounds__(kMcThreads) void forest_multi_kernel(McArgs A, int R, int tpr, int x_floats, bool vec4,
-                                                                  bool pad4, bool dma, int64_t n_tiles) {
+template <int CW, bool X_LDS, bool F_LDS, bool PERSIST, bool DW, bool POW>
+__global__ __launch_bounds__(kMcThreads) void forest_multi_kernel(std::conditional_t<DW, McDwArgs, McArgs> A, int R,
+                                                                  int tpr, int x_floats, bool vec4, bool pad4,
+                                                                  bool dma, int64_t n_tiles) {
   static_assert(!PERSIST || X_LDS, "the persistent form stages rows by LDS-DMA");
   if (PERSIST) {
     dma = true;
@@ -215,6 +292,10 @@ __global__ __launch_bounds__(kMcThreads) void forest_multi_kernel(McArgs A, int 
     // the row leader's flags are loaded with the tile (one HBM latency per tile)
     uint8_t fl_pre = DAL_ROW_CANDIDATE;
     if (A.flags && live && sub == 0) fl_pre = A.flags[row];
+    long long dens_pre = 0;  // ... and, DW, its density word
+    if constexpr (DW) {
+      if (live && sub == 0) dens_pre = static_cast<const long long*>(A.density)[row];
+    }
     if (X_LDS) {
       const int rows_here = static_cast<int>(min(static_cast<int64_t>(R), A.n - row0));
       if (dma) {
@@ -274,7 +355,7 @@ __global__ __launch_bounds__(kMcThreads) void forest_multi_kernel(McArgs A, int 
       }
     }
     __syncthreads();
-    score_tile_multi<CW, X_LDS>(A, xs, xstride, tile, R, tpr, inner, leaf, fl_pre, lut_s);
+    score_tile_multi<CW, X_LDS, DW, POW>(A, xs, xstride, tile, R, tpr, inner, leaf, fl_pre, dens_pre, lut_s);
     if (!PERSIST) break;
     __syncthreads();  // every wave done with the tile before the next one is staged
   }
@@ -307,8 +388,8 @@ McTiling multi_tiling(const float* x, int64_t d, int64_t ldx, int32_t n_trees) {
   return T;
 }
 
-template <int CW>
-int multi_launch(const McArgs& A, const McTiling& T, int64_t d, int64_t ldx, hipStream_t st) {
+template <int CW, bool DW, bool POW, class Args>
+int multi_launch(const Args& A, const McTiling& T, int64_t d, int64_t ldx, hipStream_t st) {
   const int R = T.R, tpr = kMcThreads / R;
   const int64_t blocks = ceil_div(A.n, R);
   const bool vec4 = (d % 4 == 0) && (ldx % 4 == 0) && (reinterpret_cast<uintptr_t>(A.x) % 16 == 0);
@@ -321,7 +402,7 @@ int multi_launch(const McArgs& A, const McTiling& T, int64_t d, int64_t ldx, hip
                       (f_lds ? static_cast<size_t>(f_bytes) : 0);
 #define DAL_MC_LAUNCH(XL, FL, PS)                                                                          \
   do {                                                                                                     \
-    const void* fn = reinterpret_cast<const void*>(forest_multi_kernel<CW, XL, FL, PS>);                   \
+    const void* fn = reinterpret_cast<const void*>(forest_multi_kernel<CW, XL, FL, PS, DW, POW>);          \
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) !=     \
         hipSuccess)                                                                                        \
       return DAL_ERR_HIP;                                                                                  \
@@ -335,7 +416,7 @@ int multi_launch(const McArgs& A, const McTiling& T, int64_t d, int64_t ldx, hip
       if (per_cu < 1) per_cu = 1;                                                                          \
       if (grid > static_cast<int64_t>(cus) * per_cu) grid = static_cast<int64_t>(cus) * per_cu;            \
     }                                                                                                      \
-    hipLaunchKernelGGL((forest_multi_kernel<CW, XL, FL, PS>), dim3(static_cast<unsigned>(grid)),           \
+    hipLaunchKernelGGL((forest_multi_kernel<CW, XL, FL, PS, DW, POW>), dim3(static_cast<unsigned>(grid)),  \
                        dim3(kMcThreads), smem, st, A, R, tpr, xf, vec4, pad4, T.dma, blocks);              \
   } while (0)
   if (T.dma && f_lds) DAL_MC_LAUNCH(true, true, true);
@@ -378,8 +459,44 @@ extern "C" int dal_forest_score_multiclass(const float* x, int64_t n, int64_t d,
                  scores,    keys, cstore};
   const McTiling T = multi_tiling(x, d, ldx, n_trees);
   const hipStream_t st = as_stream(stream);
-  if (n_classes <= 4) return multi_launch<1>(A, T, d, ldx, st);
-  if (n_classes <= 8) return multi_launch<2>(A, T, d, ldx, st);
-  if (n_classes <= 16) return multi_launch<4>(A, T, d, ldx, st);
-  return multi_launch<8>(A, T, d, ldx, st);
+  if (n_classes <= 4) return multi_launch<1, false, false>(A, T, d, ldx, st);
+  if (n_classes <= 8) return multi_launch<2, false, false>(A, T, d, ldx, st);
+  if (n_classes <= 16) return multi_launch<4, false, false>(A, T, d, ldx, st);
+  return multi_launch<8, false, false>(A, T, d, ldx, st);
+}
+
+extern "C" int dal_forest_score_multiclass_dw(const float* x, int64_t n, int64_t d, int64_t ldx, const int32_t* inner,
+                                              const uint8_t* leaf, int32_t n_trees, int32_t depth, int32_t n_classes,
+                                              const double* lut, const void* density, int density_kind,
+                                              double density_err, const uint8_t* row_flags, double beta,
+                                              uint8_t* counts, uint8_t* pred, double* entropy, int32_t* row_index,
+                                              double* scores, uint64_t* keys, uint64_t* keys_hi,
+                                              dal_stream_t stream) {
+  if (!x || !inner || !leaf || !lut || !density || !entropy || !row_index || !scores || !keys) return DAL_ERR_ARG;
+  if (density_kind != DAL_DENSITY_FIXED && density_kind != DAL_DENSITY_EXACT) return DAL_ERR_ARG;
+  if (n < 0 || d < 1 || ldx < d || d > (int64_t{1} << 30)) return DAL_ERR_SHAPE;
+  if (n > INT32_MAX) return DAL_ERR_SHAPE;  // row_index is int32 (dal_dw_select's vote type)
+  if (depth < 1 || depth > DAL_MAX_TREE_DEPTH) return DAL_ERR_UNSUPPORTED;
+  if (n_classes < 2 || n_classes > DAL_MC_MAX_CLASSES) return DAL_ERR_UNSUPPORTED;
+  if (n_trees < 1 || n_trees > DAL_MC_MAX_TREES) return DAL_ERR_UNSUPPORTED;
+  if (n == 0) return DAL_OK;
+  const uintptr_t ca = reinterpret_cast<uintptr_t>(counts);
+  const int cstore = (n_classes % 4 == 0 && ca % 4 == 0) ? 4 : (n_classes % 2 == 0 && ca % 2 == 0) ? 2 : 1;
+  const McDwArgs A{{x,         n,    static_cast<int>(d), ldx,       reinterpret_cast<const int2*>(inner),
+                    leaf,      n_trees, depth,            n_classes, lut,
+                    DAL_MC_ENTROPY, row_flags, DAL_DESCENDING, counts, pred,
+                    scores,    keys, cstore},
+                   density, density_kind, density_err, beta, entropy, row_index, keys_hi};
+  const McTiling T = multi_tiling(x, d, ldx, n_trees);
+  const hipStream_t st = as_stream(stream);
+  if (beta == 1.0) {  // no pow, no call
+    if (n_classes <= 4) return multi_launch<1, true, false>(A, T, d, ldx, st);
+    if (n_classes <= 8) return multi_launch<2, true, false>(A, T, d, ldx, st);
+    if (n_classes <= 16) return multi_launch<4, true, false>(A, T, d, ldx, st);
+    return multi_launch<8, true, false>(A, T, d, ldx, st);
+  }
+  if (n_classes <= 4) return multi_launch<1, true, true>(A, T, d, ldx, st);
+  if (n_classes <= 8) return multi_launch<2, true, true>(A, T, d, ldx, st);
+  if (n_classes <= 16) return multi_launch<4, true, true>(A, T, d, ldx, st);
+  return multi_launch<8, true, true>(A, T, d, ldx, st);
 }

@@ -18,7 +18,8 @@ re-ranked in canonical fp64 so the selected set is bit-exact.
 """
 from __future__ import annotations
 
-from .engine import PoolState, Selection, as_pool_state, density_step
+from ._lib import DAL_MC_MAX_TREES
+from .engine import PoolState, Selection, as_pool_state, density_step, multiclass_density_step
 from .forest import Forest
 
 
@@ -65,6 +66,13 @@ def select(pool, unlabeled_idx, forest: Forest, k: int, beta: float = 1.0, exclu
     if getattr(forest, "n_classes", 2) > 2:
         raise ValueError("density weighting is binary only: the forest has "
                          f"{forest.n_classes} classes (use dal.uncertainty_sampling.select)")
+    state = _pool_state(pool, unlabeled_idx, k, excluded_idx, window_size, device)
+    return density_step(state, unlabeled_idx, forest, k, beta=beta, density_fixed=density, mode=mode)
+
+
+def _pool_state(pool, unlabeled_idx, k, excluded_idx, window_size, device) -> PoolState:
+    """The pool with the excluded set of select / select_multiclass applied
+    (their ``excluded_idx`` and ``window_size`` arguments)."""
     if isinstance(excluded_idx, str):
         if excluded_idx != L0:
             raise ValueError(f"excluded_idx must be index-like, None or {L0!r}")
@@ -80,8 +88,29 @@ def select(pool, unlabeled_idx, forest: Forest, k: int, beta: float = 1.0, exclu
             excluded_idx = range(int(window_size))
     elif excluded_idx is None and isinstance(pool, PoolState):
         excluded_idx = []
-    state = as_pool_state(pool, excluded=excluded_idx, device=device)
-    return density_step(state, unlabeled_idx, forest, k, beta=beta, density_fixed=density, mode=mode)
+    return as_pool_state(pool, excluded=excluded_idx, device=device)
 
 
-__all__ = ["information_density", "select", "PoolState", "Selection"]
+def select_multiclass(pool, unlabeled_idx, forest: Forest, k: int, beta: float = 1.0, excluded_idx=L0,
+                      density=None, device=None, mode: str = "gram", window_size=None) -> Selection:
+    """Score every unlabeled row by class entropy x density^beta and select
+    the top k: the C-class information density.
+
+    score_i = H_i * d_i^beta, H_i = sum over the classes c, in class order, of
+    -(n_c/T) log2(n_c/T), n_c the trees voting class c (dal.luts.
+    multiclass_lut("entropy", T)); d_i the density of ``select``.  Descending,
+    NaN last, ties to the lower index; the selection and ``selected_scores``
+    are the canonical fp64 ones.  This is a definition of its own, not the
+    reference's one-sided -(1-p) log2(1-p) that ``select`` keeps: any forest
+    with n_classes >= 2 is scored through the multiclass kernel, and at two
+    classes H is the two-term Shannon entropy.  At most 32 classes and 255
+    trees.  The other arguments are those of ``select``.  The Selection
+    carries ``counts`` ([U, C] per-class votes); ``votes`` is None."""
+    forest.check_classes()
+    if forest.n_trees > DAL_MC_MAX_TREES:
+        raise ValueError(f"a multiclass forest may hold at most {DAL_MC_MAX_TREES} trees, not {forest.n_trees}")
+    state = _pool_state(pool, unlabeled_idx, k, excluded_idx, window_size, device)
+    return multiclass_density_step(state, unlabeled_idx, forest, k, beta=beta, density_fixed=density, mode=mode)
+
+
+__all__ = ["information_density", "select", "select_multiclass", "PoolState", "Selection"]

@@ -635,6 +635,48 @@ def forest_score_multiclass(state: PoolState, forest: Forest, lut_dev, flags, or
     return counts, pred, scores, keys
 
 
+def forest_score_multiclass_dw(state: PoolState, forest: Forest, flags, density, density_kind: int,
+                               density_err: float = 0.0, beta: float = 1.0, want_hi: bool = True):
+    """Launch dal_forest_score_multiclass_dw over the shard: class entropy x
+    density^beta, descending, with interval keys.  ``density``: one 8-byte
+    word per row, int64 fixed point (DAL_DENSITY_FIXED) or canonical fp64
+    (DAL_DENSITY_EXACT).  Returns (counts uint8 [n, C], pred uint8 [n],
+    entropy fp64 [n], row_index int32 [n], scores, keys, keys_hi or None).
+    flags None: every row is a candidate."""
+    torch = _torch()
+    forest.check_features(state.d)
+    forest.check_classes()
+    if forest.n_trees > DAL_MC_MAX_TREES:
+        raise ValueError(f"a multiclass forest may hold at most {DAL_MC_MAX_TREES} trees, not {forest.n_trees}")
+    if density_kind not in (DAL_DENSITY_FIXED, DAL_DENSITY_EXACT):
+        raise ValueError("density_kind must be DAL_DENSITY_FIXED or DAL_DENSITY_EXACT")
+    if density is None or int(density.shape[0]) < state.n or density.element_size() != 8:
+        raise ValueError("density must hold one 8-byte word per row of the pool")
+    inner, leaf = forest.device(state.device)
+    dev = state.device
+    n, C = state.n, int(forest.n_classes)
+    lut_dev = device_multiclass_lut("entropy", forest.n_trees, dev)
+    counts = torch.empty((n, C), dtype=torch.uint8, device=dev)
+    pred = torch.empty(n, dtype=torch.uint8, device=dev)
+    entropy = torch.empty(n, dtype=torch.float64, device=dev)
+    row_index = torch.empty(n, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, dtype=torch.float64, device=dev)
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    keys_hi = torch.empty(n, dtype=torch.int64, device=dev) if want_hi else None
+    ev = None
+    if state.forest_events is not None:  # bench: K2 launch timing on the launch stream
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+    call("dal_forest_score_multiclass_dw", _ptr(state.x), n, state.d, state.d, _ptr(inner), _ptr(leaf),
+         forest.n_trees, forest.depth, C, _ptr(lut_dev), _ptr(density), int(density_kind), float(density_err),
+         0 if flags is None else _ptr(flags), float(beta), _ptr(counts), _ptr(pred), _ptr(entropy),
+         _ptr(row_index), _ptr(scores), _ptr(keys), 0 if keys_hi is None else _ptr(keys_hi), _stream(dev))
+    if ev is not None:
+        ev[1].record()
+        state.forest_events.append(ev)
+    return counts, pred, entropy, row_index, scores, keys, keys_hi
+
+
 def _fprep(forest: Forest, state: PoolState, xb) -> int:
     """Address of the forest prepared for the blocked kernel (0 without xb)."""
     if xb is None:
@@ -877,6 +919,78 @@ def multiclass_step(state: PoolState, unlabeled_idx, forest: Forest, k: int,
     return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, counts=(counts, loc))
 
 
+def multiclass_density_step(state: PoolState, unlabeled_idx, forest: Forest, k: int, beta: float = 1.0,
+                            density_fixed=None, mode: str = "gram") -> Selection:
+    """One density-weighted iteration over a C-class forest (C >= 2): score =
+    class entropy x d^beta, descending; exact canonical selection (DESIGN.md,
+    "K2 multiclass, density-weighted").
+
+    mode "gram": as density_step's unfused branch -- on a cold pool the Gram
+    goes first with the canonical column sum on the side stream, then
+    dal_forest_score_multiclass_dw (interval keys, per-row entropy and the
+    identity index) and dal_dw_select with lut = entropy, votes = row index:
+    its fp64 re-rank forms entropy[i] * (canonical density)^beta.  No fused
+    step, blocked copy or graph: a warm step runs the same kernel on the
+    row-major pool.  mode "separable": the exact O(N*D) density, canonical
+    scores for every row and a plain top-k.
+    The Selection carries ``counts`` ([U, C] uint8); ``votes`` is None."""
+    if mode not in ("gram", "separable"):
+        raise ValueError(f"density mode must be 'gram' or 'separable', not {mode!r}")
+    unl = _as_index(unlabeled_idx, state.device)
+    if int(unl.shape[0]) == 0:
+        raise ValueError("unlabeled set is empty (the reference loop breaks here)")
+    if mode == "separable":
+        flags, unl, n_cand = state.row_flags(unl)
+        kk = min(int(k), n_cand)
+        loc = state.local_positions(unl)
+        counts, _, _, _, scores, keys, _ = forest_score_multiclass_dw(
+            state, forest, flags, state.density_exact(), DAL_DENSITY_EXACT, beta=beta, want_hi=False)
+        idx, _ = topk_keys(keys, kk, state.row_base)
+        sel_scores = scores[idx - state.row_base]
+        state.check_status()
+        return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, counts=(counts, loc))
+    # the density GEMM goes to the GPU first; the host prepares the rest while it runs
+    dens, colsum_ready = _density_for_step(state, density_fixed)
+    flags, unl, n_cand = state.row_flags(unl)
+    kk = min(int(k), n_cand)
+    loc = state.local_positions(unl)
+    counts, _, entropy, row_index, scores, keys_lo, keys_hi = forest_score_multiclass_dw(
+        state, forest, flags, dens, DAL_DENSITY_FIXED, density_err=density_error(state), beta=beta, want_hi=True)
+    # the main stream joins the column sum inside the call, just before the re-rank
+    idx, sel_scores, _ = dw_select_local(state, flags, row_index, keys_lo, keys_hi, entropy, kk, beta,
+                                         state.colsum(), colsum_ready=colsum_ready)
+    state.check_status(state.last_status)  # the word dw_select_local read (no second sync)
+    return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, counts=(counts, loc))
+
+
+def _density_for_step(state: PoolState, density_fixed=None):
+    """The fixed-point Gram density a density-weighted step scores with:
+    (density, colsum_ready).  On a cold pool the Gram is queued here, first,
+    and the canonical column sum (only the exact re-rank needs it) runs on a
+    side stream AFTER it, beside the vote / score chain (beside the Gram
+    itself it would slow the persistent Gram blocks); colsum_ready is then
+    the event recorded behind it, else None."""
+    if density_fixed is None and state._density is None and state._colsum is None and state.n:
+        torch = _torch()
+        # the fused prep also writes the canonical column-sum partials (the side
+        # stream below then only reduces them: 56 us less per config-2 step than
+        # computing them after the Gram) and zeroes the density accumulator
+        acc = torch.empty(state.n_pad, dtype=torch.int64, device=state.device)
+        state.gram_operand(with_partials=True, acc_zero=acc)
+        state._acc_pre = acc
+        dens = state.density_fixed()
+        main = torch.cuda.current_stream(state.device)
+        side = _side_stream(state.device)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            cs = state.colsum()
+            colsum_ready = torch.cuda.Event()
+            colsum_ready.record(side)
+        cs.record_stream(main)
+        return dens, colsum_ready
+    return (state.density_fixed() if density_fixed is None else density_fixed), None
+
+
 def density_step(state: PoolState, unlabeled_idx, forest: Forest, k: int, beta: float = 1.0,
                  density_fixed=None, mode: str = "gram") -> Selection:
     """One iteration of density_weighting.py:133-176 on the GPU:
@@ -896,33 +1010,11 @@ def density_step(state: PoolState, unlabeled_idx, forest: Forest, k: int, beta: 
     if (state.use_graphs and density_fixed is None and state._density is not None and state._colsum is not None
             and state.row_base == 0 and state.n == state.n_total and state.events_off()):
         return _density_step_graph(state, unl, forest, min(int(k), int(unl.shape[0])), beta)
-    # the density GEMM goes to the GPU first; the host prepares the rest while it runs
-    colsum_ready = None
     # warm (density cached): the score kernel reads the pool's blocked copy
     # (built by the first warm step); the cold step keeps the row-major kernel
     xb = state.blocked_pool(forest) if state._density is not None or density_fixed is not None else None
-    if density_fixed is None and state._density is None and state._colsum is None and state.n:
-        # cold step: the canonical column sum (only the exact re-rank needs it)
-        # runs on a side stream AFTER the Gram, beside the vote / score chain
-        # (beside the Gram itself it would slow the persistent Gram blocks)
-        torch = _torch()
-        # the fused prep also writes the canonical column-sum partials (the side
-        # stream below then only reduces them: 56 us less per config-2 step than
-        # computing them after the Gram) and zeroes the density accumulator
-        acc = torch.empty(state.n_pad, dtype=torch.int64, device=state.device)
-        state.gram_operand(with_partials=True, acc_zero=acc)
-        state._acc_pre = acc
-        dens = state.density_fixed()
-        main = torch.cuda.current_stream(state.device)
-        side = _side_stream(state.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            cs = state.colsum()
-            colsum_ready = torch.cuda.Event()
-            colsum_ready.record(side)
-        cs.record_stream(main)
-    else:
-        dens = state.density_fixed() if density_fixed is None else density_fixed
+    # the density GEMM goes to the GPU first; the host prepares the rest while it runs
+    dens, colsum_ready = _density_for_step(state, density_fixed)
     flags, unl, n_cand = state.row_flags(unl)
     kk = min(int(k), n_cand)
     loc = state.local_positions(unl)

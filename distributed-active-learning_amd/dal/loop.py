@@ -91,11 +91,15 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
              seed: int = 0, select_fn=None, device=None, beta: float = 1.0,
              verbose: bool = False, trainer="gpu") -> LoopResult:
     """Run the AL loop.  strategy: "uncertainty" (uncertainty_sampling.py),
-    "density" (density_weighting.py, E = L0 = range(window_size)) or "random".
+    "density" (density_weighting.py, E = L0 = range(window_size)),
+    "information_density" (class entropy x density, E = L0;
+    density_weighting.select_multiclass) or "random".
     trainer: see train_forest.  Labels of more than two values: "uncertainty"
-    scores the C-class forest (Forest.from_sklearn(rf, multiclass=True)) and
-    needs trainer="sklearn" or a callable; "density" and trainer="gpu" are
-    binary and raise ValueError.
+    and "information_density" score the C-class forest
+    (Forest.from_sklearn(rf, multiclass=True)) and need trainer="sklearn" or a
+    callable; "density" and trainer="gpu" are binary and raise ValueError.
+    "information_density" takes the per-class votes for any label count (two
+    labels: the two-term entropy, from any trainer).
 
     ``select_fn(strategy, pool, unlabeled, model, k) -> indices`` can replace
     the GPU step (tests use the oracle); by default the dal GPU path runs.
@@ -121,7 +125,7 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     if select_fn is None and strategy != "random":
         from .engine import PoolState
 
-        excluded = np.arange(len(labeled)) if strategy == "density" else None
+        excluded = np.arange(len(labeled)) if strategy in ("density", "information_density") else None
         state = PoolState(X, excluded=excluded, device=device)
     it = 1
     while True:
@@ -151,13 +155,17 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
             chosen = np.asarray(select_fn(strategy, X, unlabeled, rf, k))
         else:
             forest = rf.forest if isinstance(rf, GpuForestModel) else \
-                Forest.from_sklearn(rf, multiclass=True) if multiclass else Forest.from_sklearn(rf)
+                Forest.from_sklearn(rf, multiclass=True) if multiclass or strategy == "information_density" \
+                else Forest.from_sklearn(rf)
             if strategy == "uncertainty":
                 from .uncertainty_sampling import select
                 sel = select(state, unlabeled, forest, k)
             elif strategy == "density":
                 from .density_weighting import select
                 sel = select(state, unlabeled, forest, k, beta=beta)
+            elif strategy == "information_density":
+                from .density_weighting import select_multiclass
+                sel = select_multiclass(state, unlabeled, forest, k, beta=beta)
             else:
                 raise ValueError(f"unknown strategy {strategy!r}")
             chosen = sel.indices.cpu().numpy()

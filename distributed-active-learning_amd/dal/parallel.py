@@ -41,6 +41,10 @@ from ._lib import DAL_ASCENDING, DAL_CANON_CHUNK, DAL_DESCENDING, DAL_KEY_NONE, 
 # (a persistent Gram grid would otherwise hold every CU's registers and LDS).
 RCCL_RESERVED_CUS = 8
 
+# selection modes that score with the density: "dw" (binary, the reference's
+# one-sided entropy) and "dw_multiclass" (class entropy, any C >= 2)
+DENSITY_MODES = ("dw", "dw_multiclass")
+
 
 def shard_rows(n_total: int, world: int) -> int:
     """Rows per shard: ceil(N / P) rounded up to the row granule (512)."""
@@ -306,7 +310,10 @@ class ShardedSelector:
     def local_select(self, u_full, partials_full, unlabeled_idx, forest, k: int, mode: str = "dw",
                      strategy: str = "least_confidence", beta: float = 1.0,
                      density_mode: str = "gram", warm: bool = None) -> LocalTopk:
-        """This rank's exact local top-k.  ``warm``: the density was cached
+        """This rank's exact local top-k.  mode: "us" (uncertainty), "dw"
+        (binary density weighting) or "dw_multiclass" (class entropy x
+        density, any forest of two or more classes; always the row-major
+        score kernel and dal_dw_select).  ``warm``: the density was cached
         before this step (the score kernel then reads the shard's blocked
         copy, as the single-GPU warm step does; a cold step keeps the
         row-major kernel and builds no copy).  None: cached now."""
@@ -353,6 +360,26 @@ class ShardedSelector:
                                                    density_err=density_error(st), beta=beta, want_hi=True,
                                                    xb=xb)
                 i, s, kk_keys = dw_select_local(st, flags, votes, klo, khi, lut_dev, kk, beta, colsum,
+                                                cap_scale=self.cap_scale, sync=False)
+        elif mode == "dw_multiclass":
+            # class entropy x density (any C >= 2): the C-class score kernel's
+            # density-weighted form on the row-major shard, then the same
+            # exact selection with lut = entropy, votes = the identity index
+            from ._lib import DAL_DENSITY_EXACT, DAL_DENSITY_FIXED
+            from .engine import forest_score_multiclass_dw
+
+            colsum = self.global_colsum(partials_full)
+            if density_mode == "separable":
+                _, _, _, _, sc, kys, _ = forest_score_multiclass_dw(
+                    st, forest, flags, st.density_exact(colsum), DAL_DENSITY_EXACT, beta=beta, want_hi=False)
+                i, kk_keys = topk_keys(kys, kk, st.row_base)
+                s = sc[i - st.row_base]
+            else:
+                dens = self.local_density(u_full)
+                _, _, ent, rix, _, klo, khi = forest_score_multiclass_dw(
+                    st, forest, flags, dens, DAL_DENSITY_FIXED, density_err=density_error(st), beta=beta,
+                    want_hi=True)
+                i, s, kk_keys = dw_select_local(st, flags, rix, klo, khi, ent, kk, beta, colsum,
                                                 cap_scale=self.cap_scale, sync=False)
         elif forest.n_classes > 2:  # multiclass uncertainty: the C-class kernel, the same merge
             from .engine import MULTICLASS_KINDS, device_multiclass_lut, forest_score_multiclass
@@ -489,7 +516,7 @@ def select(sel: ShardedSelector, comm, unlabeled_idx, forest, k: int, mode: str 
     unl = sel.index_tensor(unlabeled_idx)
     u_full = parts_full = None
     warm = sel._density is not None  # (a cold step's score kernel keeps the row-major pool)
-    if mode == "dw":  # uncertainty sampling never normalises (no density, no zero-norm check)
+    if mode in DENSITY_MODES:  # uncertainty sampling never normalises (no density, no zero-norm check)
         need_u = density_mode == "gram" and sel._density is None
         if need_u or sel._parts_full is None:
             u_local, parts = sel.prep()
@@ -529,7 +556,7 @@ def select(sel: ShardedSelector, comm, unlabeled_idx, forest, k: int, mode: str 
 
 def _finish(sel, comm, unlabeled_idx, forest, k, mode, strategy, beta, sort_fn, density_mode, out, st):
     """Act on the OR of every rank's status word (identical on all ranks)."""
-    if mode != "dw":
+    if mode not in DENSITY_MODES:
         st &= ~_lib.DAL_FLAG_ZERO_NORM  # a zero row only matters to the cosine density
     if st & _lib.DAL_FLAG_ZERO_NORM:
         raise ValueError("pool contains a zero-norm row: cosine similarity is undefined "
@@ -608,11 +635,11 @@ def emulate(selectors, unlabeled_idx, forest, k: int, mode: str = "dw",
     """Run P shards in one process (tests): the all-gathers become concatenations."""
     torch = __import__("torch")
     u_full = parts_full = None
-    if mode == "dw":  # uncertainty sampling never normalises
+    if mode in DENSITY_MODES:  # uncertainty sampling never normalises
         preps = [s.prep() for s in selectors]
         u_full = torch.cat([p[0] for p in preps])
         parts_full = torch.cat([p[1] for p in preps])
-    if mode == "dw" and density_mode == "gram" and selectors and selectors[0]._density is None:
+    if mode in DENSITY_MODES and density_mode == "gram" and selectors and selectors[0]._density is None:
         for s in selectors:
             s.set_density(s.density_contribution(u_full))
     tops = [s.local_select(u_full, parts_full, unlabeled_idx, forest, k, mode, strategy, beta,

@@ -312,6 +312,35 @@ int dal_forest_score_multiclass(const float* x, int64_t n, int64_t d, int64_t ld
                                 const uint8_t* row_flags, int order, uint8_t* counts, uint8_t* pred,
                                 double* scores, uint64_t* keys, dal_stream_t stream);
 
+/* ---- (a5-a10, C classes) class entropy x density^beta, interval keys -----
+ * The C-class reading of density_weighting.py:148-167's e*d product (a new
+ * definition: the reference's one-sided -(1-p) log2(1-p) has no C-class form;
+ * at n_classes = 2 this is the two-term Shannon entropy).  A new symbol only:
+ * dal_abi_version() stays 10.  Forest, counts and pred as
+ * dal_forest_score_multiclass; lut = dal.luts.multiclass_lut("entropy", T):
+ *   entropy[i]   = ((0.0 + lut[n_0]) + lut[n_1]) + ...   class order, >= +0.0
+ *   scores[i]    = entropy[i] * d_i^beta   (one fp64 multiply, no FMA; d_i^beta
+ *                  = d_i at beta == 1), NaN for DAL_ROW_EXCLUDED rows
+ *   row_index[i] = i   (int32: n <= INT32_MAX, else DAL_ERR_SHAPE)
+ * d_i and the keys as dal_forest_score's density mode, always descending:
+ * density_kind DAL_DENSITY_FIXED ((int64*)density)[i] * 2^-32, the GEMM
+ * accumulator, |d - d_canonical| <= density_err: keys[i] is the key of the
+ * pessimistic end scores[i] - err_i, keys_hi[i] (nullable) of the optimistic
+ * end scores[i] + err_i, err_i = entropy[i] * density_err at beta == 1 (the
+ * d^beta image of the interval otherwise), floored at |scores[i]| * 4.5e-16;
+ * DAL_DENSITY_EXACT ((double*)density)[i], canonical fp64: keys_hi == keys.
+ * Point intervals (entropy 0, NaN) have keys_hi == keys; rows that are not
+ * DAL_ROW_CANDIDATE (row_flags NULL: every row is one) get DAL_KEY_NONE in
+ * both.  The exact selection is dal_dw_select unchanged, with votes =
+ * row_index and lut = entropy: its re-rank then forms entropy[i] *
+ * (canonical density)^beta.  n == 0 returns DAL_OK before any device call. */
+int dal_forest_score_multiclass_dw(const float* x, int64_t n, int64_t d, int64_t ldx,
+                                   const int32_t* inner, const uint8_t* leaf, int32_t n_trees, int32_t depth,
+                                   int32_t n_classes, const double* lut, const void* density,
+                                   int density_kind, double density_err, const uint8_t* row_flags, double beta,
+                                   uint8_t* counts, uint8_t* pred, double* entropy, int32_t* row_index,
+                                   double* scores, uint64_t* keys, uint64_t* keys_hi, dal_stream_t stream);
+
 /* ---- (a11) top-k: sortBy(score).take(k) --------------------------------
  * Replaces uncertainty_sampling.py:106,109 / density_weighting.py:168,172.
  * The k smallest keys, ties -> lower index; out_idx = idx_base + row, sorted
