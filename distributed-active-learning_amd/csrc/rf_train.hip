@@ -33,12 +33,12 @@
 #include <climits>
 
 #include "common.hpp"
+#include "rf_train_shared.hpp"
 
 namespace dal {
 namespace {
 
 constexpr int kSortThreads = 1024;
-constexpr uint8_t kAbsent = 0, kOpen = 1, kLeaf = 2;
 
 __device__ __forceinline__ double gini2(int64_t c0, int64_t c1) {
   const double total = static_cast<double>(c0) + static_cast<double>(c1);
@@ -208,27 +208,6 @@ __global__ void rf_bin_kernel(const float* __restrict__ x, int64_t n, int d, int
   }
 }
 
-struct RfArgs {
-  const uint8_t* bins;     // [n][d]
-  const uint8_t* labels;   // [n]
-  const int32_t* weights;  // [T][n]
-  const int32_t* subsets;  // [T][n_inner][m]
-  const float* thresholds;
-  const int32_t* n_splits;
-  int64_t n;
-  int d, m, T, max_depth, hb, kmax;
-  int min_instances;
-  double min_gain;
-  int32_t* node;       // [T][n] heap index at the previous level (-1 settled)
-  uint8_t* status;     // [T][n_all]
-  int32_t* split_f;    // [T][n_inner]
-  int32_t* split_b;    // [T][n_inner]
-  int32_t* hist;       // [T][2^l][m][hb][2] for the current level
-  int32_t* cls;        // [T][2^l][2]
-  int32_t* out_inner;  // [T][n_inner][2]
-  uint8_t* out_leaf;   // [T][n_leaf]
-};
-
 // Route every (tree, row) of positive weight from level l-1 to level l, and
 // accumulate the class counts of every live node and the (feature, bin, class)
 // histograms of the open ones.
@@ -392,32 +371,31 @@ __global__ void rf_init_status_kernel(uint8_t* status, int T, int64_t n_all) {
   if (t < T) status[static_cast<int64_t>(t) * n_all] = kOpen;
 }
 
-struct RfLayout {
-  size_t bins, node, status, split_f, split_b, hist, cls, total;
-};
+}  // namespace
 
-RfLayout rf_layout(int64_t n, int64_t d, int64_t T, int max_depth, int64_t m, int64_t hb) {
-  RfLayout L{};
-  const int64_t n_inner = (int64_t{1} << max_depth) - 1;
-  const int64_t split_nodes = int64_t{1} << (max_depth - 1);  // deepest level that is split
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += static_cast<size_t>(round_up(static_cast<int64_t>(bytes), 256));
-    return at;
-  };
-  L.bins = take(static_cast<size_t>(n * d));
-  L.node = take(static_cast<size_t>(T * n * 4));
-  L.status = take(static_cast<size_t>(T * (2 * n_inner + 1)));
-  L.split_f = take(static_cast<size_t>(T * n_inner * 4));
-  L.split_b = take(static_cast<size_t>(T * n_inner * 4));
-  L.hist = take(static_cast<size_t>(T * split_nodes * m * hb * 2 * 4));
-  L.cls = take(static_cast<size_t>(T * (n_inner + 1) * 2 * 4));
-  L.total = o;
-  return L;
+int rf_launch_bin_and_reset(const float* x, int64_t ldx, const RfArgs& A, hipStream_t st) {
+  const int64_t n_inner = (int64_t{1} << A.max_depth) - 1;
+  hipLaunchKernelGGL(rf_bin_kernel, dim3(static_cast<unsigned>(std::min<int64_t>(ceil_div(A.n * A.d, 256), 4096))),
+                     dim3(256), 0, st, x, A.n, A.d, ldx, A.thresholds, A.n_splits, const_cast<uint8_t*>(A.bins));
+  DAL_RETURN_IF_LAUNCH_FAILED();
+  // root open, everything else absent
+  if (hipMemsetAsync(A.status, 0, static_cast<size_t>(A.T) * (2 * n_inner + 1), st) != hipSuccess)
+    return DAL_ERR_HIP;
+  hipLaunchKernelGGL(rf_init_status_kernel, dim3(static_cast<unsigned>(ceil_div(A.T, 256))), dim3(256), 0, st,
+                     A.status, A.T, 2 * n_inner + 1);
+  DAL_RETURN_IF_LAUNCH_FAILED();
+  return DAL_OK;
 }
 
-}  // namespace
+int rf_launch_finalize(const RfArgs& A, hipStream_t st) {
+  const int64_t n_inner = (int64_t{1} << A.max_depth) - 1;
+  hipLaunchKernelGGL(rf_finalize_kernel,
+                     dim3(static_cast<unsigned>(std::min<int64_t>(ceil_div(A.T * n_inner, 256), 4096))), dim3(256),
+                     0, st, A);
+  DAL_RETURN_IF_LAUNCH_FAILED();
+  return DAL_OK;
+}
+
 }  // namespace dal
 
 using namespace dal;
@@ -446,7 +424,7 @@ extern "C" size_t dal_rf_train_workspace_bytes(int64_t n, int64_t d, int32_t n_t
                                                int32_t num_splits) {
   if (n < 1 || d < 1 || n_trees < 1 || max_depth < 1 || max_depth > DAL_RF_MAX_DEPTH || m < 1 || num_splits < 0)
     return 0;
-  return rf_layout(n, d, n_trees, max_depth, m, num_splits + 2).total;
+  return rf_layout(n, d, n_trees, max_depth, m, num_splits + 2, 2, 0).total;
 }
 
 extern "C" int dal_rf_train(const float* x, int64_t n, int64_t d, int64_t ldx, const uint8_t* labels,
@@ -462,7 +440,7 @@ extern "C" int dal_rf_train(const float* x, int64_t n, int64_t d, int64_t ldx, c
   const int hb = num_splits + 2;  // find_splits emits at most num_splits + 1 thresholds
   // the split kernel keeps one node's whole (slot, bin, class) histogram in LDS
   if (static_cast<int64_t>(m) * hb * 2 * 4 > DAL_RF_SPLIT_LDS_BYTES) return DAL_ERR_UNSUPPORTED;
-  const RfLayout L = rf_layout(n, d, n_trees, max_depth, m, hb);
+  const RfLayout L = rf_layout(n, d, n_trees, max_depth, m, hb, 2, 0);
   if (ws_bytes < L.total || reinterpret_cast<uintptr_t>(ws) % 256) return DAL_ERR_SHAPE;
   hipStream_t st = as_stream(stream);
   unsigned char* w = static_cast<unsigned char*>(ws);
@@ -490,18 +468,8 @@ extern "C" int dal_rf_train(const float* x, int64_t n, int64_t d, int64_t ldx, c
   A.cls = reinterpret_cast<int32_t*>(w + L.cls);
   A.out_inner = out_inner;
   A.out_leaf = out_leaf;
-  const int64_t n_inner = (int64_t{1} << max_depth) - 1;
 
-  hipLaunchKernelGGL(rf_bin_kernel, dim3(static_cast<unsigned>(std::min<int64_t>(ceil_div(n * d, 256), 4096))),
-                     dim3(256), 0, st, x, n, static_cast<int>(d), ldx, thresholds, n_splits,
-                     const_cast<uint8_t*>(A.bins));
-  DAL_RETURN_IF_LAUNCH_FAILED();
-  // root open, everything else absent
-  if (hipMemsetAsync(A.status, 0, static_cast<size_t>(n_trees) * (2 * n_inner + 1), st) != hipSuccess)
-    return DAL_ERR_HIP;
-  hipLaunchKernelGGL(rf_init_status_kernel, dim3(static_cast<unsigned>(ceil_div(n_trees, 256))), dim3(256), 0, st,
-                     A.status, n_trees, 2 * n_inner + 1);
-  DAL_RETURN_IF_LAUNCH_FAILED();
+  if (const int rc = rf_launch_bin_and_reset(x, ldx, A, st)) return rc;
   const int rows_per_block = 1024;
   const dim3 hgrid(static_cast<unsigned>(ceil_div(n, rows_per_block)), static_cast<unsigned>(n_trees));
   for (int level = 0; level <= max_depth; ++level) {
@@ -527,9 +495,5 @@ extern "C" int dal_rf_train(const float* x, int64_t n, int64_t d, int64_t ldx, c
                        dim3(64), ssmem, st, A, level);
     DAL_RETURN_IF_LAUNCH_FAILED();
   }
-  hipLaunchKernelGGL(rf_finalize_kernel,
-                     dim3(static_cast<unsigned>(std::min<int64_t>(ceil_div(n_trees * n_inner, 256), 4096))),
-                     dim3(256), 0, st, A);
-  DAL_RETURN_IF_LAUNCH_FAILED();
-  return DAL_OK;
+  return rf_launch_finalize(A, st);
 }

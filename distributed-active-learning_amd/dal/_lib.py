@@ -156,6 +156,11 @@ SIGNATURES = {
     "dal_rf_train": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32,
                              c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_void_p,
                              c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dal_rf_train_multiclass_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                                           c_int32]),
+    "dal_rf_train_multiclass": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32,
+                                        c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_int32,
+                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

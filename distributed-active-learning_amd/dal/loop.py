@@ -16,7 +16,8 @@ GPU query step:
 
 Forest training (RandomForest.trainClassifier, uncertainty_sampling.py:71-76)
 runs on the GPU by default (dal.random_forest: MLlib 2.1's gini / maxDepth 4 /
-maxBins 32 / sqrt-feature algorithm, seeded bagging draws); trainer="sklearn"
+maxBins 32 / sqrt-feature algorithm, seeded bagging draws; binary labels, or
+C classes when ``num_classes`` is given); trainer="sklearn"
 keeps the scikit-learn fit of round 1.  The selection step is the GPU path
 (dal.uncertainty_sampling / dal.density_weighting).  The random baseline
 (random_sampling.py:88-89, ``sortBy(np.random.uniform).take``) has no
@@ -50,25 +51,29 @@ class GpuForestModel:
         self.device = device
 
     def predict(self, X):
+        """Labels: ``forest.classes_[class id]`` where the forest carries labels."""
         from .random_forest import predict
 
         labels, _ = predict(self.forest, X, device=self.device)
-        return labels.cpu().numpy()
+        labels = labels.cpu().numpy()
+        return labels if self.forest.classes_ is None else np.asarray(self.forest.classes_)[labels]
 
 
 def train_forest(X, y, n_estimators: int = 10, seed: int = 0, max_depth: int = 4, trainer="gpu",
-                 device=None):
+                 device=None, num_classes=None):
     """RandomForest.trainClassifier(numTrees=T, featureSubsetStrategy='auto',
     impurity='gini') with MLlib's default maxDepth=4.  trainer: "gpu"
     (dal.random_forest), "sklearn", or a callable (X, y, T, seed) -> model with
-    ``predict``."""
+    ``predict``.  num_classes: MLlib's numClasses for the GPU trainer (y then
+    holds class ids in [0, num_classes)); None = binary labels in {0, 1}."""
     if callable(trainer):
         return trainer(X, y, n_estimators, seed)
     if trainer == "gpu":
         from .random_forest import train_classifier
 
+        kw = {} if num_classes is None else {"num_classes": int(num_classes)}
         return GpuForestModel(train_classifier(X, y, n_estimators, max_depth=max_depth, seed=seed,
-                                               device=device), device)
+                                               device=device, **kw), device)
     if trainer != "sklearn":
         raise ValueError(f"unknown trainer {trainer!r}")
     from sklearn.ensemble import RandomForestClassifier
@@ -89,7 +94,7 @@ class LoopResult:
 def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
              window_size: int = 10, n_estimators: int = 10, max_iterations=None,
              seed: int = 0, select_fn=None, device=None, beta: float = 1.0,
-             verbose: bool = False, trainer="gpu") -> LoopResult:
+             verbose: bool = False, trainer="gpu", num_classes=None) -> LoopResult:
     """Run the AL loop.  strategy: "uncertainty" (uncertainty_sampling.py),
     "density" (density_weighting.py, E = L0 = range(window_size)),
     "information_density" (class entropy x density, E = L0;
@@ -97,7 +102,13 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     trainer: see train_forest.  Labels of more than two values: "uncertainty"
     and "information_density" score the C-class forest
     (Forest.from_sklearn(rf, multiclass=True)) and need trainer="sklearn" or a
-    callable; "density" and trainer="gpu" are binary and raise ValueError.
+    callable, or trainer="gpu" with ``num_classes`` (below); "density" is
+    binary, as is trainer="gpu" without ``num_classes``: both raise ValueError.
+    num_classes: MLlib's numClasses, at least the number of distinct values
+    of y (explicit, because a labeled window can lack a class).  The GPU
+    trainer then fits C-class forests on the class ids (the position of a label
+    in np.unique(y)) and the forest's ``classes_`` maps ids back to labels;
+    train -> score -> select then all run on the GPU.
     "information_density" takes the per-class votes for any label count (two
     labels: the two-term entropy, from any trainer).
 
@@ -108,14 +119,22 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
 
     # more than two label values: multiclass uncertainty sampling (per-class
     # votes, dal.engine.multiclass_step) over a scikit-learn or caller-trained
-    # forest; the GPU trainer and density weighting are binary
-    multiclass = np.unique(np.asarray(y)).size > 2
-    if multiclass and strategy == "density":
+    # forest, or one the GPU trainer fits when num_classes is given; density
+    # weighting is binary
+    classes = np.unique(np.asarray(y))
+    multiclass = classes.size > 2
+    if num_classes is not None and int(num_classes) < max(classes.size, 2):
+        raise ValueError(f"num_classes={num_classes} is less than the {max(classes.size, 2)} label values "
+                         "(at least two) it must cover")
+    if (multiclass or (num_classes is not None and int(num_classes) > 2)) and strategy == "density":
         raise ValueError("strategy='density' is binary only: y holds more than two label values "
                          "(use strategy='uncertainty')")
-    if multiclass and trainer == "gpu":
-        raise ValueError("trainer='gpu' (dal.random_forest) trains binary forests only: y holds more than "
-                         "two label values (use trainer='sklearn' or a callable)")
+    if multiclass and trainer == "gpu" and num_classes is None:
+        raise ValueError("trainer='gpu' (dal.random_forest) trains binary forests only unless num_classes= is "
+                         "given: y holds more than two label values (pass num_classes=, or use "
+                         "trainer='sklearn' or a callable)")
+    # class ids for the GPU trainer: the label's position in np.unique(y)
+    y_fit = np.searchsorted(classes, np.asarray(y)) if num_classes is not None and trainer == "gpu" else y
     n = X.shape[0]
     labeled = list(range(min(window_size, n)))
     unlabeled = np.arange(len(labeled), n, dtype=np.int64)
@@ -138,7 +157,10 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
         if max_iterations is not None and it > max_iterations:
             break
         lab = np.asarray(labeled)
-        rf = train_forest(X[lab], y[lab], n_estimators, seed + it, trainer=trainer, device=device)
+        rf = train_forest(X[lab], y_fit[lab], n_estimators, seed + it, trainer=trainer, device=device,
+                          num_classes=num_classes)
+        if y_fit is not y:
+            rf.forest.classes_ = classes
         acc = None
         if X_test is not None:
             if isinstance(rf, GpuForestModel) and test_state is None:

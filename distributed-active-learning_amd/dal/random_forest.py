@@ -16,6 +16,10 @@ the Poisson(1) bootstrap weights and the per-node feature subsets -- with
 numpy (seeded), so a fit is deterministic; the oracle (oracle/rf_oracle.py)
 takes the same draws.  The result is a ``dal.forest.Forest`` in the heap
 layout the selection kernels consume, already resident on the device.
+
+``num_classes`` > 2 (MLlib's numClasses) takes the C-class level kernels of
+csrc/rf_train_multi.hip (dal_rf_train_multiclass): up to DAL_MC_MAX_CLASSES
+classes and DAL_MC_MAX_TREES trees; the binary path is untouched.
 """
 from __future__ import annotations
 
@@ -24,8 +28,8 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (DAL_FLAG_RF_SPLITS, DAL_RF_MAX_DEPTH, DAL_RF_MAX_SPLIT_SAMPLE, DAL_RF_MAX_SPLITS,
-                   DAL_RF_SPLIT_LDS_BYTES, call)
+from ._lib import (DAL_FLAG_RF_SPLITS, DAL_MC_MAX_CLASSES, DAL_MC_MAX_TREES, DAL_RF_MAX_DEPTH,
+                   DAL_RF_MAX_SPLIT_SAMPLE, DAL_RF_MAX_SPLITS, DAL_RF_SPLIT_LDS_BYTES, call)
 from .forest import Forest
 
 
@@ -90,12 +94,32 @@ def _stream(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def check_split_histogram(m: int, n_splits: int) -> None:
-    """dal_rf_train's split kernel holds one node's (feature slot, bin, class)
-    histogram in LDS: m * (n_splits + 2) * 2 int32 counts must fit
-    DAL_RF_SPLIT_LDS_BYTES.  MLlib itself has no such limit; raise a clear
-    error instead of the kernel's DAL_ERR_UNSUPPORTED."""
-    need = int(m) * (int(n_splits) + 2) * 8
+def check_labels(y, n: int, num_classes: int = 2, num_trees=None) -> np.ndarray:
+    """The labels as n class-id bytes, or ValueError: ids lie in
+    [0, num_classes), 2 <= num_classes <= DAL_MC_MAX_CLASSES, and a forest of
+    more than two classes has at most DAL_MC_MAX_TREES trees (the multiclass
+    score kernels take no more).  Pure host code: needs no device."""
+    num_classes = int(num_classes)
+    if not 2 <= num_classes <= DAL_MC_MAX_CLASSES:
+        raise ValueError(f"num_classes must lie in [2, {DAL_MC_MAX_CLASSES}], not {num_classes}")
+    if num_classes > 2 and num_trees is not None and not 1 <= int(num_trees) <= DAL_MC_MAX_TREES:
+        raise ValueError(f"a forest of {num_classes} classes has 1..{DAL_MC_MAX_TREES} trees, not {num_trees}")
+    yv = np.asarray(y).reshape(-1)
+    if num_classes == 2:
+        if yv.shape[0] != n or not np.isin(yv, (0, 1)).all():
+            raise ValueError("labels must be n values in {0, 1}")
+    elif yv.shape[0] != n or not np.isin(yv, np.arange(num_classes)).all():
+        raise ValueError(f"labels must be n class ids in [0, {num_classes})")
+    return yv.astype(np.uint8)
+
+
+def check_split_histogram(m: int, n_splits: int, n_classes: int = 2) -> None:
+    """The split kernel (dal_rf_train, dal_rf_train_multiclass) holds one
+    node's (feature slot, bin, class) histogram in LDS: m * (n_splits + 2) *
+    n_classes int32 counts must fit DAL_RF_SPLIT_LDS_BYTES.  MLlib itself has
+    no such limit; raise a clear error instead of the kernel's
+    DAL_ERR_UNSUPPORTED."""
+    need = int(m) * (int(n_splits) + 2) * int(n_classes) * 4
     if need > DAL_RF_SPLIT_LDS_BYTES:
         raise ValueError(f"{m} candidate features per node x {n_splits + 1} thresholds need {need} bytes of "
                          f"split histogram, more than the GPU trainer's {DAL_RF_SPLIT_LDS_BYTES} "
@@ -104,11 +128,16 @@ def check_split_histogram(m: int, n_splits: int) -> None:
 
 def train_classifier(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: int = 32, seed: int = 0,
                      feature_subset_strategy: str = "auto", weights=None, feature_subsets=None,
-                     min_instances_per_node: int = 1, min_info_gain: float = 0.0, device=None) -> Forest:
-    """RandomForest.trainClassifier(numClasses=2, categoricalFeaturesInfo={},
-    impurity='gini') on the GPU.  X [n, d] (numpy or torch), y labels in {0,1}.
-    ``weights`` [T, n] / ``feature_subsets`` [T, 2^max_depth - 1, m] override
-    the seeded draws (bagging_inputs)."""
+                     min_instances_per_node: int = 1, min_info_gain: float = 0.0, device=None,
+                     num_classes: int = 2) -> Forest:
+    """RandomForest.trainClassifier(numClasses=num_classes,
+    categoricalFeaturesInfo={}, impurity='gini') on the GPU.  X [n, d] (numpy
+    or torch), y labels in {0,1}.  ``weights`` [T, n] / ``feature_subsets``
+    [T, 2^max_depth - 1, m] override the seeded draws (bagging_inputs).
+    num_classes > 2 (dal_rf_train_multiclass, csrc/rf_train_multi.hip): y holds
+    class ids in [0, num_classes), at most DAL_MC_MAX_CLASSES classes and
+    DAL_MC_MAX_TREES trees, and the result is a Forest of n_classes =
+    num_classes for the multiclass score kernels."""
     import torch
 
     from .engine import _require_cuda
@@ -126,10 +155,7 @@ def train_classifier(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: in
     if not 2 <= max_bins <= DAL_RF_MAX_SPLITS:
         raise ValueError(f"max_bins must lie in [2, {DAL_RF_MAX_SPLITS}]")
     yv = y.cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
-    yv = yv.reshape(-1)
-    if yv.shape[0] != n or not np.isin(yv, (0, 1)).all():
-        raise ValueError("labels must be n values in {0, 1}")
-    labels = torch.from_numpy(yv.astype(np.uint8)).to(dev)
+    labels = torch.from_numpy(check_labels(yv, n, num_classes)).to(dev)
     if weights is None or feature_subsets is None:
         w_draw, s_draw = bagging_inputs(n, d, num_trees, max_depth, seed, feature_subset_strategy)
         weights = w_draw if weights is None else weights
@@ -144,7 +170,8 @@ def train_classifier(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: in
     if not 1 <= m <= d:
         raise ValueError("feature subsets must hold 1..d features")
     ns = num_splits(n, max_bins)
-    check_split_histogram(m, ns)
+    check_split_histogram(m, ns, num_classes)
+    check_labels(yv, n, num_classes, num_trees=T)
     rows = split_sample_rows(n, max_bins, seed)
     n_sample = n if rows is None else int(rows.shape[0])
     rows_t = None if rows is None else torch.from_numpy(rows).to(dev)
@@ -154,17 +181,24 @@ def train_classifier(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: in
     s = _stream(dev)
     call("dal_rf_find_splits", x.data_ptr(), n, d, d, 0 if rows_t is None else rows_t.data_ptr(), n_sample, ns,
          thresholds.data_ptr(), n_splits.data_ptr(), status.data_ptr(), s)
-    wsb = int(lib.dal_rf_train_workspace_bytes(n, d, T, max_depth, m, ns))
+    multi = int(num_classes) > 2
+    wsb = int(lib.dal_rf_train_multiclass_workspace_bytes(n, d, T, max_depth, m, ns, int(num_classes))) if multi \
+        else int(lib.dal_rf_train_workspace_bytes(n, d, T, max_depth, m, ns))
     ws = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
     wsp = (ws.data_ptr() + 255) // 256 * 256
     inner = torch.empty((T, n_inner, 2), dtype=torch.int32, device=dev)
     leaf = torch.empty((T, n_inner + 1), dtype=torch.uint8, device=dev)
-    call("dal_rf_train", x.data_ptr(), n, d, d, labels.data_ptr(), thresholds.data_ptr(), n_splits.data_ptr(), ns,
-         w.data_ptr(), sub.data_ptr(), m, T, max_depth, int(min_instances_per_node), float(min_info_gain),
-         inner.data_ptr(), leaf.data_ptr(), wsp, wsb, s)
+    head = (x.data_ptr(), n, d, d, labels.data_ptr(), thresholds.data_ptr(), n_splits.data_ptr(), ns,
+            w.data_ptr(), sub.data_ptr(), m, T, max_depth, int(min_instances_per_node), float(min_info_gain))
+    tail = (inner.data_ptr(), leaf.data_ptr(), wsp, wsb, s)
+    if multi:
+        call("dal_rf_train_multiclass", *head, int(num_classes), *tail)
+    else:
+        call("dal_rf_train", *head, *tail)
     if int(status.item()) & DAL_FLAG_RF_SPLITS:
         raise _lib.DalError("threshold search emitted more than num_splits + 1 thresholds")
-    forest = Forest(inner=inner.cpu().numpy(), leaf=leaf.cpu().numpy(), depth=max_depth)
+    forest = Forest(inner=inner.cpu().numpy(), leaf=leaf.cpu().numpy(), depth=max_depth,
+                    n_classes=int(num_classes))
     forest._dev[str(dev)] = (inner, leaf)
     forest.split_thresholds = (thresholds, n_splits)
     return forest

@@ -79,7 +79,7 @@ enum dal_status {
 #define DAL_RF_MAX_SPLITS 255          /* thresholds per feature (bins fit a uint8) */
 #define DAL_RF_MAX_SPLIT_SAMPLE 16384  /* rows one threshold search sorts in LDS */
 #define DAL_RF_MAX_DEPTH 10            /* deepest tree dal_rf_train grows */
-#define DAL_RF_SPLIT_LDS_BYTES 163840  /* m * (num_splits + 2) * 8 must fit (one node's histogram, LDS) */
+#define DAL_RF_SPLIT_LDS_BYTES 163840  /* m * (num_splits + 2) * classes * 4 must fit (one node's histogram, LDS) */
 
 const char* dal_status_string(int status);
 int dal_abi_version(void);
@@ -621,6 +621,37 @@ int dal_rf_train(const float* x, int64_t n, int64_t d, int64_t ldx, const uint8_
                  const int32_t* feature_subsets, int32_t m, int32_t n_trees, int32_t max_depth,
                  int32_t min_instances, double min_info_gain, int32_t* out_inner, uint8_t* out_leaf, void* ws,
                  size_t ws_bytes, dal_stream_t stream);
+
+/* ---- GPU random-forest training, C classes --------------------------------
+ * RandomForest.trainClassifier(train, numClasses=C, ...) of the same call
+ * sites: dal_rf_train with C classes wherever two appear.  New symbols only:
+ * dal_abi_version() stays 10 (absent from older libraries).
+ * labels [n] are class ids < n_classes, 2 <= n_classes <= DAL_MC_MAX_CLASSES
+ * (a larger byte counts as class n_classes - 1: validate before the call).
+ * thresholds / n_splits come from dal_rf_find_splits, which does not depend
+ * on the labels.  Gini over the C weighted counts in fp64 in MLlib's order:
+ * total = sum of the counts, imp = 1, imp -= (c/total)^2 per class in class
+ * order (0 when total == 0), gain = parent - (lc/tc) imp_l - (rc/tc) imp_r;
+ * first maximum over subset order then split index; leaf rules as
+ * dal_rf_train.  Output in dal_forest_score_multiclass's heap layout:
+ * out_inner as dal_rf_train, out_leaf [T][2^D] = class id, the first index of
+ * the largest weighted count.  At n_classes == 2 the output equals
+ * dal_rf_train's byte for byte.  Callers that score the forest keep
+ * n_trees <= DAL_MC_MAX_TREES; the trainer itself does not need it.
+ * Limits, checked before any HIP call (DAL_ERR_UNSUPPORTED): max_depth <=
+ * DAL_RF_MAX_DEPTH, n_classes <= DAL_MC_MAX_CLASSES, and one node's
+ * (slot, class, bin) histogram in LDS: m * (num_splits + 2) * n_classes * 4 <=
+ * DAL_RF_SPLIT_LDS_BYTES (784 features, m = 28, maxBins 32, 32 classes:
+ * 118,272 bytes).  ws: 256-B aligned,
+ * dal_rf_train_multiclass_workspace_bytes(...) bytes (0 for bad arguments). */
+size_t dal_rf_train_multiclass_workspace_bytes(int64_t n, int64_t d, int32_t n_trees, int32_t max_depth,
+                                               int32_t m, int32_t num_splits, int32_t n_classes);
+int dal_rf_train_multiclass(const float* x, int64_t n, int64_t d, int64_t ldx, const uint8_t* labels,
+                            const float* thresholds, const int32_t* n_splits, int32_t num_splits,
+                            const int32_t* weights, const int32_t* feature_subsets, int32_t m, int32_t n_trees,
+                            int32_t max_depth, int32_t min_instances, double min_info_gain, int32_t n_classes,
+                            int32_t* out_inner, uint8_t* out_leaf, void* ws, size_t ws_bytes,
+                            dal_stream_t stream);
 
 /* ---- standalone similarity kernels --------------------------------------
  * cosine_similarity.py:42-45: every entry of U.U^T (fp32 MFMA), written to
