@@ -32,6 +32,12 @@
 // of the binary kernel's density mode, plus the row's entropy and its own
 // index, so that dal_dw_select (lut = entropy, votes = index) re-ranks it
 // unchanged.  The DW = false kernels are the code they were without it.
+//
+// These are the row-major kernels: the cold step's, and every step's when the
+// pool has no blocked copy.  The warm steps' form over the blocked
+// feature-major copy and the prepared forest is forest_multi_blocked.hip
+// (dal_forest_score_multiclass_blocked / _dw_blocked; same outputs, bit for
+// bit), which also falls back to the entries below.
 #include <type_traits>
 
 #include "common.hpp"

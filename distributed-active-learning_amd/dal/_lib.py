@@ -97,6 +97,16 @@ SIGNATURES = {
                                                c_int32, c_int32, c_void_p, c_void_p, c_int, c_double, c_void_p,
                                                c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p]),
+    "dal_forest_multiclass_blocked_rows": (c_int, [c_int64, c_int32, c_int32, c_int32]),
+    "dal_forest_score_multiclass_blocked": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                                    c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int,
+                                                    c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p]),
+    "dal_forest_score_multiclass_dw_blocked": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                                       c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p,
+                                                       c_void_p, c_int, c_double, c_void_p, c_double, c_void_p,
+                                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                       c_void_p]),
     "dal_density_separable": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]),
     "dal_topk_workspace_bytes": (c_size_t, [c_int64, c_int64]),

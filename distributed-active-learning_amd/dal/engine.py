@@ -203,10 +203,14 @@ class PoolState:
         self._split = self._density_exact = self._xb = None
         self._graphs = {}
 
-    def blocked_pool(self, forest, build: bool = True):
+    def blocked_pool(self, forest, build: bool = True, multiclass: bool = None):
         """The pool's blocked feature-major copy (dal_pool_blocked) when the
         forest is one the blocked score kernel applies to (it then reads only
-        the features the forest tests), else None.  Built on first use
+        the features the forest tests), else None.  ``multiclass``: the caller
+        scores with the C-class kernels (their rule,
+        dal_forest_multiclass_blocked_rows, counts the packed counters'
+        exchange region in); None: forest.n_classes > 2 -- a two-class forest
+        scored by the C-class kernels passes True.  Built on first use
         (``build``) on the current stream and kept with the pool's caches:
         the warm steps build it, the cold step keeps the row-major kernel.
         The copy costs another n x d fp32 (2 GB at config 4): it is skipped
@@ -215,7 +219,13 @@ class PoolState:
         if self.n == 0 or not self.blocked_copy:
             return None
         lib = _lib.load()
-        if not lib.dal_forest_blocked_rows(self.d, forest.n_trees, forest.depth):
+        if multiclass is None:
+            multiclass = forest.n_classes > 2
+        if multiclass:
+            if not lib.dal_forest_multiclass_blocked_rows(self.d, forest.n_trees, forest.depth,
+                                                          int(forest.n_classes)):
+                return None
+        elif not lib.dal_forest_blocked_rows(self.d, forest.n_trees, forest.depth):
             return None
         if self._xb is None and build:
             torch = _torch()
@@ -614,10 +624,11 @@ def device_multiclass_lut(strategy: str, n_trees: int, device):
     return _LUT_CACHE[key]
 
 
-def forest_score_multiclass(state: PoolState, forest: Forest, lut_dev, flags, order: int, kind: int):
-    """Launch dal_forest_score_multiclass over the shard; returns (counts
-    uint8 [n, C], pred uint8 [n], scores, keys).  flags None: every row is a
-    candidate."""
+def forest_score_multiclass(state: PoolState, forest: Forest, lut_dev, flags, order: int, kind: int, xb=None):
+    """Launch dal_forest_score_multiclass (dal_forest_score_multiclass_blocked
+    over ``xb``, the pool's blocked copy: same bits) over the shard; returns
+    (counts uint8 [n, C], pred uint8 [n], scores, keys).  flags None: every
+    row is a candidate."""
     torch = _torch()
     forest.check_features(state.d)
     forest.check_classes()
@@ -629,16 +640,21 @@ def forest_score_multiclass(state: PoolState, forest: Forest, lut_dev, flags, or
     pred = torch.empty(n, dtype=torch.uint8, device=state.device)
     scores = torch.empty(n, dtype=torch.float64, device=state.device)
     keys = torch.empty(n, dtype=torch.int64, device=state.device)
-    call("dal_forest_score_multiclass", _ptr(state.x), n, state.d, state.d, _ptr(inner), _ptr(leaf),
-         forest.n_trees, forest.depth, C, _ptr(lut_dev), int(kind), 0 if flags is None else _ptr(flags), int(order),
-         _ptr(counts), _ptr(pred), _ptr(scores), _ptr(keys), _stream(state.device))
+    args = (n, state.d, state.d, _ptr(inner), _ptr(leaf), forest.n_trees, forest.depth, C, _ptr(lut_dev), int(kind),
+            0 if flags is None else _ptr(flags), int(order), _ptr(counts), _ptr(pred), _ptr(scores), _ptr(keys),
+            _stream(state.device))
+    if xb is None:
+        call("dal_forest_score_multiclass", _ptr(state.x), *args)
+    else:
+        call("dal_forest_score_multiclass_blocked", _ptr(state.x), _ptr(xb), _fprep(forest, state, xb), *args)
     return counts, pred, scores, keys
 
 
 def forest_score_multiclass_dw(state: PoolState, forest: Forest, flags, density, density_kind: int,
-                               density_err: float = 0.0, beta: float = 1.0, want_hi: bool = True):
-    """Launch dal_forest_score_multiclass_dw over the shard: class entropy x
-    density^beta, descending, with interval keys.  ``density``: one 8-byte
+                               density_err: float = 0.0, beta: float = 1.0, want_hi: bool = True, xb=None):
+    """Launch dal_forest_score_multiclass_dw (dal_forest_score_multiclass_dw_
+    blocked over ``xb``, the pool's blocked copy: same bits) over the shard:
+    class entropy x density^beta, descending, with interval keys.  ``density``: one 8-byte
     word per row, int64 fixed point (DAL_DENSITY_FIXED) or canonical fp64
     (DAL_DENSITY_EXACT).  Returns (counts uint8 [n, C], pred uint8 [n],
     entropy fp64 [n], row_index int32 [n], scores, keys, keys_hi or None).
@@ -667,10 +683,14 @@ def forest_score_multiclass_dw(state: PoolState, forest: Forest, flags, density,
     if state.forest_events is not None:  # bench: K2 launch timing on the launch stream
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
-    call("dal_forest_score_multiclass_dw", _ptr(state.x), n, state.d, state.d, _ptr(inner), _ptr(leaf),
-         forest.n_trees, forest.depth, C, _ptr(lut_dev), _ptr(density), int(density_kind), float(density_err),
-         0 if flags is None else _ptr(flags), float(beta), _ptr(counts), _ptr(pred), _ptr(entropy),
-         _ptr(row_index), _ptr(scores), _ptr(keys), 0 if keys_hi is None else _ptr(keys_hi), _stream(dev))
+    args = (n, state.d, state.d, _ptr(inner), _ptr(leaf), forest.n_trees, forest.depth, C, _ptr(lut_dev),
+            _ptr(density), int(density_kind), float(density_err), 0 if flags is None else _ptr(flags), float(beta),
+            _ptr(counts), _ptr(pred), _ptr(entropy), _ptr(row_index), _ptr(scores), _ptr(keys),
+            0 if keys_hi is None else _ptr(keys_hi), _stream(dev))
+    if xb is None:
+        call("dal_forest_score_multiclass_dw", _ptr(state.x), *args)
+    else:
+        call("dal_forest_score_multiclass_dw_blocked", _ptr(state.x), _ptr(xb), _fprep(forest, state, xb), *args)
     if ev is not None:
         ev[1].record()
         state.forest_events.append(ev)
@@ -870,14 +890,15 @@ def sort_pairs(keys, idx, k: int, payload=None):
 
 
 # ---------------------------------------------------------------- steps --
-def uncertainty_blocked(state: PoolState, forest: Forest):
+def uncertainty_blocked(state: PoolState, forest: Forest, multiclass: bool = None):
     """The blocked pool copy for an uncertainty step (scores only, no
-    density: every step is alike): built from the pool's second step on --
+    density: every step is alike; ``multiclass`` as PoolState.blocked_pool):
+    built from the pool's second step on --
     the one-off copy costs about five row-major score launches (2M x 256:
     0.92 ms vs 0.2 ms saved per launch), so a pool scored once keeps the
     row-major kernel."""
     state._us_steps += 1
-    return state.blocked_pool(forest, build=state._us_steps > 1)
+    return state.blocked_pool(forest, build=state._us_steps > 1, multiclass=multiclass)
 
 
 def uncertainty_step(state: PoolState, unlabeled_idx, forest: Forest, k: int,
@@ -901,8 +922,9 @@ def uncertainty_step(state: PoolState, unlabeled_idx, forest: Forest, k: int,
 def multiclass_step(state: PoolState, unlabeled_idx, forest: Forest, k: int,
                     strategy: str = "least_confidence") -> Selection:
     """One uncertainty iteration over a C-class forest: per-class votes and
-    the C-class score (dal_forest_score_multiclass), then the top-k of the
-    keys.  The Selection carries ``counts`` ([U, C] uint8); ``votes`` is None."""
+    the C-class score (dal_forest_score_multiclass; from the pool's second
+    uncertainty step on over its blocked copy, the binary policy), then the
+    top-k of the keys.  The Selection carries ``counts`` ([U, C] uint8); ``votes`` is None."""
     if strategy not in MULTICLASS_KINDS:
         raise ValueError(f"strategy must be one of {tuple(MULTICLASS_KINDS)}")
     flags, unl, n_cand = state.row_flags(unlabeled_idx)
@@ -913,7 +935,8 @@ def multiclass_step(state: PoolState, unlabeled_idx, forest: Forest, k: int,
     order = DAL_ASCENDING if MULTICLASS_ASCENDING[strategy] else DAL_DESCENDING
     lut_dev = device_multiclass_lut(strategy, forest.n_trees, state.device)
     counts, _, scores, keys = forest_score_multiclass(state, forest, lut_dev, flags, order,
-                                                      MULTICLASS_KINDS[strategy])
+                                                      MULTICLASS_KINDS[strategy],
+                                                      xb=uncertainty_blocked(state, forest, multiclass=True))
     idx, _ = topk_keys(keys, kk, state.row_base)
     sel_scores = scores[idx - state.row_base]
     return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, counts=(counts, loc))
@@ -929,10 +952,12 @@ def multiclass_density_step(state: PoolState, unlabeled_idx, forest: Forest, k: 
     goes first with the canonical column sum on the side stream, then
     dal_forest_score_multiclass_dw (interval keys, per-row entropy and the
     identity index) and dal_dw_select with lut = entropy, votes = row index:
-    its fp64 re-rank forms entropy[i] * (canonical density)^beta.  No fused
-    step, blocked copy or graph: a warm step runs the same kernel on the
-    row-major pool.  mode "separable": the exact O(N*D) density, canonical
-    scores for every row and a plain top-k.
+    its fp64 re-rank forms entropy[i] * (canonical density)^beta.  A warm
+    step (the density cached or handed in) scores over the pool's blocked
+    copy (dal_forest_score_multiclass_dw_blocked, same bits; density_step's
+    rule), built by the first warm step.  No fused step or graph.
+    mode "separable": the exact O(N*D) density, canonical scores for every
+    row and a plain top-k, on the row-major pool.
     The Selection carries ``counts`` ([U, C] uint8); ``votes`` is None."""
     if mode not in ("gram", "separable"):
         raise ValueError(f"density mode must be 'gram' or 'separable', not {mode!r}")
@@ -949,13 +974,18 @@ def multiclass_density_step(state: PoolState, unlabeled_idx, forest: Forest, k: 
         sel_scores = scores[idx - state.row_base]
         state.check_status()
         return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, counts=(counts, loc))
+    # warm (density cached): the score kernel reads the pool's blocked copy
+    # (built by the first warm step); the cold step keeps the row-major kernel
+    xb = (state.blocked_pool(forest, multiclass=True)
+          if state._density is not None or density_fixed is not None else None)
     # the density GEMM goes to the GPU first; the host prepares the rest while it runs
     dens, colsum_ready = _density_for_step(state, density_fixed)
     flags, unl, n_cand = state.row_flags(unl)
     kk = min(int(k), n_cand)
     loc = state.local_positions(unl)
     counts, _, entropy, row_index, scores, keys_lo, keys_hi = forest_score_multiclass_dw(
-        state, forest, flags, dens, DAL_DENSITY_FIXED, density_err=density_error(state), beta=beta, want_hi=True)
+        state, forest, flags, dens, DAL_DENSITY_FIXED, density_err=density_error(state), beta=beta, want_hi=True,
+        xb=xb)
     # the main stream joins the column sum inside the call, just before the re-rank
     idx, sel_scores, _ = dw_select_local(state, flags, row_index, keys_lo, keys_hi, entropy, kk, beta,
                                          state.colsum(), colsum_ready=colsum_ready)

@@ -312,8 +312,8 @@ class ShardedSelector:
                      density_mode: str = "gram", warm: bool = None) -> LocalTopk:
         """This rank's exact local top-k.  mode: "us" (uncertainty), "dw"
         (binary density weighting) or "dw_multiclass" (class entropy x
-        density, any forest of two or more classes; always the row-major
-        score kernel and dal_dw_select).  ``warm``: the density was cached
+        density, any forest of two or more classes; the C-class score kernel
+        and dal_dw_select).  ``warm``: the density was cached
         before this step (the score kernel then reads the shard's blocked
         copy, as the single-GPU warm step does; a cold step keeps the
         row-major kernel and builds no copy).  None: cached now."""
@@ -363,8 +363,9 @@ class ShardedSelector:
                                                 cap_scale=self.cap_scale, sync=False)
         elif mode == "dw_multiclass":
             # class entropy x density (any C >= 2): the C-class score kernel's
-            # density-weighted form on the row-major shard, then the same
-            # exact selection with lut = entropy, votes = the identity index
+            # density-weighted form (warm: over the shard's blocked copy, as
+            # the binary branch), then the same exact selection with lut =
+            # entropy, votes = the identity index
             from ._lib import DAL_DENSITY_EXACT, DAL_DENSITY_FIXED
             from .engine import forest_score_multiclass_dw
 
@@ -375,10 +376,12 @@ class ShardedSelector:
                 i, kk_keys = topk_keys(kys, kk, st.row_base)
                 s = sc[i - st.row_base]
             else:
+                warm_now = self._density is not None if warm is None else warm
+                xb = st.blocked_pool(forest, multiclass=True) if warm_now else None
                 dens = self.local_density(u_full)
                 _, _, ent, rix, _, klo, khi = forest_score_multiclass_dw(
                     st, forest, flags, dens, DAL_DENSITY_FIXED, density_err=density_error(st), beta=beta,
-                    want_hi=True)
+                    want_hi=True, xb=xb)
                 i, s, kk_keys = dw_select_local(st, flags, rix, klo, khi, ent, kk, beta, colsum,
                                                 cap_scale=self.cap_scale, sync=False)
         elif forest.n_classes > 2:  # multiclass uncertainty: the C-class kernel, the same merge
@@ -387,7 +390,8 @@ class ShardedSelector:
 
             order = DAL_ASCENDING if MULTICLASS_ASCENDING[strategy] else DAL_DESCENDING
             lut_dev = device_multiclass_lut(strategy, forest.n_trees, st.device)
-            _, _, sc, kys = forest_score_multiclass(st, forest, lut_dev, flags, order, MULTICLASS_KINDS[strategy])
+            _, _, sc, kys = forest_score_multiclass(st, forest, lut_dev, flags, order, MULTICLASS_KINDS[strategy],
+                                                    xb=uncertainty_blocked(st, forest, multiclass=True))
             i, kk_keys = topk_keys(kys, kk, st.row_base)
             s = sc[i - st.row_base]
         else:

@@ -299,7 +299,8 @@ int dal_forest_score_blocked(const float* x, const float* xb, const void* fprep,
  * DAL_ROW_CANDIDATE (row_flags NULL: every row is a candidate); select with
  * dal_topk.  A leaf byte >= n_classes is counted for no class (the forest is
  * device data and is not read back; dal.forest.Forest.check_classes checks it
- * before upload).  Uncertainty only: no density, no blocked copy, no plan. */
+ * before upload).  Uncertainty only, on the row-major pool: the density form
+ * and the forms over the blocked copy follow; no plan. */
 #define DAL_MC_MAX_CLASSES 32
 #define DAL_MC_MAX_TREES 255
 #define DAL_MC_LEAST_CONFIDENCE 0
@@ -340,6 +341,51 @@ int dal_forest_score_multiclass_dw(const float* x, int64_t n, int64_t d, int64_t
                                    int density_kind, double density_err, const uint8_t* row_flags, double beta,
                                    uint8_t* counts, uint8_t* pred, double* entropy, int32_t* row_index,
                                    double* scores, uint64_t* keys, uint64_t* keys_hi, dal_stream_t stream);
+
+/* ---- (a5-a10, C classes) the same two over the pool's blocked copy -------
+ * New symbols only: dal_abi_version() stays 10, and a caller probes for the
+ * feature with dal_forest_multiclass_blocked_rows (absent from older
+ * libraries).  xb is dal_pool_blocked's copy of x and fprep dal_forest_prepare's
+ * buffer for the same forest (inner, leaf, n_trees, depth) and d, both
+ * unchanged: one prepared buffer per (forest, d) serves dal_forest_score_blocked
+ * and these entries (it carries the leaf bytes verbatim, so the class ids).
+ * dal_forest_multiclass_blocked_rows is pure host code: 64 (the rows per tile)
+ * when the C-class blocked kernel applies, else 0.  It applies when
+ * dal_forest_blocked_rows(d, n_trees, depth) is non-zero (a prepared forest
+ * exists), 2 <= n_classes <= 32, 1 <= n_trees <= 255, and the block's LDS --
+ * the tile of min(nodes, d) 256-B runs, the prepared payload, the score table
+ * and the cross-wave exchange of the packed counts ((waves - 1) * ceil4(C) / 4
+ * words per row, 4 or 8 waves) -- stays within 96 KiB.
+ * dal_forest_score_multiclass_blocked / dal_forest_score_multiclass_dw_blocked
+ * take x, xb, fprep and then dal_forest_score_multiclass's /
+ * dal_forest_score_multiclass_dw's arguments from n on, and give those
+ * entries' outputs bit for bit (counts, pred, scores, keys; and counts, pred,
+ * entropy, row_index, scores, keys, keys_hi), reading only the features the
+ * forest tests.  xb == NULL runs the row-major kernel on x (fprep ignored).
+ * Otherwise xb must be 16-B aligned; when the rule above gives 0 the row-major
+ * kernel runs on x, same bits, fprep ignored; when it gives 64, fprep must be
+ * non-NULL and 16-B aligned (there is no unprepared form) -- anything else is
+ * DAL_ERR_ARG.  Every other check and status is the row-major entry's: n == 0
+ * returns DAL_OK before any device call, n > INT32_MAX is DAL_ERR_SHAPE for
+ * the density-weighted form.  A leaf byte >= n_classes is counted for no
+ * class; rows past n in the last tile are never written.  A stale fprep
+ * (another forest) gives that forest's votes.  Every inner node's feature must
+ * lie in [0, d): for an invalid forest the outputs are unspecified (the
+ * prepared forest clamps, the row-major kernel does not).  Selection stays
+ * dal_topk / dal_dw_select; there are no step hooks, group minima or plan. */
+int dal_forest_multiclass_blocked_rows(int64_t d, int32_t n_trees, int32_t depth, int32_t n_classes);
+int dal_forest_score_multiclass_blocked(const float* x, const float* xb, const void* fprep, int64_t n, int64_t d,
+                                        int64_t ldx, const int32_t* inner, const uint8_t* leaf, int32_t n_trees,
+                                        int32_t depth, int32_t n_classes, const double* lut, int score_kind,
+                                        const uint8_t* row_flags, int order, uint8_t* counts, uint8_t* pred,
+                                        double* scores, uint64_t* keys, dal_stream_t stream);
+int dal_forest_score_multiclass_dw_blocked(const float* x, const float* xb, const void* fprep, int64_t n, int64_t d,
+                                           int64_t ldx, const int32_t* inner, const uint8_t* leaf,
+                                           int32_t n_trees, int32_t depth, int32_t n_classes, const double* lut,
+                                           const void* density, int density_kind, double density_err,
+                                           const uint8_t* row_flags, double beta, uint8_t* counts, uint8_t* pred,
+                                           double* entropy, int32_t* row_index, double* scores, uint64_t* keys,
+                                           uint64_t* keys_hi, dal_stream_t stream);
 
 /* ---- (a11) top-k: sortBy(score).take(k) --------------------------------
  * Replaces uncertainty_sampling.py:106,109 / density_weighting.py:168,172.
