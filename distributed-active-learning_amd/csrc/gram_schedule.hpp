@@ -110,7 +110,25 @@ struct GramSchedule {
       while (r < rhi && !takes(P, jmap(r))) ++r;
     } else {
       if (!live(rowP(ru, 0))) return -1;
-      while (r < rhi && !takes_u(ru, jmap(r))) ++r;
+      // Away from the unit's own super blocks P0 .. P0 + 2 HV - 2 every part lies
+      // on one side of Q = J >> 1 and they share a parity, so takes_u is the
+      // first (live) part's answer -- P0 + Q odd below the unit, even above it --
+      // and an untaken Q is stepped over whole: two compares and a parity bit
+      // per pair where the loop over the parts was ~100 scalar instructions,
+      // run by all eight waves on the CU's one scalar unit behind every pair's
+      // barrier (round 12).  Near the diagonal, in a skip range and in the
+      // contiguous form the parts are asked one by one as before.
+      const int P0 = rowP(ru, 0);
+      while (r < rhi) {
+        const int J = jmap(r), Q = J >> 1;
+        if (skl == 0 && (Q < P0 || Q > P0 + 2 * HV - 2) && !(J >= skip_lo && J < skip_hi)) {
+          if (((P0 + Q) & 1) == (Q < P0 ? 1 : 0)) break;
+          r = 2 * (Q + 1) - j_lo;  // (skl == 0: jmap(r) is j_lo + r)
+          continue;
+        }
+        if (takes_u(ru, J)) break;
+        ++r;
+      }
     }
     return r < rhi ? r : -1;
   }
@@ -265,6 +283,21 @@ struct GramClaimCursor {
     J = s.jmap(r);
   }
 };
+
+// Where the wide form's wave runs its look-ahead (round 12): the claim handed
+// over, peek() and the DMA issue of the next pair's stage are scalar work no
+// MFMA of the pair reads, ~1,300 cycles when the two waves of a SIMD (w and
+// w + waves / 2, one program) run it at once behind the pair's barrier.  The
+// first half of the block's waves runs it there, before the pair's column
+// tiles; their SIMD partners run `stagger` column tiles first, so each wave's
+// scalar work lies under its partner's MFMAs.  Returns the column tiles of
+// the pair the wave multiplies before its look-ahead.  Every wave still runs
+// it between the pair's barrier and the next one, so what the kernel's
+// protocols need holds as before: the stage goes to the buffer every wave left
+// before this barrier and has landed before the next, and a claim is read
+// behind the barrier that follows its write and before the one that precedes
+// the next write to its word (tests/test_gram_pipe_schedule.py walks this).
+DAL_HD constexpr int lookahead_tiles(int wave, int waves, int stagger) { return wave < waves / 2 ? 0 : stagger; }
 
 // ---------------------------------------------------------------------------
 // Host side: pair counts and the launch's grid and column chunks.

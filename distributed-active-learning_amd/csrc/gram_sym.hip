@@ -74,6 +74,20 @@
 // pair and feeds 512 MFMAs per wave; a B fragment read feeds 16.  Against two
 // super blocks per block (rounds 4-10) the staged bytes, B reads, barriers
 // and DMA issue per MFMA halve.
+//
+// The pair boundary (round 12).  Stamped on that form (scripts/patches/
+// stamp_gram_pair.patch), the matrix pipe stood empty for 2,900 of a pair's
+// 19,300 cycles, all of it between the last MFMA of a pair and the first of
+// the next and none inside a pair: 1,264 cycles to the barrier's release (the
+// fold) and 1,300 to 2,900 behind it, the block's look-ahead -- the claim,
+// peek() and the next stage's DMA issue, ~165 scalar instructions (with three
+// turns of peek()'s column search ~350) run by all eight waves at once.  Two
+// changes: GramSchedule::first_r finds the next taken column block in closed
+// form away from the diagonal, and the look-ahead of waves 4-7 sits behind
+// their first DAL_GRAM_STAGGER column tiles instead of behind the barrier
+// (lookahead_tiles() in gram_schedule.hpp), so that each wave of a SIMD runs
+// its scalar work under its partner's MFMAs.  The schedule, every chain and
+// every fold are what they were: the bits do not change.
 #include <stdlib.h>
 
 #include <mutex>
@@ -136,6 +150,9 @@ __device__ __forceinline__ unsigned fresh_lane() {
 #endif
 #ifndef DAL_GRAM_STAGE8
 #define DAL_GRAM_STAGE8 32768  // bytes per LDS stage of the 8-wave kernel (65536: 2M x 256 1149.6 -> 1378.3 ms)
+#endif
+#ifndef DAL_GRAM_STAGGER
+#define DAL_GRAM_STAGGER 4  // wide form: column tiles waves 4-7 run before their look-ahead (waves 0-3: none); 0: every wave behind the barrier
 #endif
 #ifndef DAL_GRAM_CHAIN_MAX
 #define DAL_GRAM_CHAIN_MAX 2048  // the longest row chain dal_density_error_bound_sym_d charges
@@ -340,14 +357,17 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W, HVS>::OCC)) void gram_csym_kern
   // one stage of SC columns; fresh = first stage of a fold group (the chains
   // restart).  B fragments go through two register sets: k-step i+1's are
   // read while k-step i's 16 MFMAs issue.
-  auto compute = [&](int buf, bool fresh_stage) {
-    f16x8 bh[2];
+  // (ct0, ct1: the stage's column tiles of this call -- the wide form runs a
+  // stage in two calls, see the pair loop; the last fragment read by the first
+  // waits in bh for the second)
+  f16x8 bh[2];
+  auto compute = [&](int buf, bool fresh_stage, int ct0 = 0, int ct1 = C::NCT) {
     auto load_b = [&](int set, int c, int ct) {
       bh[set] = __builtin_bit_cast(f16x8, lds[buf * C::F4 + ct * 16 * C::SLOTS + b_off(c)]);
     };
-    load_b(0, 0, 0);
+    if (ct0 == 0) load_b(0, 0, 0);
 #pragma unroll
-    for (int ct = 0; ct < C::NCT; ++ct) {
+    for (int ct = ct0; ct < ct1; ++ct) {
       __builtin_amdgcn_sched_barrier(0);
       const bool fresh = fresh_stage && ct == 0;
 #pragma unroll
@@ -493,6 +513,41 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W, HVS>::OCC)) void gram_csym_kern
 #pragma unroll
     for (int s = 0; s < C::SPP; ++s) {
       stage_sync();
+      if constexpr (C::WIDE && DAL_GRAM_STAGGER > 0) {
+        // The wide form's look-ahead (the claim, peek() and the next stage's
+        // DMA issue: ~165 scalar instructions, ~1,300 cycles when both waves
+        // of a SIMD run them at once behind the barrier with the matrix pipe
+        // empty -- stamped, round 12) sits at two places of the pair: waves
+        // 0-3 run it behind the barrier, their SIMD partners 4-7 behind their
+        // first DAL_GRAM_STAGGER column tiles, so each runs under the other's
+        // MFMAs.  Nothing of it is read by the pair's own MFMAs; the DMA goes
+        // to the buffer every wave left before the barrier, the claim word
+        // read here is next written two claims on, and the rare barriers in
+        // claim_take() are the same in number for every wave.  The flush needs
+        // only the unit noted at the last change of rows and stays behind the
+        // barrier in every wave.
+        if (flushRU >= 0) {
+          flush_rows(flushRU);
+          flushRU = -1;
+        }
+        auto look_ahead = [&]() {
+          if (cur.new_unit) claim_take();
+          cur.peek();
+          if (cur.has_next) issue(buf ^ 1, cur.next_J, 0, cur.next_slice());
+        };
+        const bool lead = lookahead_tiles(wave, W, DAL_GRAM_STAGGER) == 0;  // (gram_schedule.hpp)
+        if (!act) {
+          look_ahead();
+        } else {
+          if (lead) look_ahead();
+          compute(buf, true, 0, DAL_GRAM_STAGGER);
+          if (!lead) look_ahead();
+          compute(buf, true, DAL_GRAM_STAGGER, C::NCT);
+          fold_rows();
+        }
+        buf ^= 1;
+        continue;
+      }
       if (s == 0) {
         if (cur.new_unit) claim_take();
         cur.peek();
