@@ -90,6 +90,20 @@ __device__ __forceinline__ double row_sq_norm_bf16(const uint16_t* __restrict__ 
   return s;
 }
 
+// One global_load_lds_dwordx4 (LDS-DMA): lane l's 16 B at src + voff land at
+// LDS byte lds_dst + 16 l, no VGPR in between.  src and lds_dst are
+// wave-uniform; lds_dst travels in M0, which is put back (the compiler does
+// not know the instruction reads it).  Completion: vmcnt.
+__device__ __forceinline__ void lds_dma_x4(unsigned voff, unsigned lds_dst, const void* src) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(lds_dst), "s"(src)
+      : "memory");
+}
+
 // Row-group minima of the optimistic keys carry a row hint in their low
 // kHintBits bits: (key & ~kHintMask) | (row offset in the group), so the
 // select kernel can prefetch each group's best row before tau is known (its

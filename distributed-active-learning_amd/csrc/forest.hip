@@ -21,7 +21,10 @@
 // flight (ILP over trees).  Votes are integers; the score comes from an fp64
 // look-up table indexed by v, so US scores are exact fp64 and identical to the
 // reference's Python float arithmetic.
-#include "common.hpp"
+//
+// The pieces the multiclass kernels use too (forest_multi.hip,
+// forest_multi_blocked.hip) are defined once, in forest_shared.hpp.
+#include "forest_shared.hpp"
 
 namespace dal {
 namespace {
@@ -62,20 +65,10 @@ struct ForestArgs {
 };
 
 
-// beta != 1 calls out of line: inlined, pow's registers counted against every
-// score kernel's occupancy although beta == 1 in the common case, where no
-// call is made (the blocked kernel 101 -> 74 VGPRs, 4 -> 6 waves per SIMD).
-__device__ __attribute__((noinline)) double density_pow_general(double d, double beta) { return pow(d, beta); }
+// density^beta and its error bound (forest_shared.hpp), beta tested at run
+// time: beta != 1 calls out of line, beta == 1 makes no call.
 __device__ __forceinline__ double density_pow(double d, double beta) {
   return beta == 1.0 ? d : density_pow_general(d, beta);
-}
-
-// |d^beta - d'^beta| bound for |d - d'| <= derr.
-__device__ __attribute__((noinline)) double density_pow_err_general(double d, double derr, double beta) {
-  const double p = pow(fabs(d), beta);
-  const double hi = pow(fabs(d) + derr, beta);
-  const double lo = pow(fmax(fabs(d) - derr, 0.0), beta);
-  return fmax(fabs(hi - p), fabs(p - lo)) * (1.0 + 1e-12) + fabs(p) * 1e-14;
 }
 __device__ __forceinline__ double density_pow_err(double d, double derr, double beta) {
   return beta == 1.0 ? derr : density_pow_err_general(d, derr, beta);
@@ -158,58 +151,9 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
 // WROWS (the blocked feature-major path): wave w holds rows (w / tpr) * 64 +
 // lane and walks trees w % tpr, + tpr, ...; the waves' partial votes of a row
 // are summed through LDS.
-// Byte-addressed walks of M trees (t, t + tpr, ...) at once for one row
-// (score_tile BYTEA): node h of tree t sits at LDS byte tb + 8 h, so its
-// child 2h + 1 (x <= thr) or 2h + 2 sits at 2a + (8 - tb) or 2a + (16 - tb)
-// -- a select and a shift-add per level; the leaf byte at (a >> 3) + lbase +
-// t * n_leaf - n_inner - tb / 8.  Returns the M trees' summed votes.
-struct ByteWalk {
-  unsigned fbase, lbase, xb;  // LDS byte addresses: nodes, leaves, this row's x
-  int tpr, n_inner, n_leaf, depth;
-};
-template <int M>
-__device__ __forceinline__ int walk_group(const ByteWalk& W, int t) {
-  typedef __attribute__((address_space(3))) const float lds_float;
-  typedef __attribute__((address_space(3))) const uint8_t lds_u8;
-  typedef __attribute__((address_space(3))) const unsigned long long lds_u64;
-  unsigned a[M], kl[M], kr[M], lo[M];
-#pragma unroll
-  for (int j = 0; j < M; ++j) {
-    const int tj = t + j * W.tpr;
-    const unsigned tb = W.fbase + static_cast<unsigned>(8 * tj * W.n_inner);
-    a[j] = tb;
-    kl[j] = 8u - tb;
-    kr[j] = 16u - tb;
-    lo[j] = W.lbase + static_cast<unsigned>(tj * W.n_leaf - W.n_inner) - (tb >> 3);
-    // opaque to the optimiser and held in vector registers, so the step stays
-    // select + shift-add instead of shift, subtract, select, add
-    asm volatile("" : "+v"(kl[j]), "+v"(kr[j]));
-  }
-  for (int lvl = 0; lvl < W.depth; ++lvl) {
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-      const unsigned long long nd = *(lds_u64*)static_cast<uintptr_t>(a[j]);  // {feature run offset, thr}
-      const float xv = *(lds_float*)static_cast<uintptr_t>(W.xb + static_cast<unsigned>(nd));
-      a[j] = 2u * a[j] + (xv <= __uint_as_float(static_cast<unsigned>(nd >> 32)) ? kl[j] : kr[j]);
-    }
-  }
-  int v = 0;
-#pragma unroll
-  for (int j = 0; j < M; ++j) v += *(lds_u8*)static_cast<uintptr_t>((a[j] >> 3) + lo[j]);
-  return v;
-}
-// the last rem (< ILP) trees of a wave as one group (rem wave-uniform)
-template <int M>
-__device__ __forceinline__ int walk_tail(const ByteWalk& W, int t, int rem) {
-  if constexpr (M == 0) {
-    return 0;
-  } else {
-    return rem == M ? walk_group<M>(W, t) : walk_tail<M - 1>(W, t, rem);
-  }
-}
-
 // BYTEA (the prepared blocked path: LDS nodes whose feature is the BYTE
-// offset slot * 256 of its run): walk_group -- 4 VALU per node visit (x
+// offset slot * 256 of its run): the byte-addressed walks of
+// forest_shared.hpp, the leaf bytes summed -- 4 VALU per node visit (x
 // address, compare, select, shift-add) against 5, the tree index
 // wave-uniform (scalar), and a wave's last trees walked together.
 template <bool X_LDS, bool WROWS = false, int NW = kForestWaves, int ILP = kTreeIlp, bool BYTEA = false>
@@ -245,7 +189,11 @@ __device__ __forceinline__ void score_tile(const ForestArgs& A, const float* xs,
       // count (T = 10 over 4 waves: 3 or 2 walks in flight, not one at a time)
       for (int t = __builtin_amdgcn_readfirstlane(sub); t < A.n_trees; t += ILP * tpr) {  // (wave-uniform)
         const int rem = (A.n_trees - t + tpr - 1) / tpr;
-        v += rem >= ILP ? walk_group<ILP>(W, t) : walk_tail<ILP - 1>(W, t, rem);
+        int g = 0;  // the group's leaf bytes, summed
+        auto sum = [&](unsigned c) { g += static_cast<int>(c); };
+        if (rem >= ILP) walk_group<ILP>(W, t, sum);
+        else walk_tail<ILP - 1>(W, t, rem, sum);
+        v += g;
       }
     }
   } else if (live) {
@@ -431,15 +379,7 @@ __global__ __launch_bounds__(kForestThreads) void forest_score_kernel(ForestArgs
             const unsigned dst = __builtin_amdgcn_readfirstlane(
                 static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_float*)(xs + rr * xstride + p * 256))));
             const unsigned voff = static_cast<unsigned>(p * 1024 + lane * 16);
-            if (static_cast<int>(voff) < row_bytes) {
-              unsigned keep;
-              asm volatile(
-                  "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                  "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                  : "=&s"(keep)
-                  : "v"(voff), "s"(dst), "s"(src)
-                  : "memory");
-            }
+            if (static_cast<int>(voff) < row_bytes) lds_dma_x4(voff, dst, src);
           }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -497,8 +437,8 @@ __global__ __launch_bounds__(kForestThreads) void forest_score_kernel(ForestArgs
 // dal_pool_blocked: the pool as tiles of kBlk rows, feature-major inside a
 // tile: xb[(tile * d + f) * kBlk + r] = x[tile * kBlk + r][f] (rows past n are
 // zero).  A tile's feature f is one contiguous 256-B run, so a kernel that
-// needs only some features of a tile reads only those runs.
-constexpr int kBlk = 64;
+// needs only some features of a tile reads only those runs.  (kBlk = 64:
+// forest_shared.hpp.)
 
 __global__ __launch_bounds__(256) void pool_blocked_kernel(const float* __restrict__ x, int64_t n, int d,
                                                            int64_t ldx, float* __restrict__ xb) {
@@ -533,26 +473,9 @@ __global__ __launch_bounds__(256) void pool_blocked_kernel(const float* __restri
 // 4 d for the row-major tile (config 4, T = 10: ~113 of 256 features).
 // PREP (ABI v10): the forest was prepared once per (forest, d) by
 // dal_forest_prepare -- feature list, remapped nodes and leaves in the LDS
-// layout below -- and every block copies that blob instead of building it
-// (the per-block bitmap, popcounts and remap are gone).
-
-// The prepared forest (dal_forest_prepare): a 16-B header {fu, bad, nn,
-// fu_max} then the payload [nodes int2 nn (feature -> byte offset slot * kBlk * 4 of its
-// run in the LDS tile) | leaves u8
-// round4(T * 2^depth) | feature list u16 round2(fu_max)], zero-padded to 16 B:
-// the blocked kernel's LDS layout from its forest region on.
-struct BlockedPrepLayout {
-  int64_t nodes, leaves, used, payload, total;
-};
-__host__ __device__ inline BlockedPrepLayout blocked_prep_layout(int64_t n_trees, int32_t depth, int64_t fu_max) {
-  BlockedPrepLayout L;
-  L.nodes = n_trees * ((int64_t{1} << depth) - 1) * 8;
-  L.leaves = round_up(n_trees << depth, 4);
-  L.used = round_up(fu_max, 2) * 2;
-  L.payload = round_up(L.nodes + L.leaves + L.used, 16);
-  L.total = 16 + L.payload;
-  return L;
-}
+// layout of forest_shared.hpp's blocked_prep_layout -- and every block copies
+// that blob instead of building it (the per-block bitmap, popcounts and remap
+// are gone).
 
 // The prepared forest's tree walks by LDS byte address (score_tile BYTEA; 1)
 // or by heap index like the unprepared kernel (0).  The prepared node format
@@ -666,8 +589,7 @@ __global__ __launch_bounds__(NW * 64) void forest_blocked_kernel(ForestArgs A, c
   fu = pre[nw - 1] + __popc(bits[nw - 1]);  // <= fu_max
   __syncthreads();
   }
-  const int n_ins = (fu + 3) >> 2;  // DMA instructions per tile (4 runs each)
-  typedef __attribute__((address_space(3))) float lds_float;
+  const int n_ins = blocked_dma_count(fu);  // DMA instructions per tile (4 runs each)
   GroupFold fold;
   __shared__ unsigned long long wmin[2][2][NW];
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {  // block-uniform
@@ -680,21 +602,7 @@ __global__ __launch_bounds__(NW * 64) void forest_blocked_kernel(ForestArgs A, c
       if (A.dkind) dens_pre = static_cast<const long long*>(A.density)[row];
     }
     const char* src = reinterpret_cast<const char*>(xb + tile * A.d * kBlk);
-    for (int i = wave; i < n_ins; i += NW) {
-      const int sl = 4 * i + (lane >> 4);
-      const unsigned dst = __builtin_amdgcn_readfirstlane(
-          static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_float*)(xs + 4 * i * kBlk))));
-      if (sl < fu) {
-        const unsigned voff = static_cast<unsigned>(used[sl]) * (kBlk * 4u) + static_cast<unsigned>(lane & 15) * 16u;
-        unsigned keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(voff), "s"(dst), "s"(src)
-            : "memory");
-      }
-    }
+    for (int i = wave; i < n_ins; i += NW) stage_blocked_runs(xs, src, used, fu, i, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) issue_fold<NW>(A, fold, wmin);  // after this tile's DMA wait
@@ -811,48 +719,12 @@ int blocked_fu_max(int64_t d, int32_t n_trees, int32_t depth) {
   return blocked_smem(static_cast<int>(fu), d, n_trees, depth) <= 96 * 1024 ? static_cast<int>(fu) : 0;
 }
 
-struct ForestTiling {
-  int R;        // rows per block
-  bool x_lds;   // pool rows staged in LDS
-  bool dma;     // ... by LDS-DMA (wide rows)
-};
-
-ForestTiling forest_tiling(const float* x, int64_t d, int64_t ldx, int32_t n_trees) {
-  // rows per block: stage up to ~16 KiB of pool rows in LDS.  Small tiles keep
-  // more blocks (and their loads) resident per CU: at 2M x 256 a 16 KiB tile
-  // runs 0.52 ms vs 0.60 (32 KiB) / 0.85 (96 KiB) / 0.75 (8 KiB); neutral at
-  // 100k x 64 and 284,807 x 30
-  ForestTiling T{256, true, false};
-  // LDS-DMA staging for wide rows (d % 4 == 0, ldx % 4 == 0, 16-B-aligned
-  // pool; narrow rows leave most lanes of each DMA instruction idle: 2M x 32 x
-  // 100: 264 -> 290 us, 100k x 64: 18.4 -> 19.8) holds no registers: 32 KiB
-  // tiles there (2M x 256: 441 -> 411 us; 64 KiB 1248)
-  T.dma = d >= 128 && d % 4 == 0 && ldx % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0;
-  const int64_t tile_cap = T.dma ? 33280 : 16640 * (kForestThreads / 256);
-  while (T.R > 16 && static_cast<int64_t>(T.R) * (d + 1) * 4 > tile_cap) T.R >>= 1;
-  // wide rows: 16 rows may exceed the preferred tile; LDS staging up to 64 KiB
-  if (static_cast<int64_t>(T.R) * (d + 1) * 4 > 65536) {
-    T.x_lds = false;
-    T.dma = false;
-    T.R = 256;
-  }
-  // many trees (config 3: T = 100): spread a row's trees over more lanes --
-  // the traversal's dependent LDS round trips, not HBM, bound that case
-#ifndef DAL_FOREST_TPR
-#define DAL_FOREST_TPR 2
-#endif
-  const int tpr_min = n_trees >= 64 ? DAL_FOREST_TPR : 1;  // config 3: 60.7 -> 51.8 us (4: 53.5, 8: 60.9)
-  if (T.x_lds) {
-    while (T.R > 1 && kForestThreads / T.R < tpr_min) T.R >>= 1;
-  }
-  return T;
-}
 }  // namespace
 
 int forest_rows_per_block(const float* x, const float* xb, int64_t d, int64_t ldx, int32_t n_trees,
                           int32_t depth) {
   if (xb && blocked_fu_max(d, n_trees, depth)) return kBlk;
-  return forest_tiling(x, d, ldx, n_trees).R;
+  return forest_tiling(x, d, ldx, n_trees, kForestThreads).R;
 }
 
 int forest_score_launch(const float* x, const float* xb, const void* fprep, int64_t n, int64_t d, int64_t ldx,
@@ -888,19 +760,12 @@ int forest_score_launch(const float* x, const float* xb, const void* fprep, int6
                                 : reinterpret_cast<const void*>(forest_blocked_kernel<kBlockedWavesWide, false>))
                           : (pr ? reinterpret_cast<const void*>(forest_blocked_kernel<kBlockedWaves, true>)
                                 : reinterpret_cast<const void*>(forest_blocked_kernel<kBlockedWaves, false>));
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1 ||
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nw * 64, smem) != hipSuccess)
-      return DAL_ERR_HIP;
     // at most DAL_FOREST_BLOCKED_PER_CU blocks per CU: every block stages the
     // forest once, so more, shorter-lived blocks pay that setup more often
     // (config 3 at 6 blocks per CU 37.0 us, at 5 35.5, at 4 -- the VGPR limit
     // before pow went out of line -- 37.8)
-    if (per_cu > DAL_FOREST_BLOCKED_PER_CU) per_cu = DAL_FOREST_BLOCKED_PER_CU;
-    if (per_cu < 1) per_cu = 1;
-    const int64_t grid = tiles < static_cast<int64_t>(cus) * per_cu ? tiles : static_cast<int64_t>(cus) * per_cu;
+    const int64_t grid = persistent_grid(fn, nw * 64, smem, DAL_FOREST_BLOCKED_PER_CU, tiles);
+    if (grid < 0) return static_cast<int>(grid);
     const unsigned char* pb = static_cast<const unsigned char*>(fprep);
 #define DAL_BLOCKED_LAUNCH(W, P)                                                                          \
   hipLaunchKernelGGL((forest_blocked_kernel<W, P>), dim3(static_cast<unsigned>(grid)), dim3(nw * 64), smem, st, A, \
@@ -913,7 +778,7 @@ int forest_score_launch(const float* x, const float* xb, const void* fprep, int6
     DAL_RETURN_IF_LAUNCH_FAILED();
     return DAL_OK;
   }
-  const ForestTiling T = forest_tiling(x, d, ldx, n_trees);
+  const ForestTiling T = forest_tiling(x, d, ldx, n_trees, kForestThreads);
   const int R = T.R, tpr = kForestThreads / R;
   const int64_t blocks = ceil_div(n, R);
   if (hooks_in.gmin &&
@@ -935,23 +800,15 @@ int forest_score_launch(const float* x, const float* xb, const void* fprep, int6
   const int xf = static_cast<int>(round_up(x_floats, 4));  // forest region 16-B aligned
   size_t smem = static_cast<size_t>(xf) * 4 + (f_lds ? static_cast<size_t>(f_bytes) : 0);
   if (smem == 0) smem = 16;
-  // LDS-DMA tiles: a persistent grid of exactly the blocks resident at once
-  // (registers, LDS, waves: the occupancy query -- a grid past it would start
-  // its extra blocks only when others END) (2M x 256: 430 -> 404 us at
-  // T = 10, 677 -> 486 us at T = 100: the forest is copied once per block,
-  // not once per 32-row tile)
+  // LDS-DMA tiles: a persistent grid of the blocks resident at once (2M x
+  // 256: 430 -> 404 us at T = 10, 677 -> 486 us at T = 100: the forest is
+  // copied once per block, not once per 32-row tile)
   int64_t persist_grid = 0;
   if (T.dma) {
-    int dev = 0, cus = 0, per_cu = 0;
     const void* fn = f_lds ? reinterpret_cast<const void*>(forest_score_kernel<true, true, true>)
                            : reinterpret_cast<const void*>(forest_score_kernel<true, false, true>);
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1 ||
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kForestThreads, smem) != hipSuccess)
-      return DAL_ERR_HIP;
-    if (per_cu < 1) per_cu = 1;
-    persist_grid = blocks < static_cast<int64_t>(cus) * per_cu ? blocks : static_cast<int64_t>(cus) * per_cu;
+    persist_grid = persistent_grid(fn, kForestThreads, smem, 0, blocks);
+    if (persist_grid < 0) return static_cast<int>(persist_grid);
   }
 #define DAL_FOREST_LAUNCH(XL, FL, PS, G)                                                                  \
   do {                                                                                                    \

@@ -22,8 +22,11 @@
 // parameter, every word index a compile-time constant so the words stay in
 // registers).  T <= 255, so no field carries, in a thread or after the
 // cross-lane sum of a row's tpr partial words (plain 32-bit adds).  The
-// staging code is a copy of forest.hip's, not shared: the binary kernels'
-// code generation does not move.
+// tiling rule, the grid sizing, the counters and the row epilogue are the one
+// definition of forest_shared.hpp, which the binary kernels and the blocked
+// multiclass kernels use too; the staging loops are this kernel's own (the
+// forms of forest.hip's: inside a shared helper they compiled the binary
+// kernels, which are held to the instructions they had, to other code).
 //
 // The density-weighted form (template parameter DW; dal_forest_score_
 // multiclass_dw) is the C-class reading of density_weighting.py:148-167's e*d
@@ -38,9 +41,7 @@
 // feature-major copy and the prepared forest is forest_multi_blocked.hip
 // (dal_forest_score_multiclass_blocked / _dw_blocked; same outputs, bit for
 // bit), which also falls back to the entries below.
-#include <type_traits>
-
-#include "common.hpp"
+#include "forest_shared.hpp"
 
 namespace dal {
 namespace {
@@ -83,52 +84,11 @@ struct McDwArgs : McArgs {
   uint64_t* keys_hi;  // nullable
 };
 
-// Copies of forest.hip's helpers (not shared: the binary kernels' code
-// generation does not move).  pow stays out of line, and the launcher picks
-// the kernel by beta: the beta == 1 kernels (POW false) hold no call at all --
-// a call that is never taken still cost them 1 % (config 4, T = 10) to 3 %
-// (T = 100) and 8 bytes of scratch per lane.
-__device__ __attribute__((noinline)) double mc_density_pow_general(double d, double beta) { return pow(d, beta); }
-template <bool POW>
-__device__ __forceinline__ double mc_density_pow(double d, double beta) {
-  if constexpr (POW) return mc_density_pow_general(d, beta);
-  return d;
-}
-
-// |d^beta - d'^beta| bound for |d - d'| <= derr.
-__device__ __attribute__((noinline)) double mc_density_pow_err_general(double d, double derr, double beta) {
-  const double p = pow(fabs(d), beta);
-  const double hi = pow(fabs(d) + derr, beta);
-  const double lo = pow(fmax(fabs(d) - derr, 0.0), beta);
-  return fmax(fabs(hi - p), fabs(p - lo)) * (1.0 + 1e-12) + fabs(p) * 1e-14;
-}
-template <bool POW>
-__device__ __forceinline__ double mc_density_pow_err(double d, double derr, double beta) {
-  if constexpr (POW) return mc_density_pow_err_general(d, derr, beta);
-  return derr;
-}
-
-// One vote for class c: 1 << 8 (c & 3) added to word c >> 2.  The loop is
-// unrolled over the CW words (a runtime-indexed register array would live in
-// scratch); a class >= 4 CW matches no word and is dropped.  (A bit extract
-// from a one-hot word mask and a shift-add per word, 2 VALU instead of 3,
-// measured the same: config 3 56.3 -> 56.5 us.)
-template <int CW>
-__device__ __forceinline__ void add_vote(unsigned (&w)[CW], unsigned c) {
-  const unsigned inc = 1u << (8u * (c & 3u));
-  const unsigned word = c >> 2;
-#pragma unroll
-  for (int j = 0; j < CW; ++j) w[j] += word == static_cast<unsigned>(j) ? inc : 0u;
-}
-
-template <int CW>
-__device__ __forceinline__ int vote_field(const unsigned (&w)[CW], int c) {  // c: a compile-time constant at every call
-  return static_cast<int>((w[c >> 2] >> (8 * (c & 3))) & 255u);
-}
-
 // Counts, prediction, score and key of tile `tile` (R rows from LDS or global
-// memory).  fl_pre: the row leader's flags, loaded with the tile; DW: dens_pre,
-// its density word, loaded with them.
+// memory): the walks, the cross-lane sum, then the row leader's epilogue
+// (forest_shared.hpp).  fl_pre: the row leader's flags, loaded with the tile;
+// DW: dens_pre, its density word, loaded with them.  The launcher picks POW by
+// beta: the beta == 1 kernels hold no pow call at all.
 template <int CW, bool X_LDS, bool DW, bool POW, class Args>
 __device__ __forceinline__ void score_tile_multi(const Args& A, const float* xs, int xstride, int64_t tile, int R,
                                                  int tpr, const int2* inner, const uint8_t* leaf, uint8_t fl_pre,
@@ -181,78 +141,7 @@ __device__ __forceinline__ void score_tile_multi(const Args& A, const float* xs,
     for (int j = 0; j < CW; ++j) w[j] += __shfl_xor(w[j], o);
   }
   if (!(live && sub == 0)) return;
-  const int C = A.n_classes;
-  // largest and second-largest count, the lowest class holding the largest
-  int m1 = -1, m2 = -1, arg = 0;
-#pragma unroll
-  for (int c = 0; c < 4 * CW; ++c) {
-    if (c < C) {
-      const int nc = vote_field<CW>(w, c);
-      if (nc > m1) {
-        m2 = m1;
-        m1 = nc;
-        arg = c;
-      } else if (nc > m2) {
-        m2 = nc;
-      }
-    }
-  }
-  double s;
-  if (DW || A.kind == DAL_MC_ENTROPY) {
-    s = 0.0;
-#pragma unroll
-    for (int c = 0; c < 4 * CW; ++c)
-      if (c < C) s = __dadd_rn(s, lut_s[vote_field<CW>(w, c)]);  // class order, one rounding per add
-  } else {
-    s = lut_s[A.kind == DAL_MC_MARGIN ? m1 - m2 : m1];
-  }
-  if (A.counts) {
-    // the packed words are the row's count bytes in memory order (little
-    // endian): whole words or halves where C and the buffer's alignment allow
-    uint8_t* cr = A.counts + row * C;
-    if (A.cstore == 4) {
-#pragma unroll
-      for (int j = 0; j < CW; ++j)
-        if (4 * j < C) reinterpret_cast<uint32_t*>(cr)[j] = w[j];
-    } else if (A.cstore == 2) {
-#pragma unroll
-      for (int hw = 0; hw < 2 * CW; ++hw)
-        if (2 * hw < C) reinterpret_cast<uint16_t*>(cr)[hw] = static_cast<uint16_t>(w[hw >> 1] >> (16 * (hw & 1)));
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4 * CW; ++c)
-        if (c < C) cr[c] = static_cast<uint8_t>(vote_field<CW>(w, c));
-    }
-  }
-  if (A.pred) A.pred[row] = static_cast<uint8_t>(arg);
-  if constexpr (DW) {
-    // the binary kernel's density epilogue (forest.hip) on the class entropy
-    // e (never NaN, >= +0.0): s = e d^beta, descending, and for the GEMM
-    // density the interval s -+ e err(d^beta) as two keys
-    const double e = s;
-    double d = A.dkind == DAL_DENSITY_FIXED ? from_fixed(dens_pre) : __builtin_bit_cast(double, dens_pre);
-    if (fl_pre & DAL_ROW_EXCLUDED) d = __builtin_nan("");
-    s = e * mc_density_pow<POW>(d, A.beta);
-    double err = 0.0;
-    if (A.dkind == DAL_DENSITY_FIXED && e != 0.0 && d == d) {
-      err = e * mc_density_pow_err<POW>(d, A.derr, A.beta);
-      // keep the interval ends distinct from s after rounding
-      err = fmax(err, fabs(s) * 4.5e-16);
-    }
-    unsigned long long klo = DAL_KEY_NONE, khi = DAL_KEY_NONE;
-    if (fl_pre & DAL_ROW_CANDIDATE) {
-      klo = score_key(pessimistic(s, err, DAL_DESCENDING), DAL_DESCENDING);
-      khi = score_key(optimistic(s, err, DAL_DESCENDING), DAL_DESCENDING);
-    }
-    A.entropy[row] = e;
-    A.row_index[row] = static_cast<int32_t>(row);  // (n <= INT32_MAX, checked by the entry)
-    A.scores[row] = s;
-    A.keys[row] = klo;
-    if (A.keys_hi) A.keys_hi[row] = khi;
-  } else {
-    A.scores[row] = s;
-    A.keys[row] = (fl_pre & DAL_ROW_CANDIDATE) ? score_key(s, A.order) : DAL_KEY_NONE;
-  }
+  row_epilogue<CW, DW, POW>(A, w, row, fl_pre, dens_pre, lut_s);
 }
 
 // One block per tile (grid = tiles), or PERSIST (LDS-DMA staging only; grid =
@@ -317,15 +206,7 @@ __global__ __launch_bounds__(kMcThreads) void forest_multi_kernel(std::condition
             const unsigned dst = __builtin_amdgcn_readfirstlane(
                 static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_float*)(xs + rr * xstride + p * 256))));
             const unsigned voff = static_cast<unsigned>(p * 1024 + lane * 16);
-            if (static_cast<int>(voff) < row_bytes) {
-              unsigned keep;
-              asm volatile(
-                  "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                  "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                  : "=&s"(keep)
-                  : "v"(voff), "s"(dst), "s"(src)
-                  : "memory");
-            }
+            if (static_cast<int>(voff) < row_bytes) lds_dma_x4(voff, dst, src);
           }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -367,35 +248,10 @@ __global__ __launch_bounds__(kMcThreads) void forest_multi_kernel(std::condition
   }
 }
 
-struct McTiling {
-  int R;       // rows per block
-  bool x_lds;  // pool rows staged in LDS
-  bool dma;    // ... by LDS-DMA (wide rows)
-};
-
-// The binary launcher's tiling rule (forest.hip, forest_tiling; the figures
-// behind its thresholds are there): ~16 KiB tiles, 32 KiB with LDS-DMA
-// (d >= 128, 16-B aligned rows), rows from global memory when 16 of them pass
-// 64 KiB, and at least two lanes per row from 64 trees on.
-McTiling multi_tiling(const float* x, int64_t d, int64_t ldx, int32_t n_trees) {
-  McTiling T{256, true, false};
-  T.dma = d >= 128 && d % 4 == 0 && ldx % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0;
-  const int64_t tile_cap = T.dma ? 33280 : 16640;
-  while (T.R > 16 && static_cast<int64_t>(T.R) * (d + 1) * 4 > tile_cap) T.R >>= 1;
-  if (static_cast<int64_t>(T.R) * (d + 1) * 4 > 65536) {
-    T.x_lds = false;
-    T.dma = false;
-    T.R = 256;
-  }
-  const int tpr_min = n_trees >= 64 ? 2 : 1;
-  if (T.x_lds) {
-    while (T.R > 1 && kMcThreads / T.R < tpr_min) T.R >>= 1;
-  }
-  return T;
-}
-
+// The binary launcher's tiling rule (forest_shared.hpp, forest_tiling).
 template <int CW, bool DW, bool POW, class Args>
-int multi_launch(const Args& A, const McTiling& T, int64_t d, int64_t ldx, hipStream_t st) {
+int multi_launch(const Args& A, int64_t d, int64_t ldx, hipStream_t st) {
+  const ForestTiling T = forest_tiling(A.x, d, ldx, A.n_trees, kMcThreads);
   const int R = T.R, tpr = kMcThreads / R;
   const int64_t blocks = ceil_div(A.n, R);
   const bool vec4 = (d % 4 == 0) && (ldx % 4 == 0) && (reinterpret_cast<uintptr_t>(A.x) % 16 == 0);
@@ -409,18 +265,13 @@ int multi_launch(const Args& A, const McTiling& T, int64_t d, int64_t ldx, hipSt
 #define DAL_MC_LAUNCH(XL, FL, PS)                                                                          \
   do {                                                                                                     \
     const void* fn = reinterpret_cast<const void*>(forest_multi_kernel<CW, XL, FL, PS, DW, POW>);          \
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) !=     \
-        hipSuccess)                                                                                        \
-      return DAL_ERR_HIP;                                                                                  \
     int64_t grid = blocks;                                                                                 \
     if (PS) { /* a persistent grid of exactly the blocks resident at once */                               \
-      int dev = 0, cus = 0, per_cu = 0;                                                                    \
-      if (hipGetDevice(&dev) != hipSuccess ||                                                              \
-          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||         \
-          cus < 1 || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kMcThreads, smem) != hipSuccess) \
-        return DAL_ERR_HIP;                                                                                \
-      if (per_cu < 1) per_cu = 1;                                                                          \
-      if (grid > static_cast<int64_t>(cus) * per_cu) grid = static_cast<int64_t>(cus) * per_cu;            \
+      grid = persistent_grid(fn, kMcThreads, smem, 0, blocks);                                             \
+      if (grid < 0) return static_cast<int>(grid);                                                         \
+    } else if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,                         \
+                                   static_cast<int>(smem)) != hipSuccess) {                                \
+      return DAL_ERR_HIP;                                                                                  \
     }                                                                                                      \
     hipLaunchKernelGGL((forest_multi_kernel<CW, XL, FL, PS, DW, POW>), dim3(static_cast<unsigned>(grid)),  \
                        dim3(kMcThreads), smem, st, A, R, tpr, xf, vec4, pad4, T.dma, blocks);              \
@@ -448,27 +299,16 @@ extern "C" int dal_forest_score_multiclass(const float* x, int64_t n, int64_t d,
                                            const double* lut, int score_kind, const uint8_t* row_flags, int order,
                                            uint8_t* counts, uint8_t* pred, double* scores, uint64_t* keys,
                                            dal_stream_t stream) {
-  if (!x || !inner || !leaf || !lut || !scores || !keys) return DAL_ERR_ARG;
-  if (order != DAL_ASCENDING && order != DAL_DESCENDING) return DAL_ERR_ARG;
-  if (score_kind != DAL_MC_LEAST_CONFIDENCE && score_kind != DAL_MC_MARGIN && score_kind != DAL_MC_ENTROPY)
-    return DAL_ERR_ARG;
-  if (n < 0 || d < 1 || ldx < d || d > (int64_t{1} << 30)) return DAL_ERR_SHAPE;
-  if (depth < 1 || depth > DAL_MAX_TREE_DEPTH) return DAL_ERR_UNSUPPORTED;
-  if (n_classes < 2 || n_classes > DAL_MC_MAX_CLASSES) return DAL_ERR_UNSUPPORTED;
-  if (n_trees < 1 || n_trees > DAL_MC_MAX_TREES) return DAL_ERR_UNSUPPORTED;
+  const bool args_ok = x && inner && leaf && lut && scores && keys && mc_uncertainty_enums_ok(order, score_kind);
+  if (const int rc = mc_validate(args_ok, n, d, ldx, n_trees, depth, n_classes, false)) return rc;
   if (n == 0) return DAL_OK;
-  const uintptr_t ca = reinterpret_cast<uintptr_t>(counts);
-  const int cstore = (n_classes % 4 == 0 && ca % 4 == 0) ? 4 : (n_classes % 2 == 0 && ca % 2 == 0) ? 2 : 1;
   const McArgs A{x,         n,   static_cast<int>(d), ldx,       reinterpret_cast<const int2*>(inner),
                  leaf,      n_trees, depth,           n_classes, lut,
                  score_kind, row_flags, order,        counts,    pred,
-                 scores,    keys, cstore};
-  const McTiling T = multi_tiling(x, d, ldx, n_trees);
+                 scores,    keys, mc_cstore(counts, n_classes)};
   const hipStream_t st = as_stream(stream);
-  if (n_classes <= 4) return multi_launch<1, false, false>(A, T, d, ldx, st);
-  if (n_classes <= 8) return multi_launch<2, false, false>(A, T, d, ldx, st);
-  if (n_classes <= 16) return multi_launch<4, false, false>(A, T, d, ldx, st);
-  return multi_launch<8, false, false>(A, T, d, ldx, st);
+  return dispatch_cw(n_classes,
+                     [&](auto cw) { return multi_launch<decltype(cw)::value, false, false>(A, d, ldx, st); });
 }
 
 extern "C" int dal_forest_score_multiclass_dw(const float* x, int64_t n, int64_t d, int64_t ldx, const int32_t* inner,
@@ -478,31 +318,19 @@ extern "C" int dal_forest_score_multiclass_dw(const float* x, int64_t n, int64_t
                                               uint8_t* counts, uint8_t* pred, double* entropy, int32_t* row_index,
                                               double* scores, uint64_t* keys, uint64_t* keys_hi,
                                               dal_stream_t stream) {
-  if (!x || !inner || !leaf || !lut || !density || !entropy || !row_index || !scores || !keys) return DAL_ERR_ARG;
-  if (density_kind != DAL_DENSITY_FIXED && density_kind != DAL_DENSITY_EXACT) return DAL_ERR_ARG;
-  if (n < 0 || d < 1 || ldx < d || d > (int64_t{1} << 30)) return DAL_ERR_SHAPE;
-  if (n > INT32_MAX) return DAL_ERR_SHAPE;  // row_index is int32 (dal_dw_select's vote type)
-  if (depth < 1 || depth > DAL_MAX_TREE_DEPTH) return DAL_ERR_UNSUPPORTED;
-  if (n_classes < 2 || n_classes > DAL_MC_MAX_CLASSES) return DAL_ERR_UNSUPPORTED;
-  if (n_trees < 1 || n_trees > DAL_MC_MAX_TREES) return DAL_ERR_UNSUPPORTED;
+  const bool args_ok = x && inner && leaf && lut && density && entropy && row_index && scores && keys &&
+                       (density_kind == DAL_DENSITY_FIXED || density_kind == DAL_DENSITY_EXACT);
+  if (const int rc = mc_validate(args_ok, n, d, ldx, n_trees, depth, n_classes, true)) return rc;
   if (n == 0) return DAL_OK;
-  const uintptr_t ca = reinterpret_cast<uintptr_t>(counts);
-  const int cstore = (n_classes % 4 == 0 && ca % 4 == 0) ? 4 : (n_classes % 2 == 0 && ca % 2 == 0) ? 2 : 1;
   const McDwArgs A{{x,         n,    static_cast<int>(d), ldx,       reinterpret_cast<const int2*>(inner),
                     leaf,      n_trees, depth,            n_classes, lut,
                     DAL_MC_ENTROPY, row_flags, DAL_DESCENDING, counts, pred,
-                    scores,    keys, cstore},
+                    scores,    keys, mc_cstore(counts, n_classes)},
                    density, density_kind, density_err, beta, entropy, row_index, keys_hi};
-  const McTiling T = multi_tiling(x, d, ldx, n_trees);
   const hipStream_t st = as_stream(stream);
-  if (beta == 1.0) {  // no pow, no call
-    if (n_classes <= 4) return multi_launch<1, true, false>(A, T, d, ldx, st);
-    if (n_classes <= 8) return multi_launch<2, true, false>(A, T, d, ldx, st);
-    if (n_classes <= 16) return multi_launch<4, true, false>(A, T, d, ldx, st);
-    return multi_launch<8, true, false>(A, T, d, ldx, st);
-  }
-  if (n_classes <= 4) return multi_launch<1, true, true>(A, T, d, ldx, st);
-  if (n_classes <= 8) return multi_launch<2, true, true>(A, T, d, ldx, st);
-  if (n_classes <= 16) return multi_launch<4, true, true>(A, T, d, ldx, st);
-  return multi_launch<8, true, true>(A, T, d, ldx, st);
+  return dispatch_cw(n_classes, [&](auto cw) {
+    constexpr int CW = decltype(cw)::value;
+    return beta == 1.0 ? multi_launch<CW, true, false>(A, d, ldx, st)  // no pow, no call
+                       : multi_launch<CW, true, true>(A, d, ldx, st);
+  });
 }

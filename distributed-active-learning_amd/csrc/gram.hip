@@ -100,13 +100,7 @@ __global__ __launch_bounds__(kGramThreads, 1) void gram_rowsum_kernel(
     const unsigned voff = static_cast<unsigned>((row * ld + slot * 4) * 4);
     const unsigned dst = __builtin_amdgcn_readfirstlane(
         static_cast<unsigned>(reinterpret_cast<uintptr_t>((AS3 float4*)(lds + buf * kStageF4 + base))));
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(dst), "s"(sbase)
-        : "memory");
+    lds_dma_x4(voff, dst, sbase);
   };
   auto stage_base = [&](int64_t stage) { return ucols + stage * C::SC * ld + ks_off; };
 

@@ -316,13 +316,7 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W, HVS>::OCC)) void gram_csym_kern
       const unsigned dst = dst0 + static_cast<unsigned>(buf * C::STAGE + q * 1024);
       const unsigned voff = (vlane ^ (static_cast<unsigned>(C::swz(q * RPP)) << 4)) +
                             static_cast<unsigned>(q * RPP) * rowbytes;
-      unsigned keep;
-      asm volatile(
-          "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-          "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-          : "=&s"(keep)
-          : "v"(voff), "s"(dst), "s"(sbase)
-          : "memory");
+      lds_dma_x4(voff, dst, sbase);
     }
   };
 

@@ -125,13 +125,7 @@ __global__ __launch_bounds__(256, OCC) void maxcos_kernel(
 #pragma unroll
     for (int q = 0; q < C::PIECES; ++q) {
       const unsigned dst = dst0 + static_cast<unsigned>(buf * C::STAGE + q * 1024);
-      unsigned keep;
-      asm volatile(
-          "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-          "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-          : "=&s"(keep)
-          : "v"(voff[q]), "s"(dst), "s"(sbase)
-          : "memory");
+      lds_dma_x4(voff[q], dst, sbase);
     }
   };
   issue(0, 0);

@@ -15,6 +15,14 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def functions(lib):
+    for _, name, chunk in object_functions(lib):
+        yield name, chunk
+
+
+def object_functions(lib):
+    """(code object index, function name, disassembly) for every function of
+    the library's gfx950 code objects, one object per source file in link order
+    (file-local helpers of two sources may share a name)."""
     with tempfile.TemporaryDirectory() as tmp:
         p = os.path.join(tmp, "lib.so")
         shutil.copy(lib, p)
@@ -27,7 +35,7 @@ def functions(lib):
             for chunk in re.split(r"\n(?=[0-9a-f]+ <)", dis):
                 m = re.match(r"[0-9a-f]+ <(.*?)>:", chunk)
                 if m:
-                    yield m.group(1), chunk
+                    yield int(f.split(".")[2]), m.group(1), chunk  # lib.so.<index>.hipv4-...-gfx950
 
 
 def stats(body):
