@@ -155,7 +155,9 @@ __device__ __forceinline__ unsigned wave_sum_u32_dpp(unsigned v) {
       wave_reduce_u64(v, 0ull, [](unsigned long long a, unsigned long long b) { return a + b; }));
 }
 
-// Internal hooks of dal_dw_step into dal_forest_score's kernel (forest.hip):
+// Internal hooks of dal_dw_step into dal_forest_score's kernel (forest.hip),
+// and of dal_dw_step_multiclass into the C-class density kernels (the blocked
+// one takes them all, the row-major one the status and flag hooks only):
 //   status_reset (nullable) is zeroed by the first thread, before any later
 //                kernel of the step can raise a flag (a replayed step starts clean);
 //   base_flags   (nullable; the warm-step plan) the row flags are built here:
@@ -201,6 +203,43 @@ int forest_score_launch(const float* x, const float* xb, const void* fprep, int6
                         double beta, int order, int32_t* votes, double* scores, uint64_t* keys,
                         uint64_t* keys_hi, const ForestStepHooks& hooks, hipStream_t st);
 
+// The C-class score of dal_dw_step_multiclass: dal_forest_score_multiclass_dw_
+// blocked's operands (DAL_DENSITY_FIXED) without the buffers the selection
+// shares with the binary step (row flags, scores, keys).
+struct McStepScore {
+  const float* x;
+  const float* xb;    // nullable: the row-major kernel
+  const void* fprep;  // with xb, where the blocked rule applies
+  int64_t n, d, ldx;
+  const int32_t* inner;
+  const uint8_t* leaf;
+  int32_t n_trees, depth, n_classes;
+  const double* lut;  // multiclass_lut("entropy", T)
+  const int64_t* density_fixed;
+  double density_err, beta;
+  uint8_t* counts;  // nullable
+  uint8_t* pred;    // nullable
+  double* entropy;
+  int32_t* row_index;
+};
+// Rows per block of the blocked C-class kernel (a tile of the blocked copy).
+constexpr int kMcStepRows = 64;
+// The score entries' shape checks alone (pure host code).
+int forest_multiclass_step_shape_check(int64_t n, int64_t d, int32_t n_trees, int32_t depth, int32_t n_classes);
+// The blocked C-class kernel runs (xb given and dal_forest_multiclass_blocked_rows
+// non-zero): its 64-row tiles are then the step's row groups.
+bool forest_multiclass_step_blocked(const float* xb, int64_t d, int32_t n_trees, int32_t depth, int32_t n_classes);
+// The score entries' checks (forest_shared.hpp, mc_validate; with xb the
+// blocked operands'), before n == 0; args_ok: the caller's own operand tests.
+int forest_multiclass_step_check(const McStepScore& S, bool args_ok);
+// The launch with the step hooks (forest_multi_blocked.hip; gmin with the
+// blocked kernel only), and the row-major kernel's (forest_multi.hip).
+int forest_multiclass_step_launch(const McStepScore& S, const uint8_t* row_flags, double* scores, uint64_t* keys,
+                                  uint64_t* keys_hi, const ForestStepHooks& hooks, hipStream_t st);
+int forest_multiclass_step_launch_rowmajor(const McStepScore& S, const uint8_t* row_flags, double* scores,
+                                           uint64_t* keys, uint64_t* keys_hi, const ForestStepHooks& hooks,
+                                           hipStream_t st);
+
 // dal_dw_step with the plan's publishing hooks (topk.hip, SortTail): the
 // selection is also written to *out_slot (a host-mapped word holding a device
 // address; nullable) and the final status word to *status_mirror (host-mapped).
@@ -214,5 +253,14 @@ int dw_step_impl(const float* x, const float* xb, const void* fprep, int64_t n, 
                  double* out_scores, uint64_t* out_keys, int32_t* dev_status, dal_event_t colsum_ready,
                  dal_stream_t stream, int64_t* const* out_slot, int32_t* status_mirror,
                  const ForestStepHooks* plan_hooks);
+
+// dal_dw_step_multiclass with the plan's publishing hooks (topk.hip): the
+// C-class score kernel under dw_step_impl's step.
+int dw_step_multiclass_impl(const McStepScore& M, const uint8_t* row_flags, int64_t idx_base, const double* norm64,
+                            const double* colsum, int64_t k, int64_t cap, int32_t level1_passes,
+                            uint32_t step_flags, void* ws, size_t ws_bytes, double* scores, uint64_t* keys_lo,
+                            uint64_t* keys_hi, int64_t* out_idx, double* out_scores, uint64_t* out_keys,
+                            int32_t* dev_status, dal_event_t colsum_ready, dal_stream_t stream,
+                            int64_t* const* out_slot, int32_t* status_mirror, const ForestStepHooks* plan_hooks);
 
 }  // namespace dal

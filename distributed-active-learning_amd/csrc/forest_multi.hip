@@ -148,108 +148,39 @@ __device__ __forceinline__ void score_tile_multi(const Args& A, const float* xs,
 // the blocks resident at once, walking tiles blockIdx.x, + gridDim.x, ...): the
 // forest and the LUT are copied into LDS once per block instead of once per
 // tile.  LDS: [R staged rows | LUT, T + 1 doubles | forest nodes, leaves].
+// The body is forest_multi_body.inc: the kernels below and the step form's
+// (McStepArgs: the density-weighted form's arguments and the step hooks).
+struct McStepArgs : McDwArgs {
+  ForestStepHooks hooks;
+};
+
 template <int CW, bool X_LDS, bool F_LDS, bool PERSIST, bool DW, bool POW>
 __global__ __launch_bounds__(kMcThreads) void forest_multi_kernel(std::conditional_t<DW, McDwArgs, McArgs> A, int R,
                                                                   int tpr, int x_floats, bool vec4, bool pad4,
                                                                   bool dma, int64_t n_tiles) {
-  static_assert(!PERSIST || X_LDS, "the persistent form stages rows by LDS-DMA");
-  if (PERSIST) {
-    dma = true;
-    vec4 = false;
-    pad4 = true;
-  }
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* xs = reinterpret_cast<float*>(smem);
-  double* lut_s = reinterpret_cast<double*>(smem + static_cast<size_t>(x_floats) * 4);  // (x_floats % 4 == 0)
-  const int n_inner = (1 << A.depth) - 1;
-  const int n_leaf = 1 << A.depth;
-  const int2* inner = A.inner;
-  const uint8_t* leaf = A.leaf;
-  const int tid = threadIdx.x;
-  for (int i = tid; i <= A.n_trees; i += kMcThreads) lut_s[i] = A.lut[i];  // (read after the staging barrier)
-  if (F_LDS) {
-    int2* fs = reinterpret_cast<int2*>(lut_s + round_up(A.n_trees + 1, 2));
-    uint8_t* ls = reinterpret_cast<uint8_t*>(fs + A.n_trees * n_inner);
-    for (int e = tid; e < A.n_trees * n_inner; e += kMcThreads) fs[e] = A.inner[e];
-    for (int e = tid; e < A.n_trees * n_leaf; e += kMcThreads) ls[e] = A.leaf[e];
-    inner = fs;
-    leaf = ls;
-  }
-  // row stride in LDS: d + 1 words for scalar staging; d + 4 with 16-B staging
-  // (rows stay 16-B aligned, rows of a wave start 4 banks apart)
-  const int xstride = A.d + (pad4 ? 4 : 1);
-  const int r = tid / tpr;  // (the row / tree-phase mapping of score_tile_multi)
-  const int sub = tid - r * tpr;
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {  // block-uniform
-    const int64_t row0 = tile * R;
-    const int64_t row = row0 + r;
-    const bool live = r < R && row < A.n;
-    // the row leader's flags are loaded with the tile (one HBM latency per tile)
-    uint8_t fl_pre = DAL_ROW_CANDIDATE;
-    if (A.flags && live && sub == 0) fl_pre = A.flags[row];
-    long long dens_pre = 0;  // ... and, DW, its density word
-    if constexpr (DW) {
-      if (live && sub == 0) dens_pre = static_cast<const long long*>(A.density)[row];
-    }
-    if (X_LDS) {
-      const int rows_here = static_cast<int>(min(static_cast<int64_t>(R), A.n - row0));
-      if (dma) {
-        // LDS-DMA staging (d % 4 == 0, 16-B-aligned padded rows): one
-        // global_load_lds_dwordx4 per 1 KiB of a row (the last piece with only
-        // the lanes it needs), lane l's 16 B landing at M0 + 16 l
-        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-        const int row_bytes = A.d * 4;
-        for (int rr = wave; rr < rows_here; rr += kMcThreads / 64) {
-          const float* src = A.x + (row0 + rr) * A.ldx;
-          for (int p = 0; p * 1024 < row_bytes; ++p) {
-            typedef __attribute__((address_space(3))) float lds_float;
-            const unsigned dst = __builtin_amdgcn_readfirstlane(
-                static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_float*)(xs + rr * xstride + p * 256))));
-            const unsigned voff = static_cast<unsigned>(p * 1024 + lane * 16);
-            if (static_cast<int>(voff) < row_bytes) lds_dma_x4(voff, dst, src);
-          }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      } else if (vec4) {
-        // 16-B loads, kStageBatch per thread issued before any LDS write
-        constexpr int kStageBatch = 8;
-        const int q = A.d >> 2, total = rows_here * q;
-        for (int e0 = 0; e0 < total; e0 += kMcThreads * kStageBatch) {
-          typedef float v4f __attribute__((ext_vector_type(4)));
-          v4f v[kStageBatch];
-#pragma unroll
-          for (int j = 0; j < kStageBatch; ++j) {
-            const int e = e0 + j * kMcThreads + tid;
-            if (e < total) {
-              const int rr = e / q, c = e - rr * q;
-              v[j] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(A.x + (row0 + rr) * A.ldx) + c);
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < kStageBatch; ++j) {
-            const int e = e0 + j * kMcThreads + tid;
-            if (e < total) {
-              const int rr = e / q, c = e - rr * q;
-              *reinterpret_cast<v4f*>(xs + rr * xstride + 4 * c) = v[j];  // (vec4 implies pad4: 16-B aligned rows)
-            }
-          }
-        }
-      } else {
-        for (int e = tid; e < rows_here * A.d; e += kMcThreads) {
-          const int rr = e / A.d, c = e - rr * A.d;
-          xs[rr * xstride + c] = A.x[(row0 + rr) * A.ldx + c];
-        }
-      }
-    }
-    __syncthreads();
-    score_tile_multi<CW, X_LDS, DW, POW>(A, xs, xstride, tile, R, tpr, inner, leaf, fl_pre, dens_pre, lut_s);
-    if (!PERSIST) break;
-    __syncthreads();  // every wave done with the tile before the next one is staged
-  }
+  constexpr bool STEP = std::is_same_v<decltype(A), McStepArgs>;  // false
+#include "forest_multi_body.inc"
+}
+
+// dal_dw_step_multiclass's row-major kernel: the density-weighted form with
+// the status and flag hooks, the same body.
+template <int CW, bool X_LDS, bool F_LDS, bool PERSIST, bool POW>
+__global__ __launch_bounds__(kMcThreads) void forest_multi_step_kernel(McStepArgs A, int R, int tpr, int x_floats,
+                                                                       bool vec4, bool pad4, bool dma,
+                                                                       int64_t n_tiles) {
+  constexpr bool DW = true, STEP = true;
+#include "forest_multi_body.inc"
+}
+
+// The kernel of a form: STEP (Args = McStepArgs) the one with the step hooks.
+template <int CW, bool XL, bool FL, bool PS, bool DW, bool POW, bool STEP>
+constexpr auto mc_kernel() {
+  if constexpr (STEP) return &forest_multi_step_kernel<CW, XL, FL, PS, POW>;
+  else return &forest_multi_kernel<CW, XL, FL, PS, DW, POW>;
 }
 
 // The binary launcher's tiling rule (forest_shared.hpp, forest_tiling).
-template <int CW, bool DW, bool POW, class Args>
+template <int CW, bool DW, bool POW, bool STEP = false, class Args>
 int multi_launch(const Args& A, int64_t d, int64_t ldx, hipStream_t st) {
   const ForestTiling T = forest_tiling(A.x, d, ldx, A.n_trees, kMcThreads);
   const int R = T.R, tpr = kMcThreads / R;
@@ -264,7 +195,8 @@ int multi_launch(const Args& A, int64_t d, int64_t ldx, hipStream_t st) {
                       (f_lds ? static_cast<size_t>(f_bytes) : 0);
 #define DAL_MC_LAUNCH(XL, FL, PS)                                                                          \
   do {                                                                                                     \
-    const void* fn = reinterpret_cast<const void*>(forest_multi_kernel<CW, XL, FL, PS, DW, POW>);          \
+    const auto kern = mc_kernel<CW, XL, FL, PS, DW, POW, STEP>();                                          \
+    const void* fn = reinterpret_cast<const void*>(kern);                                                  \
     int64_t grid = blocks;                                                                                 \
     if (PS) { /* a persistent grid of exactly the blocks resident at once */                               \
       grid = persistent_grid(fn, kMcThreads, smem, 0, blocks);                                             \
@@ -273,8 +205,8 @@ int multi_launch(const Args& A, int64_t d, int64_t ldx, hipStream_t st) {
                                    static_cast<int>(smem)) != hipSuccess) {                                \
       return DAL_ERR_HIP;                                                                                  \
     }                                                                                                      \
-    hipLaunchKernelGGL((forest_multi_kernel<CW, XL, FL, PS, DW, POW>), dim3(static_cast<unsigned>(grid)),  \
-                       dim3(kMcThreads), smem, st, A, R, tpr, xf, vec4, pad4, T.dma, blocks);              \
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kMcThreads), smem, st, A, R, tpr, xf, \
+                       vec4, pad4, T.dma, blocks);                                                         \
   } while (0)
   if (T.dma && f_lds) DAL_MC_LAUNCH(true, true, true);
   else if (T.dma) DAL_MC_LAUNCH(true, false, true);
@@ -288,6 +220,24 @@ int multi_launch(const Args& A, int64_t d, int64_t ldx, hipStream_t st) {
 }
 
 }  // namespace
+
+int forest_multiclass_step_launch_rowmajor(const McStepScore& S, const uint8_t* row_flags, double* scores,
+                                           uint64_t* keys, uint64_t* keys_hi, const ForestStepHooks& hooks,
+                                           hipStream_t st) {
+  if (hooks.gmin) return DAL_ERR_ARG;  // no group fold in the row-major kernel
+  if (S.n == 0) return DAL_OK;
+  const McStepArgs A{{{S.x, S.n, static_cast<int>(S.d), S.ldx, reinterpret_cast<const int2*>(S.inner), S.leaf,
+                       S.n_trees, S.depth, S.n_classes, S.lut, DAL_MC_ENTROPY, row_flags, DAL_DESCENDING, S.counts,
+                       S.pred, scores, keys, mc_cstore(S.counts, S.n_classes)},
+                      S.density_fixed, DAL_DENSITY_FIXED, S.density_err, S.beta, S.entropy, S.row_index, keys_hi},
+                     hooks};
+  return dispatch_cw(S.n_classes, [&](auto cw) {
+    constexpr int CW = decltype(cw)::value;
+    return S.beta == 1.0 ? multi_launch<CW, true, false, true>(A, S.d, S.ldx, st)
+                         : multi_launch<CW, true, true, true>(A, S.d, S.ldx, st);
+  });
+}
+
 }  // namespace dal
 
 using namespace dal;

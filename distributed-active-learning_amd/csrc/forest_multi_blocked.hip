@@ -34,6 +34,12 @@
 // LDS: [tile, fu_max runs of 256 B | prepared payload: nodes, leaves, feature
 // list | LUT, round2(T + 1) doubles | exchange, (NW - 1) CW 256-B rows].
 //
+// The kernels' body is forest_multi_blocked_body.inc, included into the kernels
+// the four score entries launch and into the step kernel of
+// dal_dw_step_multiclass (forest_multi_blocked_step_kernel: the density-weighted
+// form with ForestStepHooks -- status reset, plan flags, and the tiles' minimum
+// keys folded into the top-k's row groups by wave 0).
+//
 // The prepared layout, a tile's DMA instruction, the walks, the counters and
 // the row epilogue are forest_shared.hpp's, the definitions forest.hip and
 // forest_multi.hip use (these kernels compile from them to the instructions
@@ -89,96 +95,59 @@ struct McDwArgs : McArgs {
   uint64_t* keys_hi;  // nullable
 };
 
+// The step form's arguments (dal_dw_step_multiclass): the density-weighted
+// form's and the step hooks (common.hpp), with the meaning forest.hip gives
+// them.  The kernels without hooks take the structs they always took.
+struct McStepArgs : McDwArgs {
+  ForestStepHooks hooks;
+};
+
+#ifndef DAL_MCB_DEFER_FOLD
+#define DAL_MCB_DEFER_FOLD 1
+#endif
+// The step kernel's atomic group fold (several tiles per group) is issued by
+// thread 0 after the NEXT tile's DMA wait in the four-wave kernels (1), or at
+// once in the epilogue everywhere (0).  The fused step's device span, us,
+// at once / deferred in every kernel, 30 rounds each, beside the unfused pair
+// of the same run (kernel, group_min_kernel, select): config 4 (2M x 256,
+// T = 10, C = 10, four waves) 267.8 / 249.3 (pair 255.7 / 256.5); config 4 at
+// T = 100 (eight waves) 703.5 / 789.7 (pair 715.6 / 716.5); config 3 (four
+// waves) 68.8 / 68.6 (pair 69.2 / 69.0).  So: deferred where the block has four
+// waves, at once where it has eight.
+constexpr bool kMcbDeferFold = DAL_MCB_DEFER_FOLD != 0;
+
+// A tile's wave minima awaiting their atomics (thread 0 of the step kernel).
+struct McbFold {
+  unsigned long long lo = DAL_KEY_NONE, hi = DAL_KEY_NONE;
+  uint32_t g = 0;
+  bool pending = false;
+};
+__device__ __forceinline__ void mcb_issue_fold(const ForestStepHooks& H, McbFold& f) {
+  if (!f.pending) return;
+  unsigned long long* lo_g = reinterpret_cast<unsigned long long*>(H.gmin) + f.g;
+  if (f.lo != DAL_KEY_NONE) atomicMax(lo_g, ~f.lo);
+  if (f.hi != DAL_KEY_NONE) atomicMax(lo_g + H.n_groups, ~f.hi);
+  f.pending = false;
+}
+
 template <int NW, int CW, bool DW, bool POW>
 __global__ __launch_bounds__(NW * 64) void forest_multi_blocked_kernel(std::conditional_t<DW, McDwArgs, McArgs> A,
                                                                        const float* __restrict__ xb,
                                                                        const unsigned char* __restrict__ prep,
                                                                        int fu_max, int64_t n_tiles) {
-  constexpr int NT = NW * 64;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int n_inner = (1 << A.depth) - 1, n_leaf = 1 << A.depth;
-  const BlockedPrepLayout L = blocked_prep_layout(A.n_trees, A.depth, fu_max);
-  float* xs = reinterpret_cast<float*>(smem);
-  unsigned char* fs = smem + static_cast<size_t>(fu_max) * kBlk * 4;  // the prepared payload
-  const uint8_t* ls = fs + L.nodes;
-  const uint16_t* used = reinterpret_cast<const uint16_t*>(fs + L.nodes + L.leaves);
-  double* lut_s = reinterpret_cast<double*>(fs + L.payload);                      // (16-B aligned)
-  unsigned* ex = reinterpret_cast<unsigned*>(lut_s + round_up(A.n_trees + 1, 2));  // (16-B aligned)
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  for (int i = tid; i <= A.n_trees; i += NT) lut_s[i] = A.lut[i];
-  {
-    // the prepared payload -> LDS, 16 B per thread, kPrepBatch loads in flight
-    // (forest.hip's loop)
-    constexpr int kPrepBatch = 4;
-    const int n16 = static_cast<int>(L.payload >> 4);
-    const uint4* src = reinterpret_cast<const uint4*>(prep + 16);
-    uint4* dst = reinterpret_cast<uint4*>(fs);
-    for (int e0 = tid; e0 < n16; e0 += kPrepBatch * NT) {
-      uint4 q[kPrepBatch];
-#pragma unroll
-      for (int j = 0; j < kPrepBatch; ++j) q[j] = e0 + j * NT < n16 ? src[e0 + j * NT] : uint4{};
-#pragma unroll
-      for (int j = 0; j < kPrepBatch; ++j)
-        if (e0 + j * NT < n16) dst[e0 + j * NT] = q[j];
-    }
-  }
-  int fu = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(prep));
-  fu = fu < fu_max ? fu : fu_max;  // (the buffer's own bound: the tile holds fu_max runs)
-  __syncthreads();
-  const int n_ins = blocked_dma_count(fu);  // DMA instructions per tile (4 runs each)
-  typedef __attribute__((address_space(3))) float lds_float;
-  typedef __attribute__((address_space(3))) const unsigned char lds_u8;
-  const ByteWalk W{static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_u8*)fs)),
-                   static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_u8*)ls)),
-                   static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_float*)(xs + lane))),
-                   NW, n_inner, n_leaf, A.depth};
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {  // block-uniform
-    const int64_t row = tile * kBlk + lane;
-    const bool live = row < A.n;
-    const bool lead = wave == 0 && live;  // the rows' epilogue: wave 0
-    // the row leader's flags (and, DW, its density word) are loaded with the tile
-    uint8_t fl_pre = DAL_ROW_CANDIDATE;
-    long long dens_pre = 0;
-    if (lead) {
-      if (A.flags) fl_pre = A.flags[row];
-      if constexpr (DW) dens_pre = static_cast<const long long*>(A.density)[row];
-    }
-    const char* src = reinterpret_cast<const char*>(xb + tile * A.d * kBlk);
-    // (wave 0 stages nothing unless kMcbStageWave0)
-    for (int i = kMcbStageWave0 ? wave : wave - 1; i >= 0 && i < n_ins; i += kMcbStageWave0 ? NW : NW - 1)
-      stage_blocked_runs(xs, src, used, fu, i, lane);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    unsigned w[CW];
-#pragma unroll
-    for (int j = 0; j < CW; ++j) w[j] = 0u;
-    if (live) {
-      // groups of ILP trees, then the wave's last trees as ONE group of their
-      // count; each tree's leaf byte is a class id, voted into w
-      auto vote = [&](unsigned c) { add_vote<CW>(w, c); };
-      for (int t = wave; t < A.n_trees; t += kMcbIlp * NW) {  // (wave-uniform)
-        const int rem = (A.n_trees - t + NW - 1) / NW;
-        if (rem >= kMcbIlp) walk_group<kMcbIlp>(W, t, vote);
-        else walk_tail<kMcbIlp - 1>(W, t, rem, vote);
-      }
-    }
-    // a row's NW partial word sets, one per wave, added field by field
-    // through LDS (a field's total <= T <= 255: no carry)
-    if (wave != 0) {
-#pragma unroll
-      for (int j = 0; j < CW; ++j) ex[((wave - 1) * CW + j) * kBlk + lane] = w[j];
-    }
-    __syncthreads();  // ... and every walk of this tile is over: the next tile may be staged
-    if (wave == 0) {
-#pragma unroll
-      for (int q = 0; q < NW - 1; ++q) {
-#pragma unroll
-        for (int j = 0; j < CW; ++j) w[j] += ex[(q * CW + j) * kBlk + lane];
-      }
-      if (live) row_epilogue<CW, DW, POW>(A, w, row, fl_pre, dens_pre, lut_s);
-    }
-  }
+  constexpr bool STEP = std::is_same_v<decltype(A), McStepArgs>;  // false
+#include "forest_multi_blocked_body.inc"
+}
+
+// dal_dw_step_multiclass's kernel: the density-weighted form with the step
+// hooks, the same body.
+template <int NW, int CW, bool POW>
+__global__ __launch_bounds__(NW * 64) void forest_multi_blocked_step_kernel(McStepArgs A,
+                                                                            const float* __restrict__ xb,
+                                                                            const unsigned char* __restrict__ prep,
+                                                                            int fu_max, int64_t n_tiles) {
+  constexpr bool DW = true, STEP = true;
+#include "forest_multi_blocked_body.inc"
 }
 
 // The applicability rule and the launch shape.  The prepared forest is
@@ -212,23 +181,25 @@ McbPlan mcb_plan(int64_t d, int32_t n_trees, int32_t depth, int32_t n_classes) {
   return P;
 }
 
-template <int CW, bool DW, bool POW, class Args>
+// The kernel of a form: STEP (Args = McStepArgs) the one with the step hooks.
+template <int NW, int CW, bool DW, bool POW, bool STEP>
+constexpr auto mcb_kernel() {
+  if constexpr (STEP) return &forest_multi_blocked_step_kernel<NW, CW, POW>;
+  else return &forest_multi_blocked_kernel<NW, CW, DW, POW>;
+}
+
+template <int CW, bool DW, bool POW, bool STEP = false, class Args>
 int mcb_launch(const Args& A, const float* xb, const void* fprep, const McbPlan& P, hipStream_t st) {
   const int64_t tiles = ceil_div(A.n, kBlk);
   const bool wide = P.nw == kMcbWavesWide;
-  const void* fn = wide ? reinterpret_cast<const void*>(forest_multi_blocked_kernel<kMcbWavesWide, CW, DW, POW>)
-                        : reinterpret_cast<const void*>(forest_multi_blocked_kernel<kMcbWaves, CW, DW, POW>);
+  const auto kern = wide ? mcb_kernel<kMcbWavesWide, CW, DW, POW, STEP>() : mcb_kernel<kMcbWaves, CW, DW, POW, STEP>();
   // a persistent grid of the blocks resident at once, kMcbPerCu per CU at
   // most: every block stages the forest once (forest.hip)
-  const int64_t grid = persistent_grid(fn, P.nw * 64, P.smem, kMcbPerCu, tiles);
+  const int64_t grid = persistent_grid(reinterpret_cast<const void*>(kern), P.nw * 64, P.smem, kMcbPerCu, tiles);
   if (grid < 0) return static_cast<int>(grid);
   const unsigned char* pb = static_cast<const unsigned char*>(fprep);
-  if (wide)
-    hipLaunchKernelGGL((forest_multi_blocked_kernel<kMcbWavesWide, CW, DW, POW>), dim3(static_cast<unsigned>(grid)),
-                       dim3(kMcbWavesWide * 64), P.smem, st, A, xb, pb, P.fu_max, tiles);
-  else
-    hipLaunchKernelGGL((forest_multi_blocked_kernel<kMcbWaves, CW, DW, POW>), dim3(static_cast<unsigned>(grid)),
-                       dim3(kMcbWaves * 64), P.smem, st, A, xb, pb, P.fu_max, tiles);
+  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(P.nw * 64), P.smem, st, A, xb, pb, P.fu_max,
+                     tiles);
   DAL_RETURN_IF_LAUNCH_FAILED();
   return DAL_OK;
 }
@@ -245,6 +216,47 @@ int mcb_validate(bool args_ok, const float* xb, const void* fprep, int64_t n, in
 }
 
 }  // namespace
+
+// The score launch of dal_dw_step_multiclass (common.hpp): the blocked kernel
+// with the step hooks when the step has a blocked copy and the rule applies,
+// else forest_multi.hip's row-major one (status and flag hooks only).
+bool forest_multiclass_step_blocked(const float* xb, int64_t d, int32_t n_trees, int32_t depth, int32_t n_classes) {
+  return xb && mcb_plan(d, n_trees, depth, n_classes).fu_max;
+}
+
+static_assert(kMcStepRows == kBlk, "the step's row groups are the blocked kernel's tiles");
+
+int forest_multiclass_step_shape_check(int64_t n, int64_t d, int32_t n_trees, int32_t depth, int32_t n_classes) {
+  return mc_validate(true, n, d, d, n_trees, depth, n_classes, true);
+}
+
+int forest_multiclass_step_check(const McStepScore& S, bool args_ok) {
+  args_ok = args_ok && S.x && S.inner && S.leaf && S.lut && S.density_fixed && S.entropy && S.row_index;
+  if (!S.xb) return mc_validate(args_ok, S.n, S.d, S.ldx, S.n_trees, S.depth, S.n_classes, true);
+  return mcb_validate(args_ok, S.xb, S.fprep, S.n, S.d, S.ldx, S.n_trees, S.depth, S.n_classes, true);
+}
+
+int forest_multiclass_step_launch(const McStepScore& S, const uint8_t* row_flags, double* scores, uint64_t* keys,
+                                  uint64_t* keys_hi, const ForestStepHooks& hooks, hipStream_t st) {
+  if (S.n == 0) return DAL_OK;
+  if (!forest_multiclass_step_blocked(S.xb, S.d, S.n_trees, S.depth, S.n_classes))
+    return forest_multiclass_step_launch_rowmajor(S, row_flags, scores, keys, keys_hi, hooks, st);
+  // the row groups are whole tiles, and every group index lies below n_groups
+  if (hooks.gmin &&
+      (hooks.group_blocks < 1 || ceil_div(ceil_div(S.n, kBlk), hooks.group_blocks) != hooks.n_groups))
+    return DAL_ERR_ARG;
+  const McbPlan P = mcb_plan(S.d, S.n_trees, S.depth, S.n_classes);
+  const McStepArgs A{{{S.n, static_cast<int>(S.d), S.n_trees, S.depth, S.n_classes, S.lut, DAL_MC_ENTROPY, row_flags,
+                       DAL_DESCENDING, S.counts, S.pred, scores, keys, mc_cstore(S.counts, S.n_classes)},
+                      S.density_fixed, DAL_DENSITY_FIXED, S.density_err, S.beta, S.entropy, S.row_index, keys_hi},
+                     hooks};
+  return dispatch_cw(S.n_classes, [&](auto cw) {
+    constexpr int CW = decltype(cw)::value;
+    return S.beta == 1.0 ? mcb_launch<CW, true, false, true>(A, S.xb, S.fprep, P, st)
+                         : mcb_launch<CW, true, true, true>(A, S.xb, S.fprep, P, st);
+  });
+}
+
 }  // namespace dal
 
 using namespace dal;

@@ -89,10 +89,14 @@ __device__ __forceinline__ int vote_field(const unsigned (&w)[CW], int c) {  // 
 
 // The multiclass row leader's epilogue: w holds the row's C counts.  Args: a
 // kernel's McArgs, or with DW its McDwArgs (fl_pre: the row's flags; dens_pre:
-// its density word, both loaded with the tile).
+// its density word, both loaded with the tile).  Hands back the row's interval
+// keys (DW; DAL_KEY_NONE for a non-candidate) for the step kernels' group fold.
+struct RowKeys {
+  unsigned long long lo = DAL_KEY_NONE, hi = DAL_KEY_NONE;
+};
 template <int CW, bool DW, bool POW, class Args>
-__device__ __forceinline__ void row_epilogue(const Args& A, const unsigned (&w)[CW], int64_t row, uint8_t fl_pre,
-                                             long long dens_pre, const double* lut_s) {
+__device__ __forceinline__ RowKeys row_epilogue(const Args& A, const unsigned (&w)[CW], int64_t row, uint8_t fl_pre,
+                                                long long dens_pre, const double* lut_s) {
   const int C = A.n_classes;
   // largest and second-largest count, the lowest class holding the largest
   int m1 = -1, m2 = -1, arg = 0;
@@ -161,10 +165,24 @@ __device__ __forceinline__ void row_epilogue(const Args& A, const unsigned (&w)[
     A.scores[row] = s;
     A.keys[row] = klo;
     if (A.keys_hi) A.keys_hi[row] = khi;
+    return RowKeys{klo, khi};
   } else {
     A.scores[row] = s;
     A.keys[row] = (fl_pre & DAL_ROW_CANDIDATE) ? score_key(s, A.order) : DAL_KEY_NONE;
+    return RowKeys{};
   }
+}
+
+// The row leader's flags in a step kernel of the multiclass forms
+// (ForestStepHooks, forest.hip's row_flag): row_flags[row], or for a plan the
+// pool's base flags with DAL_ROW_CANDIDATE from this step's mark stamp --
+// written to row_flags for the step's later kernels when write_flags is set.
+__device__ __forceinline__ uint8_t step_row_flag(const ForestStepHooks& H, const uint8_t* flags, int64_t row) {
+  if (!H.base_flags) return flags ? flags[row] : static_cast<uint8_t>(DAL_ROW_CANDIDATE);
+  const bool cand = H.stamp[row] == static_cast<uint8_t>(*H.step_id);
+  const uint8_t fl = static_cast<uint8_t>(H.base_flags[row] | (cand ? DAL_ROW_CANDIDATE : 0));
+  if (H.write_flags && flags) const_cast<uint8_t*>(flags)[row] = fl;
+  return fl;
 }
 
 // ------------------------------------------------- byte-addressed walks --

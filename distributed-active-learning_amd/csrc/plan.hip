@@ -122,16 +122,15 @@ class DeviceGuard {
   bool ok_ = false;
 };
 
-extern "C" int dal_dw_plan_create(const float* x, const float* xb, const void* fprep, int64_t n, int64_t d,
-                                  int64_t ldx,
-                                  const int32_t* inner,
-                                  const uint8_t* leaf, int32_t n_trees, int32_t depth, const double* lut,
-                                  const int64_t* density_fixed, double density_err, const uint8_t* base_flags,
-                                  uint8_t* flags, double beta, int64_t idx_base, const double* norm64,
-                                  const double* colsum, int64_t k, int64_t cap, int32_t level1_passes, void* ws,
-                                  size_t ws_bytes, int32_t* votes, double* scores, uint64_t* keys_lo,
-                                  uint64_t* keys_hi, int64_t* out_pair, uint64_t* out_keys, int32_t* dev_status,
-                                  dal_stream_t stream, dal_dw_plan_t** plan_out) {
+// The creator both plans share: the host-mapped slot, the stamps, the capture
+// of [mark kernel, step(capture stream, hooks, slot)] and the mark node's
+// lookup.  step queues one fused step (DAL_STEP_RESET_STATUS |
+// DAL_STEP_WS_CLEAN) with the plan's flag hooks and publishing slot: the
+// binary dw_step_impl or the C-class dw_step_multiclass_impl.
+template <class Step>
+static int plan_create(int64_t n, const uint8_t* base_flags, uint8_t* flags, int64_t idx_base, int64_t k, void* ws,
+                       size_t ws_bytes, int64_t* out_pair, int32_t* dev_status, dal_stream_t stream,
+                       dal_dw_plan_t** plan_out, Step&& step) {
   if (!plan_out || !base_flags || !flags || !out_pair || !ws) return DAL_ERR_ARG;
   *plan_out = nullptr;
   if (n < 1 || k < 1) return DAL_ERR_SHAPE;
@@ -169,11 +168,7 @@ extern "C" int dal_dw_plan_create(const float* x, const float* xb, const void* f
     hooks.base_flags = base_flags;
     hooks.stamp = p->stamp;
     hooks.step_id = p->step_dev;
-    const int step_rc = dw_step_impl(x, xb, fprep, n, d, ldx, inner, leaf, n_trees, depth, lut, density_fixed, density_err,
-                                     flags, beta, idx_base, norm64, colsum, k, cap, level1_passes,
-                                     DAL_STEP_RESET_STATUS | DAL_STEP_WS_CLEAN, ws, ws_bytes, votes, scores, keys_lo,
-                                     keys_hi, out_pair, reinterpret_cast<double*>(out_pair + k), out_keys,
-                                     dev_status, nullptr, cs, p->slot_dev->out, &p->slot_dev->status, &hooks);
+    const int step_rc = step(cs, hooks, p->slot_dev);
     const hipError_t end = hipStreamEndCapture(cs, &p->graph);
     rc = step_rc ? step_rc : (end != hipSuccess ? DAL_ERR_HIP : DAL_OK);
   }
@@ -211,6 +206,51 @@ extern "C" int dal_dw_plan_create(const float* x, const float* xb, const void* f
   p->dev_status = dev_status;
   *plan_out = p;
   return DAL_OK;
+}
+
+extern "C" int dal_dw_plan_create(const float* x, const float* xb, const void* fprep, int64_t n, int64_t d,
+                                  int64_t ldx,
+                                  const int32_t* inner,
+                                  const uint8_t* leaf, int32_t n_trees, int32_t depth, const double* lut,
+                                  const int64_t* density_fixed, double density_err, const uint8_t* base_flags,
+                                  uint8_t* flags, double beta, int64_t idx_base, const double* norm64,
+                                  const double* colsum, int64_t k, int64_t cap, int32_t level1_passes, void* ws,
+                                  size_t ws_bytes, int32_t* votes, double* scores, uint64_t* keys_lo,
+                                  uint64_t* keys_hi, int64_t* out_pair, uint64_t* out_keys, int32_t* dev_status,
+                                  dal_stream_t stream, dal_dw_plan_t** plan_out) {
+  return plan_create(n, base_flags, flags, idx_base, k, ws, ws_bytes, out_pair, dev_status, stream, plan_out,
+                     [&](hipStream_t cs, const ForestStepHooks& hooks, PlanSlot* slot) {
+                       return dw_step_impl(x, xb, fprep, n, d, ldx, inner, leaf, n_trees, depth, lut, density_fixed,
+                                           density_err, flags, beta, idx_base, norm64, colsum, k, cap, level1_passes,
+                                           DAL_STEP_RESET_STATUS | DAL_STEP_WS_CLEAN, ws, ws_bytes, votes, scores,
+                                           keys_lo, keys_hi, out_pair, reinterpret_cast<double*>(out_pair + k),
+                                           out_keys, dev_status, nullptr, cs, slot->out, &slot->status, &hooks);
+                     });
+}
+
+// The C-class plan: dal_dw_step_multiclass captured the same way; run, launch
+// and destroy are the binary plan's.
+extern "C" int dal_dw_plan_create_multiclass(const float* x, const float* xb, const void* fprep, int64_t n,
+                                             int64_t d, int64_t ldx, const int32_t* inner, const uint8_t* leaf,
+                                             int32_t n_trees, int32_t depth, int32_t n_classes, const double* lut,
+                                             const int64_t* density_fixed, double density_err,
+                                             const uint8_t* base_flags, uint8_t* flags, double beta,
+                                             int64_t idx_base, const double* norm64, const double* colsum, int64_t k,
+                                             int64_t cap, int32_t level1_passes, void* ws, size_t ws_bytes,
+                                             uint8_t* counts, uint8_t* pred, double* entropy, int32_t* row_index,
+                                             double* scores, uint64_t* keys_lo, uint64_t* keys_hi, int64_t* out_pair,
+                                             uint64_t* out_keys, int32_t* dev_status, dal_stream_t stream,
+                                             dal_dw_plan_t** plan_out) {
+  const McStepScore M{x, xb, fprep, n, d, ldx, inner, leaf, n_trees, depth, n_classes, lut, density_fixed,
+                      density_err, beta, counts, pred, entropy, row_index};
+  return plan_create(n, base_flags, flags, idx_base, k, ws, ws_bytes, out_pair, dev_status, stream, plan_out,
+                     [&](hipStream_t cs, const ForestStepHooks& hooks, PlanSlot* slot) {
+                       return dw_step_multiclass_impl(M, flags, idx_base, norm64, colsum, k, cap, level1_passes,
+                                                      DAL_STEP_RESET_STATUS | DAL_STEP_WS_CLEAN, ws, ws_bytes, scores,
+                                                      keys_lo, keys_hi, out_pair,
+                                                      reinterpret_cast<double*>(out_pair + k), out_keys, dev_status,
+                                                      nullptr, cs, slot->out, &slot->status, &hooks);
+                     });
 }
 
 extern "C" int dal_dw_plan_run(dal_dw_plan_t* p, const int64_t* unl, int64_t n_unl, int64_t* out_idx,

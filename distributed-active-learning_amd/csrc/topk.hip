@@ -501,7 +501,14 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {  // l wave-uni
 // d^beta for beta != 1 (the reference declares beta, density_weighting.py:33;
 // 1 in every call): out of line, so its constants do not crowd the callers'
 // scalar registers.
-__device__ __attribute__((noinline)) double density_pow_canon(double d, double beta) { return pow(d, beta); }
+// beta == 2 is one multiply: d * d is the correctly rounded square, which the
+// fp64 reference's np.power(d, 2.0) returns too, while the device libm's pow is
+// good to an ulp only (two of sixteen selected scores at 2,500 x 256 came out
+// one ulp off the reference).  No other exponent is a single rounded
+// operation the same way on both sides; they stay with pow, to its ulp.
+__device__ __attribute__((noinline)) double density_pow_canon(double d, double beta) {
+  return beta == 2.0 ? d * d : pow(d, beta);
+}
 
 __device__ __forceinline__ bool dw_canonical_score_wave(const DwRerank& R, int64_t i, double& s, double* tr,
                                                         double lut_lane = 0.0, int n_lut = 0) {
@@ -2120,10 +2127,15 @@ static RerankWs rerank_ws(int64_t n, int64_t k, int64_t cap) {
 static size_t rerank_ws_bytes(int64_t n, int64_t k, int64_t cap) { return rerank_ws(n, k, cap).total; }
 
 // Candidate arguments shared by the level-1 checks of the three selections.
-static int check_rerank_args(int64_t n, int64_t k, int64_t cap, int passes, void* ws, size_t ws_bytes) {
+// (check_rerank_shape: the part that needs no workspace)
+static int check_rerank_shape(int64_t n, int64_t k, int64_t cap, int passes) {
   if (n < 1 || k < 1 || k > n || cap < k) return DAL_ERR_SHAPE;
   if (passes < 0 || passes >= kPasses || (passes > 0 && cap > DAL_SORT_CAP_PAYLOAD)) return DAL_ERR_ARG;
   if (k > DAL_SORT_CAP) return DAL_ERR_CAPACITY;
+  return DAL_OK;
+}
+static int check_rerank_args(int64_t n, int64_t k, int64_t cap, int passes, void* ws, size_t ws_bytes) {
+  if (const int rc = check_rerank_shape(n, k, cap, passes)) return rc;
   if (ws_bytes < rerank_ws_bytes(n, k, cap) || (reinterpret_cast<uintptr_t>(ws) & 255)) return DAL_ERR_SHAPE;
   return DAL_OK;
 }
@@ -2298,22 +2310,40 @@ extern "C" size_t dal_dw_step_workspace_bytes(int64_t n, int64_t k, int64_t cap)
 // with DAL_STEP_RESET_STATUS.  Same bits as the two calls.
 namespace dal {
 
-int dw_step_impl(const float* x, const float* xb, const void* fprep, int64_t n, int64_t d, int64_t ldx,
-                 const int32_t* inner,
-                 const uint8_t* leaf,
-                 int32_t n_trees, int32_t depth, const double* lut, const int64_t* density_fixed, double density_err,
-                 const uint8_t* row_flags, double beta, int64_t idx_base, const double* norm64, const double* colsum,
-                 int64_t k, int64_t cap, int32_t level1_passes, uint32_t step_flags, void* ws, size_t ws_bytes,
-                 int32_t* votes, double* scores, uint64_t* keys_lo, uint64_t* keys_hi, int64_t* out_idx,
-                 double* out_scores, uint64_t* out_keys, int32_t* dev_status, dal_event_t colsum_ready,
-                 dal_stream_t stream, int64_t* const* out_slot, int32_t* status_mirror,
-                 const ForestStepHooks* plan_hooks) {
-  if (!x || !inner || !leaf || !lut || !density_fixed || !norm64 || !colsum || !ws || !votes || !scores ||
-      !keys_lo || !keys_hi || !out_idx || !out_scores || !dev_status)
-    return DAL_ERR_ARG;
-  if (step_flags & ~static_cast<uint32_t>(DAL_STEP_RESET_STATUS | DAL_STEP_WS_CLEAN | DAL_STEP_KEEP_GROUPS |
-                                         DAL_STEP_SELECT_ONLY))
-    return DAL_ERR_ARG;
+// What the step needs of its score kernel: the binary forest score
+// (dal_dw_step) or the C-class one (dal_dw_step_multiclass).  launch(hooks)
+// queues the kernel with the step hooks; the re-rank's factor of row i is
+// lut[votes[i]].
+struct StepScore {
+  int rows_per_block;  // rows per block of the score kernel (its blocks are the row groups of the fold)
+  bool can_fold;       // the kernel folds its blocks' minimum keys (ForestStepHooks::gmin)
+  const double* lut;
+  const int32_t* votes;
+  int n_lut;  // > 0: the LUT is held in a wave's lanes (lut has n_lut <= 64 entries)
+};
+
+// The branch a step takes (dal_dw_step_multiclass_form's values): 0 exact
+// level 1; 1 fast, group_min_kernel pass after the score kernel; 2 fast, folded
+// in the score kernel with plain stores; 3 fast, folded with atomics.  The
+// score kernel's blocks are the row groups when there are >= 2k of them (tau
+// then lies within a few ranks of K); smaller pools take one group_min_kernel
+// pass over finer groups after the score kernel.
+static int step_form(const StepScore& sc, int64_t n, int64_t k, int32_t level1_passes) {
+  if (level1_passes == 0) return 0;
+  if (!sc.can_fold) return 1;
+  const GroupSummary S = make_groups(nullptr, n, sc.rows_per_block);
+  if (S.ng < 2 * k) return 1;
+  return S.group_rows == sc.rows_per_block ? 2 : 3;
+}
+
+template <class Launch>
+static int dw_step_core(const StepScore& sc, Launch&& launch, const float* x, int64_t n, int64_t d, int64_t ldx,
+                        const uint8_t* row_flags, double beta, int64_t idx_base, const double* norm64,
+                        const double* colsum, int64_t k, int64_t cap, int32_t level1_passes, uint32_t step_flags,
+                        void* ws, size_t ws_bytes, uint64_t* keys_lo, uint64_t* keys_hi, int64_t* out_idx,
+                        double* out_scores, uint64_t* out_keys, int32_t* dev_status, dal_event_t colsum_ready,
+                        dal_stream_t stream, int64_t* const* out_slot, int32_t* status_mirror,
+                        const ForestStepHooks* plan_hooks) {
   if (d < 1 || ldx < d) return DAL_ERR_SHAPE;
   int rc = check_rerank_args(n, k, cap, level1_passes, ws, ws_bytes);
   if (rc) return rc;
@@ -2331,12 +2361,11 @@ int dw_step_impl(const float* x, const float* xb, const void* fprep, int64_t n, 
   const RerankWs W = rerank_ws(n, k, cap);
   char* base = static_cast<char*>(ws);
   TopkHdr* h1 = reinterpret_cast<TopkHdr*>(base + W.L1.hdr);
-  if (level1_passes == 0) {  // exact level 1: the two calls as they are
-    rc = forest_score_launch(x, xb, fprep, n, d, ldx, inner, leaf, n_trees, depth, lut, density_fixed, DAL_DENSITY_FIXED,
-                             density_err, row_flags, beta, DAL_DESCENDING, votes, scores, keys_lo, keys_hi, hooks,
-                             st);
+  const int form = step_form(sc, n, k, level1_passes);
+  if (form == 0) {  // exact level 1: the two calls as they are
+    rc = launch(hooks);
     if (rc) return rc;
-    rc = dal_dw_select(keys_lo, keys_hi, votes, row_flags, n, k, idx_base, lut, beta, x, d, ldx, norm64, colsum,
+    rc = dal_dw_select(keys_lo, keys_hi, sc.votes, row_flags, n, k, idx_base, sc.lut, beta, x, d, ldx, norm64, colsum,
                        cap, 0, ws, ws_bytes, out_idx, out_scores, out_keys, dev_status, colsum_ready, stream);
     if (rc) return rc;
     if (clean) zero_header(h1, st);  // keep the contract: the header is left zero
@@ -2346,28 +2375,22 @@ int dw_step_impl(const float* x, const float* xb, const void* fprep, int64_t n, 
     DAL_RETURN_IF_LAUNCH_FAILED();
     return DAL_OK;
   }
-  // the score kernel's blocks are the row groups when there are >= 2k of them
-  // (tau then lies within a few ranks of K); smaller pools take one
-  // group_min_kernel pass over finer groups after the score kernel
   uint64_t* gmin = reinterpret_cast<uint64_t*>(base + W.gmin);
-  const int rows_per_block = forest_rows_per_block(x, xb, d, ldx, n_trees, depth);
-  GroupSummary S = make_groups(gmin, n, rows_per_block);
-  const bool in_score = S.ng >= 2 * k;
+  GroupSummary S = make_groups(gmin, n, sc.rows_per_block);
+  const bool in_score = form >= 2;
   if (in_score) {
     hooks.gmin = gmin;
-    hooks.group_blocks = static_cast<int>(S.group_rows / rows_per_block);
+    hooks.group_blocks = static_cast<int>(S.group_rows / sc.rows_per_block);
     hooks.n_groups = S.ng;
   }
-  const bool folded = in_score && hooks.group_blocks > 1;  // atomic max: the buffer starts (and is left) zero
+  const bool folded = form == 3;  // atomic max: the buffer starts (and is left) zero
   hooks.write_flags = false;  // the re-rank below derives its candidates' flags from the stamps
   if (!clean) {
     zero_words(reinterpret_cast<uint32_t*>(h1), kFastHdrWords, st);
     if (folded) zero_words(reinterpret_cast<uint32_t*>(gmin), 2 * S.ng * 2, st);
   }
   if (!select_only) {
-    rc = forest_score_launch(x, xb, fprep, n, d, ldx, inner, leaf, n_trees, depth, lut, density_fixed, DAL_DENSITY_FIXED,
-                             density_err, row_flags, beta, DAL_DESCENDING, votes, scores, keys_lo, keys_hi, hooks,
-                             st);
+    rc = launch(hooks);
     if (rc) return rc;
     if (!in_score) S = launch_group_min(keys_lo, keys_hi, n, gmin, nullptr, 0, st);
   } else if (!in_score) {
@@ -2375,9 +2398,8 @@ int dw_step_impl(const float* x, const float* xb, const void* fprep, int64_t n, 
   }
   if (colsum_ready && hipStreamWaitEvent(st, reinterpret_cast<hipEvent_t>(colsum_ready), 0) != hipSuccess)
     return DAL_ERR_HIP;
-  const DwRerank R{x, static_cast<int>(d), ldx, norm64, colsum, lut, votes, row_flags, beta,
+  const DwRerank R{x, static_cast<int>(d), ldx, norm64, colsum, sc.lut, sc.votes, row_flags, beta,
                    hooks.base_flags, hooks.stamp, hooks.step_id};
-  const int n_lut = n_trees < 64 ? n_trees + 1 : 0;  // LUT held in lanes when it fits a wave
   SortTail tail;
   tail.cap = cap;
   tail.cap_miss = true;
@@ -2396,9 +2418,77 @@ int dw_step_impl(const float* x, const float* xb, const void* fprep, int64_t n, 
   set_regions(tail, h1, cap, G);
   hipLaunchKernelGGL(summary_select_kernel<true>, dim3(static_cast<unsigned>(G)), dim3(kSumThreads), 0, st, keys_hi,
                      n, k, idx_base, S, h1, Rg.idx, cap, AppendRerank{R, Rg.keys, Rg.pay},
-                     n_lut, out_keys, out_idx, out_scores, tail);
+                     sc.n_lut, out_keys, out_idx, out_scores, tail);
   DAL_RETURN_IF_LAUNCH_FAILED();
   return DAL_OK;
+}
+
+int dw_step_impl(const float* x, const float* xb, const void* fprep, int64_t n, int64_t d, int64_t ldx,
+                 const int32_t* inner,
+                 const uint8_t* leaf,
+                 int32_t n_trees, int32_t depth, const double* lut, const int64_t* density_fixed, double density_err,
+                 const uint8_t* row_flags, double beta, int64_t idx_base, const double* norm64, const double* colsum,
+                 int64_t k, int64_t cap, int32_t level1_passes, uint32_t step_flags, void* ws, size_t ws_bytes,
+                 int32_t* votes, double* scores, uint64_t* keys_lo, uint64_t* keys_hi, int64_t* out_idx,
+                 double* out_scores, uint64_t* out_keys, int32_t* dev_status, dal_event_t colsum_ready,
+                 dal_stream_t stream, int64_t* const* out_slot, int32_t* status_mirror,
+                 const ForestStepHooks* plan_hooks) {
+  if (!x || !inner || !leaf || !lut || !density_fixed || !norm64 || !colsum || !ws || !votes || !scores ||
+      !keys_lo || !keys_hi || !out_idx || !out_scores || !dev_status)
+    return DAL_ERR_ARG;
+  if (step_flags & ~static_cast<uint32_t>(DAL_STEP_RESET_STATUS | DAL_STEP_WS_CLEAN | DAL_STEP_KEEP_GROUPS |
+                                         DAL_STEP_SELECT_ONLY))
+    return DAL_ERR_ARG;
+  if (d < 1 || ldx < d) return DAL_ERR_SHAPE;
+  // both binary score kernels fold; the LUT is held in lanes when it fits a wave
+  const StepScore sc{forest_rows_per_block(x, xb, d, ldx, n_trees, depth), true, lut, votes,
+                     n_trees < 64 ? n_trees + 1 : 0};
+  const hipStream_t st = as_stream(stream);
+  auto launch = [&](const ForestStepHooks& hooks) {
+    return forest_score_launch(x, xb, fprep, n, d, ldx, inner, leaf, n_trees, depth, lut, density_fixed,
+                               DAL_DENSITY_FIXED, density_err, row_flags, beta, DAL_DESCENDING, votes, scores, keys_lo,
+                               keys_hi, hooks, st);
+  };
+  return dw_step_core(sc, launch, x, n, d, ldx, row_flags, beta, idx_base, norm64, colsum, k, cap, level1_passes,
+                      step_flags, ws, ws_bytes, keys_lo, keys_hi, out_idx, out_scores, out_keys, dev_status,
+                      colsum_ready, stream, out_slot, status_mirror, plan_hooks);
+}
+
+// dal_dw_step_multiclass (and the plan's captured step): the C-class score
+// kernel under the same step.  The re-rank's "LUT" is the per-row entropy the
+// kernel writes and its "vote" the row's own index (dal_dw_select's reading of
+// the C-class score), so nothing is held in lanes (n_lut = 0).  The blocked
+// kernel folds; the row-major one takes the group_min_kernel pass.
+static StepScore mc_step_score(bool blocked, const double* entropy, const int32_t* row_index) {
+  return StepScore{kMcStepRows, blocked, entropy, row_index, 0};
+}
+
+// A capacity past the one-block sort has no fast level 1: the step then takes
+// the exact one, whatever level1_passes (in range) asks for.
+static int32_t mc_step_passes(int64_t cap, int32_t level1_passes) {
+  return level1_passes > 0 && level1_passes < kPasses && cap > DAL_SORT_CAP_PAYLOAD ? 0 : level1_passes;
+}
+
+int dw_step_multiclass_impl(const McStepScore& M, const uint8_t* row_flags, int64_t idx_base, const double* norm64,
+                            const double* colsum, int64_t k, int64_t cap, int32_t level1_passes,
+                            uint32_t step_flags, void* ws, size_t ws_bytes, double* scores, uint64_t* keys_lo,
+                            uint64_t* keys_hi, int64_t* out_idx, double* out_scores, uint64_t* out_keys,
+                            int32_t* dev_status, dal_event_t colsum_ready, dal_stream_t stream,
+                            int64_t* const* out_slot, int32_t* status_mirror, const ForestStepHooks* plan_hooks) {
+  const bool args_ok = norm64 && colsum && ws && scores && keys_lo && keys_hi && out_idx && out_scores &&
+                       dev_status && !(step_flags & ~static_cast<uint32_t>(DAL_STEP_RESET_STATUS | DAL_STEP_WS_CLEAN));
+  if (const int rc = forest_multiclass_step_check(M, args_ok)) return rc;
+  if (M.n == 0) return DAL_OK;
+  level1_passes = mc_step_passes(cap, level1_passes);
+  const StepScore sc = mc_step_score(
+      forest_multiclass_step_blocked(M.xb, M.d, M.n_trees, M.depth, M.n_classes), M.entropy, M.row_index);
+  const hipStream_t st = as_stream(stream);
+  auto launch = [&](const ForestStepHooks& hooks) {
+    return forest_multiclass_step_launch(M, row_flags, scores, keys_lo, keys_hi, hooks, st);
+  };
+  return dw_step_core(sc, launch, M.x, M.n, M.d, M.ldx, row_flags, M.beta, idx_base, norm64, colsum, k, cap,
+                      level1_passes, step_flags, ws, ws_bytes, keys_lo, keys_hi, out_idx, out_scores, out_keys,
+                      dev_status, colsum_ready, stream, out_slot, status_mirror, plan_hooks);
 }
 
 }  // namespace dal
@@ -2417,6 +2507,37 @@ extern "C" int dal_dw_step(const float* x, const float* xb, const void* fprep, i
                       idx_base, norm64, colsum, k, cap, level1_passes, step_flags, ws, ws_bytes, votes, scores,
                       keys_lo, keys_hi, out_idx, out_scores, out_keys, dev_status, colsum_ready, stream, nullptr,
                       nullptr, nullptr);
+}
+
+extern "C" int dal_dw_step_multiclass(const float* x, const float* xb, const void* fprep, int64_t n, int64_t d,
+                                      int64_t ldx, const int32_t* inner, const uint8_t* leaf, int32_t n_trees,
+                                      int32_t depth, int32_t n_classes, const double* lut,
+                                      const int64_t* density_fixed, double density_err, const uint8_t* row_flags,
+                                      double beta, int64_t idx_base, const double* norm64, const double* colsum,
+                                      int64_t k, int64_t cap, int32_t level1_passes, uint32_t step_flags, void* ws,
+                                      size_t ws_bytes, uint8_t* counts, uint8_t* pred, double* entropy,
+                                      int32_t* row_index, double* scores, uint64_t* keys_lo, uint64_t* keys_hi,
+                                      int64_t* out_idx, double* out_scores, uint64_t* out_keys, int32_t* dev_status,
+                                      dal_event_t colsum_ready, dal_stream_t stream) {
+  const McStepScore M{x, xb, fprep, n, d, ldx, inner, leaf, n_trees, depth, n_classes, lut, density_fixed,
+                      density_err, beta, counts, pred, entropy, row_index};
+  return dw_step_multiclass_impl(M, row_flags, idx_base, norm64, colsum, k, cap, level1_passes, step_flags, ws,
+                                 ws_bytes, scores, keys_lo, keys_hi, out_idx, out_scores, out_keys, dev_status,
+                                 colsum_ready, stream, nullptr, nullptr, nullptr);
+}
+
+// Pure host code: the branch dal_dw_step_multiclass takes for this shape (the
+// values of step_form), or the negative status its shape checks give.
+// blocked: the call is given a blocked copy (and a prepared forest).
+extern "C" int dal_dw_step_multiclass_form(int64_t n, int64_t d, int32_t n_trees, int32_t depth, int32_t n_classes,
+                                           int64_t k, int64_t cap, int32_t level1_passes, int blocked) {
+  // (the score entries' checks on a contiguous pool, then the selection's without its workspace)
+  if (const int rc = forest_multiclass_step_shape_check(n, d, n_trees, depth, n_classes)) return rc;
+  if (n == 0) return DAL_OK;
+  level1_passes = mc_step_passes(cap, level1_passes);
+  if (const int rc = check_rerank_shape(n, k, cap, level1_passes)) return rc;
+  const bool fold = blocked && dal_forest_multiclass_blocked_rows(d, n_trees, depth, n_classes) != 0;
+  return step_form(mc_step_score(fold, nullptr, nullptr), n, k, level1_passes);
 }
 
 extern "C" size_t dal_maxcos_select_workspace_bytes(int64_t n, int64_t k, int64_t cap) {

@@ -122,6 +122,20 @@ SIGNATURES = {
                             c_void_p, c_double, c_void_p, c_double, c_int64, c_void_p, c_void_p, c_int64, c_int64,
                             c_int32, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dal_dw_step_multiclass": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                       c_int32, c_int32, c_int32, c_void_p, c_void_p, c_double, c_void_p, c_double,
+                                       c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, ctypes.c_uint32,
+                                       c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    "dal_dw_step_multiclass_form": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32,
+                                            c_int]),
+    "dal_dw_plan_create_multiclass": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                              c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_double,
+                                              c_void_p, c_void_p, c_double, c_int64, c_void_p, c_void_p, c_int64,
+                                              c_int64, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p]),
     "dal_dw_plan_create": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32,
                                    c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_double, c_int64, c_void_p,
                                    c_void_p, c_int64, c_int64, c_int32, c_void_p, c_size_t, c_void_p, c_void_p,

@@ -193,7 +193,7 @@ class PoolState:
         self.cap_base = None  # initial re-rank capacity override (tests: force the overflow path)
         self.level1_fast = True  # fast top-k level 1 allowed (cleared after an overflow on this pool)
         self.use_graphs = True  # hipGraph replay of warm steps (tests compare with eager steps)
-        self._graphs = {}  # warm-step graphs by (T, depth, k, beta, cap, level-1 passes)
+        self._graphs = {}  # warm-step graphs by (T, depth, k, beta, cap, level-1 passes[, C: a C-class plan])
         self.last_status = 0     # status word read by the last synchronising select
 
     def clear_caches(self):
@@ -811,11 +811,15 @@ def dw_select_local(state: PoolState, flags, votes, keys_lo, keys_hi, lut_dev, k
 
 
 def dw_step_local(state: PoolState, forest: Forest, flags, dens, lut_dev, k: int, beta: float, colsum,
-                  colsum_ready=None, cap_scale: int = None, sync: bool = True, xb=None):
+                  colsum_ready=None, cap_scale: int = None, sync: bool = True, xb=None, n_classes=None):
     """dal_dw_step on this pool or shard: votes, scores and interval keys
     of every row, then the exact canonical top-k -- one C call with fused
     launches (the fast level 1; ``xb``: the pool's blocked copy for the score
     kernel).  Same retries as dw_select_local.
+    ``n_classes`` (None: the binary step): dal_dw_step_multiclass over a
+    C-class forest -- ``lut_dev`` is then the multiclass entropy table, ``xb``
+    the copy the C-class rule allowed, and per-class counts ([n, C] uint8)
+    come back in the place of the votes.
     Returns (votes, scores, indices, selected scores); sync=False (the
     multi-GPU path: the caller reads the status word after the merge and
     re-runs with a larger ``cap_scale``) also returns the selected keys."""
@@ -827,7 +831,19 @@ def dw_step_local(state: PoolState, forest: Forest, flags, dens, lut_dev, k: int
     norm64 = state.norms()
     derr = float(density_error(state))
     dev = state.device
-    votes = torch.empty(n, dtype=torch.int32, device=dev)
+    if n_classes is None:
+        votes = torch.empty(n, dtype=torch.int32, device=dev)
+        entry, classes, rows = "dal_dw_step", (), (_ptr(votes),)
+    else:
+        forest.check_classes()
+        if forest.n_trees > DAL_MC_MAX_TREES:
+            raise ValueError(f"a multiclass forest may hold at most {DAL_MC_MAX_TREES} trees, not {forest.n_trees}")
+        votes = torch.empty((n, int(n_classes)), dtype=torch.uint8, device=dev)  # the per-class counts
+        entropy = torch.empty(n, dtype=torch.float64, device=dev)
+        row_index = torch.empty(n, dtype=torch.int32, device=dev)
+        # (pred is not kept: a Selection carries the counts)
+        entry, classes, rows = "dal_dw_step_multiclass", (int(n_classes),), (_ptr(votes), 0, _ptr(entropy),
+                                                                              _ptr(row_index))
     scores = torch.empty(n, dtype=torch.float64, device=dev)
     keys_lo = torch.empty(n, dtype=torch.int64, device=dev)
     keys_hi = torch.empty(n, dtype=torch.int64, device=dev)
@@ -848,11 +864,11 @@ def dw_step_local(state: PoolState, forest: Forest, flags, dens, lut_dev, k: int
         out_scores = torch.empty(k, dtype=torch.float64, device=dev)
         out_keys = None if sync else torch.empty(k, dtype=torch.int64, device=dev)
         try:
-            call("dal_dw_step", _ptr(state.x), 0 if xb is None else _ptr(xb), _fprep(forest, state, xb), n,
+            call(entry, _ptr(state.x), 0 if xb is None else _ptr(xb), _fprep(forest, state, xb), n,
                  state.d, state.d, _ptr(inner),
-                 _ptr(leaf), forest.n_trees, forest.depth, _ptr(lut_dev), _ptr(dens), derr, _ptr(flags),
+                 _ptr(leaf), forest.n_trees, forest.depth, *classes, _ptr(lut_dev), _ptr(dens), derr, _ptr(flags),
                  float(beta), state.row_base,
-                 _ptr(norm64), _ptr(colsum), k, cap, passes, DAL_STEP_WS_CLEAN, wsp, wsb, _ptr(votes),
+                 _ptr(norm64), _ptr(colsum), k, cap, passes, DAL_STEP_WS_CLEAN, wsp, wsb, *rows,
                  _ptr(scores), _ptr(keys_lo), _ptr(keys_hi), _ptr(out_idx), _ptr(out_scores),
                  0 if out_keys is None else _ptr(out_keys), _ptr(state.status),
                  0 if colsum_ready is None else colsum_ready.cuda_event, _stream(dev))
@@ -955,7 +971,12 @@ def multiclass_density_step(state: PoolState, unlabeled_idx, forest: Forest, k: 
     its fp64 re-rank forms entropy[i] * (canonical density)^beta.  A warm
     step (the density cached or handed in) scores over the pool's blocked
     copy (dal_forest_score_multiclass_dw_blocked, same bits; density_step's
-    rule), built by the first warm step.  No fused step or graph.
+    rule), built by the first warm step.  As in density_step, a warm step on
+    the whole pool replays a cached plan (WarmStepGraph with n_classes:
+    dal_dw_plan_create_multiclass) when ``use_graphs`` is set and no events
+    are requested; a cold step, a handed-in density or a shard is one
+    dal_dw_step_multiclass call (dw_step_local's clean workspace), and the
+    unfused pair stays for the per-kernel timing path.
     mode "separable": the exact O(N*D) density, canonical scores for every
     row and a plain top-k, on the row-major pool.
     The Selection carries ``counts`` ([U, C] uint8); ``votes`` is None."""
@@ -974,6 +995,10 @@ def multiclass_density_step(state: PoolState, unlabeled_idx, forest: Forest, k: 
         sel_scores = scores[idx - state.row_base]
         state.check_status()
         return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, counts=(counts, loc))
+    C = int(forest.n_classes)
+    if (state.use_graphs and density_fixed is None and state._density is not None and state._colsum is not None
+            and state.row_base == 0 and state.n == state.n_total and state.events_off()):
+        return _density_step_graph(state, unl, forest, min(int(k), int(unl.shape[0])), beta, n_classes=C)
     # warm (density cached): the score kernel reads the pool's blocked copy
     # (built by the first warm step); the cold step keeps the row-major kernel
     xb = (state.blocked_pool(forest, multiclass=True)
@@ -983,6 +1008,14 @@ def multiclass_density_step(state: PoolState, unlabeled_idx, forest: Forest, k: 
     flags, unl, n_cand = state.row_flags(unl)
     kk = min(int(k), n_cand)
     loc = state.local_positions(unl)
+    if state.forest_events is None and state.select_events is None:
+        # one C call, fused launches, for a cold step, a handed-in density or a
+        # shard (the per-kernel timing path below keeps K2 / K3 apart)
+        counts, scores, idx, sel_scores = dw_step_local(
+            state, forest, flags, dens, device_multiclass_lut("entropy", forest.n_trees, state.device), kk, beta,
+            state.colsum(), colsum_ready, xb=xb, n_classes=C)
+        state.check_status(state.last_status)
+        return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, counts=(counts, loc))
     counts, _, entropy, row_index, scores, keys_lo, keys_hi = forest_score_multiclass_dw(
         state, forest, flags, dens, DAL_DENSITY_FIXED, density_err=density_error(state), beta=beta, want_hi=True,
         xb=xb)
@@ -1077,10 +1110,16 @@ class WarmStepGraph:
     buffers.  Per step ONE C call (dal_dw_plan_run) rebuilds the row flags
     from the pool's base flags and the unlabeled list, replays the graph,
     copies the selection out and reads the status word.  A different forest
-    is copied into the static heap arrays first."""
+    is copied into the static heap arrays first.
+
+    ``n_classes`` (None: the binary step) makes it the C-class plan
+    (dal_dw_plan_create_multiclass: dal_dw_step_multiclass captured the same
+    way): per-class ``counts`` [n, C] in the place of ``votes``, the per-row
+    entropy and row index the re-rank reads, and the C-class blocked rule for
+    the pool's blocked copy."""
 
     def __init__(self, state: PoolState, forest: Forest, k: int, beta: float, cap: int, passes: int,
-                 colsum=None, packed=None):
+                 colsum=None, packed=None, n_classes=None):
         """colsum: the canonical column sum to re-rank against (default the
         pool's own; a shard passes the global one).  packed: an int64 [3k+1]
         row receiving (selected keys | indices | score bits | status) -- the
@@ -1091,14 +1130,28 @@ class WarmStepGraph:
         dev = state.device
         n = state.n
         self.state, self.k, self.cap, self.passes = state, int(k), int(cap), int(passes)
+        self.n_classes = None if n_classes is None else int(n_classes)
+        multi = self.n_classes is not None
         forest.check_features(state.d)
+        if multi:
+            forest.check_classes()
+            if forest.n_trees > DAL_MC_MAX_TREES:
+                raise ValueError(
+                    f"a multiclass forest may hold at most {DAL_MC_MAX_TREES} trees, not {forest.n_trees}")
         inner, leaf = forest.device(dev)
         self.inner, self.leaf = inner.clone(), leaf.clone()
         self.forest_ref = forest
         self.n_trees, self.depth = forest.n_trees, forest.depth
         self.flags = state.flags.clone()
-        self.lut = device_lut("entropy", forest.n_trees, dev)
-        self.votes = torch.empty(n, dtype=torch.int32, device=dev)
+        if multi:
+            self.lut = device_multiclass_lut("entropy", forest.n_trees, dev)
+            self.votes = None
+            self.counts = torch.empty((n, self.n_classes), dtype=torch.uint8, device=dev)
+            self.entropy = torch.empty(n, dtype=torch.float64, device=dev)
+            self.row_index = torch.empty(n, dtype=torch.int32, device=dev)
+        else:
+            self.lut = device_lut("entropy", forest.n_trees, dev)
+            self.votes = torch.empty(n, dtype=torch.int32, device=dev)
         self.scores = torch.empty(n, dtype=torch.float64, device=dev)
         self.keys_lo = torch.empty(n, dtype=torch.int64, device=dev)
         self.keys_hi = torch.empty(n, dtype=torch.int64, device=dev)
@@ -1119,7 +1172,8 @@ class WarmStepGraph:
         lib = _lib.load()
         self.wsb = int(lib.dal_dw_step_workspace_bytes(n, k, cap))
         self.ws, self.wsp = workspace(self.wsb, dev)
-        xb = state.blocked_pool(forest)  # the score kernel reads the pool's blocked copy when it applies
+        # the score kernel reads the pool's blocked copy when it applies
+        xb = state.blocked_pool(forest, multiclass=True) if multi else state.blocked_pool(forest)
         # the forest prepared for the blocked kernel, in a static buffer the
         # plan reads at its captured address (re-prepared when the forest changes)
         self.fprep = None
@@ -1132,13 +1186,17 @@ class WarmStepGraph:
                       state.flags, state.x, xb)
         dens, colsum, norm64 = self._keep[:3]
         plan = ctypes.c_void_p()
-        call("dal_dw_plan_create", _ptr(state.x), 0 if xb is None else _ptr(xb),
-             0 if self.fprep is None else _ptr(self.fprep), n, state.d, state.d,
-             _ptr(self.inner), _ptr(self.leaf),
-             self.n_trees, self.depth, _ptr(self.lut), _ptr(dens), float(density_error(state)), _ptr(state.flags),
-             _ptr(self.flags), float(beta), state.row_base, _ptr(norm64), _ptr(colsum), k, cap, passes, self.wsp,
-             self.wsb, _ptr(self.votes), _ptr(self.scores), _ptr(self.keys_lo), _ptr(self.keys_hi),
-             _ptr(self.out_pair), _ptr(self.out_keys), _ptr(status), _stream(dev), ctypes.byref(plan))
+        head = (_ptr(state.x), 0 if xb is None else _ptr(xb), 0 if self.fprep is None else _ptr(self.fprep), n,
+                state.d, state.d, _ptr(self.inner), _ptr(self.leaf), self.n_trees, self.depth)
+        step = (_ptr(self.lut), _ptr(dens), float(density_error(state)), _ptr(state.flags), _ptr(self.flags),
+                float(beta), state.row_base, _ptr(norm64), _ptr(colsum), k, cap, passes, self.wsp, self.wsb)
+        tail = (_ptr(self.scores), _ptr(self.keys_lo), _ptr(self.keys_hi), _ptr(self.out_pair), _ptr(self.out_keys),
+                _ptr(status), _stream(dev), ctypes.byref(plan))
+        if multi:  # (pred is not kept: a Selection carries the counts)
+            call("dal_dw_plan_create_multiclass", *head, self.n_classes, *step, _ptr(self.counts), 0,
+                 _ptr(self.entropy), _ptr(self.row_index), *tail)
+        else:
+            call("dal_dw_plan_create", *head, *step, _ptr(self.votes), *tail)
         self.plan = plan
         self._status = ctypes.c_int32()
         self._status_ref = ctypes.byref(self._status)
@@ -1153,11 +1211,12 @@ class WarmStepGraph:
                  _ptr(self.fprep), int(self.fprep.shape[0]), _stream(self.state.device))
 
     def run(self, forest: Forest, unl):
-        """Refresh the inputs, replay, read the status: returns (votes,
-        scores, selected indices, selected scores, status).  votes / scores
-        are the plan's buffers, valid until the next replay (copy-on-write:
-        the previous step's Selection is materialised before they are
-        reused); the selection lands in fresh tensors."""
+        """Refresh the inputs, replay, read the status: returns (votes --
+        the C-class plan: counts --, scores, selected indices, selected
+        scores, status).  votes / scores are the plan's buffers, valid until
+        the next replay (copy-on-write: the previous step's Selection is
+        materialised before they are reused); the selection lands in fresh
+        tensors."""
         torch = _torch()
         prev = self._last() if self._last is not None else None
         if prev is not None:
@@ -1165,6 +1224,8 @@ class WarmStepGraph:
         dev = self.state.device
         if forest is not self.forest_ref:
             forest.check_features(self.state.d)
+            if self.n_classes is not None:
+                forest.check_classes()
             inner, leaf = forest.device(dev)
             self.inner.copy_(inner)
             self.leaf.copy_(leaf)
@@ -1176,7 +1237,7 @@ class WarmStepGraph:
                        _raw_stream(dev))
         if rc:
             _lib.check(rc, "dal_dw_plan_run")
-        return self.votes, self.scores, idx, sc, self._status.value
+        return (self.votes if self.n_classes is None else self.counts), self.scores, idx, sc, self._status.value
 
     def launch(self, forest: Forest, unl):
         """Refresh and replay on the current stream WITHOUT waiting (the
@@ -1191,10 +1252,11 @@ class WarmStepGraph:
         call("dal_dw_plan_launch", self.plan, unl.data_ptr(), int(unl.shape[0]), _raw_stream(self.state.device))
 
 
-def _density_step_graph(state: PoolState, unl, forest: Forest, kk: int, beta: float) -> Selection:
+def _density_step_graph(state: PoolState, unl, forest: Forest, kk: int, beta: float, n_classes=None) -> Selection:
     """Warm density step through a cached WarmStepGraph (same selection as
     the eager path; a level-1 or re-rank capacity overflow rebuilds the plan
-    with the exact level 1 / a larger capacity and replays)."""
+    with the exact level 1 / a larger capacity and replays).  ``n_classes``:
+    the C-class step (its plans are cached beside the binary ones, by C)."""
     n = state.n
     loc = state.local_positions(unl)
     while True:
@@ -1202,9 +1264,11 @@ def _density_step_graph(state: PoolState, unl, forest: Forest, kk: int, beta: fl
         cap = int(min(n, base * state.cap_scale))
         passes = level1_passes(state, n, kk, cap)
         key = (forest.n_trees, forest.depth, kk, float(beta), cap, passes)
+        if n_classes is not None:
+            key += (int(n_classes),)
         g = state._graphs.get(key)
         if g is None:
-            g = state._graphs[key] = WarmStepGraph(state, forest, kk, beta, cap, passes)
+            g = state._graphs[key] = WarmStepGraph(state, forest, kk, beta, cap, passes, n_classes=n_classes)
         try:
             votes, scores, idx, sel_scores, st = g.run(forest, unl)
         except _lib.DalError:
@@ -1221,7 +1285,10 @@ def _density_step_graph(state: PoolState, unl, forest: Forest, kk: int, beta: fl
             state.cap_scale *= 4
             continue
         state.check_status(st)
-        sel = Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, votes=(votes, loc))
+        if n_classes is None:
+            sel = Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, votes=(votes, loc))
+        else:
+            sel = Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, counts=(votes, loc))
         g._last = weakref.ref(sel)
         return sel
 

@@ -371,8 +371,10 @@ int dal_forest_score_multiclass_dw(const float* x, int64_t n, int64_t d, int64_t
  * class; rows past n in the last tile are never written.  A stale fprep
  * (another forest) gives that forest's votes.  Every inner node's feature must
  * lie in [0, d): for an invalid forest the outputs are unspecified (the
- * prepared forest clamps, the row-major kernel does not).  Selection stays
- * dal_topk / dal_dw_select; there are no step hooks, group minima or plan. */
+ * prepared forest clamps, the row-major kernel does not).  Selection is
+ * dal_topk / dal_dw_select after these entries; the fused step with the group
+ * minima folded by the score kernel, and its plan, are dal_dw_step_multiclass
+ * and dal_dw_plan_create_multiclass below. */
 int dal_forest_multiclass_blocked_rows(int64_t d, int32_t n_trees, int32_t depth, int32_t n_classes);
 int dal_forest_score_multiclass_blocked(const float* x, const float* xb, const void* fprep, int64_t n, int64_t d,
                                         int64_t ldx, const int32_t* inner, const uint8_t* leaf, int32_t n_trees,
@@ -403,7 +405,8 @@ int dal_topk(const uint64_t* keys, int64_t n, int64_t k, int64_t idx_base, void*
  * first k point-interval rows == K, in row order -- a superset of the
  * canonical top-k (at most ``cap`` of them).  Each candidate's canonical fp64
  * score  lut[v] * (sum_f (x_if / norm64[i]) * colsum[f])^beta  (sequential,
- * no FMA) is recomputed and an exact top-k over the candidates returns the k
+ * no FMA; beta == 2 is one multiply, the correctly rounded square, any other
+ * beta != 1 the device pow, good to an ulp) is recomputed and an exact top-k over the candidates returns the k
  * best by (score desc, NaN last, index asc): bit-exact with the fp64 oracle.
  * out_scores are canonical fp64 scores, out_keys (nullable) their keys.  More
  * than ``cap`` candidates sets DAL_FLAG_CAND_OVERFLOW (retry with a larger cap).
@@ -483,6 +486,47 @@ int dal_dw_step(const float* x, const float* xb, const void* fprep, int64_t n, i
                 uint64_t* keys_lo, uint64_t* keys_hi, int64_t* out_idx, double* out_scores,
                 uint64_t* out_keys, int32_t* dev_status, dal_event_t colsum_ready, dal_stream_t stream);
 
+/* ---- one density-weighted iteration over a C-class forest in one call ----
+ * New symbols only: dal_abi_version() stays 10; a caller probes for the
+ * feature with dal_dw_step_multiclass_form (absent from older libraries).
+ * dal_dw_step_multiclass is equivalent to dal_forest_score_multiclass_dw_blocked
+ * (x, xb, fprep, ..., lut, density_fixed, DAL_DENSITY_FIXED, density_err,
+ * row_flags, beta, counts, pred, entropy, row_index, scores, keys_lo, keys_hi)
+ * followed by dal_dw_select(keys_lo, keys_hi, row_index, row_flags, n, k,
+ * idx_base, entropy, beta, x, d, ldx, norm64, colsum, cap, level1_passes, ...)
+ * -- same outputs, same bits -- as dal_dw_step is to the binary pair: with the
+ * fast level 1 the blocked C-class kernel folds each tile's minimum keys into
+ * the row groups itself when the pool has at least 2k tiles (else, and with the
+ * row-major kernel, one group-minimum pass follows the score kernel), and ONE
+ * more launch derives tau, appends the candidates with their canonical scores
+ * and sorts them.  lut is multiclass_lut("entropy", T): T + 1 doubles.
+ * step_flags: DAL_STEP_RESET_STATUS and DAL_STEP_WS_CLEAN as for dal_dw_step;
+ * the two measurement flags are DAL_ERR_ARG.  counts and pred are nullable.
+ * xb (nullable) and fprep: as dal_forest_score_multiclass_dw_blocked's, with
+ * every check of that entry (2 <= n_classes <= 32, n_trees <= 255, n <=
+ * INT32_MAX, 16-B aligned xb, fprep present and aligned where
+ * dal_forest_multiclass_blocked_rows gives 64); n == 0 returns DAL_OK before the
+ * selection's checks.  A capacity above DAL_SORT_CAP_PAYLOAD takes the exact
+ * level 1 whatever level1_passes (0..5) says.  Workspace:
+ * dal_dw_step_workspace_bytes.
+ * dal_dw_step_multiclass_form is pure host code: the branch the call takes for
+ * a shape -- 0 exact level 1; 1 fast level 1, group-minimum pass; 2 fast,
+ * folded by the score kernel with plain stores (one tile per group); 3 fast,
+ * folded with atomic maxima (several tiles per group) -- or the negative status
+ * the entry's shape checks return.  blocked: non-zero when the call is given xb
+ * (and fprep). */
+int dal_dw_step_multiclass(const float* x, const float* xb, const void* fprep, int64_t n, int64_t d, int64_t ldx,
+                           const int32_t* inner, const uint8_t* leaf, int32_t n_trees, int32_t depth,
+                           int32_t n_classes, const double* lut, const int64_t* density_fixed, double density_err,
+                           const uint8_t* row_flags, double beta, int64_t idx_base, const double* norm64,
+                           const double* colsum, int64_t k, int64_t cap, int32_t level1_passes, uint32_t step_flags,
+                           void* ws, size_t ws_bytes, uint8_t* counts, uint8_t* pred, double* entropy,
+                           int32_t* row_index, double* scores, uint64_t* keys_lo, uint64_t* keys_hi,
+                           int64_t* out_idx, double* out_scores, uint64_t* out_keys, int32_t* dev_status,
+                           dal_event_t colsum_ready, dal_stream_t stream);
+int dal_dw_step_multiclass_form(int64_t n, int64_t d, int32_t n_trees, int32_t depth, int32_t n_classes, int64_t k,
+                                int64_t cap, int32_t level1_passes, int blocked);
+
 /* ---- warm-step plan: a replayed dal_dw_step with a one-call host side -----
  * dal_dw_plan_create captures dal_dw_step (DAL_STEP_RESET_STATUS |
  * DAL_STEP_WS_CLEAN, no colsum event) over the given caller-owned buffers as a
@@ -514,6 +558,21 @@ int dal_dw_plan_create(const float* x, const float* xb, const void* fprep, int64
                        size_t ws_bytes, int32_t* votes, double* scores, uint64_t* keys_lo, uint64_t* keys_hi,
                        int64_t* out_pair, uint64_t* out_keys, int32_t* dev_status, dal_stream_t stream,
                        dal_dw_plan_t** plan);
+/* The C-class plan: dal_dw_step_multiclass captured the same way (the same
+ * mark kernel, stamps, host-mapped slot and status word).  dal_dw_plan_create's
+ * arguments with n_classes after depth and counts, pred (both nullable),
+ * entropy, row_index in the place of votes; lut is multiclass_lut("entropy", T).
+ * dal_dw_plan_run, dal_dw_plan_launch and dal_dw_plan_destroy serve it
+ * unchanged.  A new symbol: dal_abi_version() stays 10. */
+int dal_dw_plan_create_multiclass(const float* x, const float* xb, const void* fprep, int64_t n, int64_t d,
+                                  int64_t ldx, const int32_t* inner, const uint8_t* leaf, int32_t n_trees,
+                                  int32_t depth, int32_t n_classes, const double* lut, const int64_t* density_fixed,
+                                  double density_err, const uint8_t* base_flags, uint8_t* flags, double beta,
+                                  int64_t idx_base, const double* norm64, const double* colsum, int64_t k,
+                                  int64_t cap, int32_t level1_passes, void* ws, size_t ws_bytes, uint8_t* counts,
+                                  uint8_t* pred, double* entropy, int32_t* row_index, double* scores,
+                                  uint64_t* keys_lo, uint64_t* keys_hi, int64_t* out_pair, uint64_t* out_keys,
+                                  int32_t* dev_status, dal_stream_t stream, dal_dw_plan_t** plan);
 int dal_dw_plan_run(dal_dw_plan_t* plan, const int64_t* unl, int64_t n_unl, int64_t* out_idx,
                     double* out_scores, int32_t* status, dal_stream_t stream);
 /* The plan's replay WITHOUT the host wait (ABI v5): refreshes the row marks,
