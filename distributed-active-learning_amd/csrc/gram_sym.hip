@@ -88,11 +88,27 @@
 // (lookahead_tiles() in gram_schedule.hpp), so that each wave of a SIMD runs
 // its scalar work under its partner's MFMAs.  The schedule, every chain and
 // every fold are what they were: the bits do not change.
+//
+// The int8 form (round 13; gram_i8.hpp, dal_gram_rowsum_sym_i8_skip +
+// dal_gram_sym_residual_i8: pools of KS-128 slices above the contiguous
+// limit).  The step of rounds 5 and 7 once more, with integers: H = 32 a + (H -
+// 32 a), a = clamp(rint(H / 32), -127, 127) an int8.  The MFMAs form only the
+// row sums of <a_i, a_j> over the taken pairs -- v_mfma_i32_16x16x64_i8, the
+// cycles of the fp16 instruction at twice the K, so a 128-feature slice of a
+// pair is one pass of 512 MFMAs per wave instead of two -- and the closed
+// form above, fed h' = 32 a and l' = (H - h') + L where it decodes (H, L),
+// adds everything else.  int32 chains are exact: the MFMA part of the density
+// is one integer whatever the grid, the column split or the GPU count.
+// gram_i8sym_kernel is the wide form's body (gram_csym_body.inc) on the int8
+// operand (dal_quant_i8): the same stages, swizzle, DMA pieces, B reads,
+// look-ahead, claim and flush, byte for byte.
 #include <stdlib.h>
 
 #include <mutex>
+#include <type_traits>
 
 #include "common.hpp"
+#include "gram_i8.hpp"
 #include "gram_schedule.hpp"
 
 namespace dal {
@@ -101,6 +117,7 @@ namespace {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 #define AS3 __attribute__((address_space(3)))
 
 constexpr int kSB = 512;       // super block rows
@@ -118,8 +135,8 @@ __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) {
 // (ROCm 7; the sum came out as a + a).  The s_nop covers the wait states
 // between a VALU write of an operand, or an earlier swap, and the swap, which
 // the compiler does not track through the asm.
-template <bool kRows32>
-__device__ __forceinline__ float swap_add(float a, float b) {
+template <bool kRows32, typename T>
+__device__ __forceinline__ T swap_add(T a, T b) {
   if constexpr (kRows32)
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
   else
@@ -166,22 +183,28 @@ __device__ __forceinline__ unsigned fresh_lane() {
 #ifndef DAL_GRAM_KS32_OCC
 #define DAL_GRAM_KS32_OCC 5  // KS 32: 4-wave blocks per CU (3: 16 KiB stages; >= 4: 8 KiB stages. Config 3: 2 -> 3 -> 4 blocks 3.944 -> 3.827 -> 3.745 ms; row sums only (94 VGPRs): 4 -> 5 blocks 3.430 -> 3.391 ms)
 #endif
-template <int KS, int W = 4, int HVS = W / 4>
+// I8 (the wide form only): the operands are the int8 quantisation a(H) of the
+// split operand's H runs (gram_i8.hpp), [rows][d_pad] bytes in feature order;
+// the kernel forms sum_j <a_i, a_j> in int32 by v_mfma_i32_16x16x64_i8 -- a
+// whole 128-feature slice per pass of 512 MFMAs, where the fp16 form takes
+// two.  Offsets stay in 2-byte units (ldh = d_pad / 2).
+template <int KS, int W = 4, int HVS = W / 4, bool I8F = false>
 struct Cfg {
+  static constexpr bool I8 = I8F;
   static constexpr int WAVES = W;                   // 4: one super block per block; 8: two (P, P + 2) or four
   static constexpr int HALVES = HVS;                // super blocks per block
   // the wide form: 8 waves hold four super blocks (P, P + 2, P + 4, P + 6), 256
   // rows per wave, over sub-slices of half the slice's features -- the same
   // A registers as 128 rows x KS features, twice the rows per staged B byte
   static constexpr bool WIDE = HVS == 4;
-  static constexpr int KW = WIDE ? KS / 2 : KS;     // features of the resident A fragments and of a staged row
+  static constexpr int KW = WIDE && !I8 ? KS / 2 : KS;  // features of the resident A fragments, of a staged row
   static constexpr int NSUB = KS / KW;              // sub-slices per slice
   static constexpr int WPS = W / HVS;               // waves per super block: 4, or 2
   static constexpr int RPW = kSB / WPS;             // rows per wave: 128, or 256
   static constexpr int NT = 64 * W;                 // threads
-  static constexpr int ROWB = KW * 2;               // bytes per staged operand row of a sub-slice (its H run)
+  static constexpr int ROWB = KW * (I8 ? 1 : 2);    // bytes per staged operand row of a sub-slice (its H run)
   // halves from the launch's first slice to sub-slice q: the operand keeps H run | L run per KS-slice
-  static constexpr int sub_off(int q) { return (q / NSUB) * 2 * KS + (q % NSUB) * KW; }
+  static constexpr int sub_off(int q) { return I8 ? q * KS / 2 : (q / NSUB) * 2 * KS + (q % NSUB) * KW; }
   static constexpr int SLOTS = ROWB / 16;           // 16-B slots per row: 4 / 8 / 16
   // three 4-wave blocks per CU at KS 64 (OCC3): 16 KiB stages so three fit the LDS
   static constexpr int OCC = W == 8 ? (KS == 64 ? DAL_GRAM_W8_OCC64 : 1)
@@ -212,14 +235,15 @@ struct Cfg {
   static constexpr int PIECES = STAGE / (W * 1024);  // 1-KiB DMA pieces per wave per stage
   static constexpr int RT = RPW / 16;               // 16-row tiles per wave
   static constexpr int LG = 4;
-  static constexpr int NKS = KW / 32;               // k-steps of v_mfma_f32_16x16x32_f16 per column tile
+  // k-steps of v_mfma_f32_16x16x32_f16 (int8: v_mfma_i32_16x16x64_i8) per column tile
+  static constexpr int NKS = KW / (I8 ? 64 : 32);
   static constexpr int NCT = SC / 16;               // column tiles per stage
   // Row-sum chains per row tile.  KS 128: one chain per 64-feature half of the
   // slice (k-steps 2h, 2h + 1 of every column tile, tiles in column order),
   // each folded on its own -- the 4-wave form keeps both in registers, the wide
   // form meets them as its two sub-slices: every KS-128 form sums the same
   // products in the same order, so their bits agree.
-  static constexpr int NCH = KW == 128 ? 2 : 1;
+  static constexpr int NCH = KW == 128 && !I8 ? 2 : 1;  // (int8: one exact int32 chain)
   // products summed by one row-chain element between two folds (the FOLD
   // columns' tiles, KW / NCH products per tile: 512 at KS 32, 1,024 at KS 64
   // and 128)
@@ -232,8 +256,37 @@ struct Cfg {
   static_assert(SPF >= 1 && SPP % SPF == 0 && PIECES >= 1 && NKS >= 1, "bad slice");
   static_assert(W == 4 || (W == 8 && KS >= 64), "several super blocks per block: KS >= 64 only");
   static_assert(!WIDE || (W == 8 && KS == 128), "the wide form: 8 waves at KS 128");
-  static_assert(NKS % NCH == 0 && KW / NCH == 64 / (KS == 32 ? 2 : 1), "a chain is 64 features of every tile (KS 32: 32)");
-  static_assert(CHAIN <= CHARGED, "row chain longer than the density bound charges");
+  static_assert(I8 || (NKS % NCH == 0 && KW / NCH == 64 / (KS == 32 ? 2 : 1)),
+                "a chain is 64 features of every tile (KS 32: 32)");
+  static_assert(I8 || CHAIN <= CHARGED, "row chain longer than the density bound charges");
+  static_assert(!I8 || (WIDE && ROWB == 128 && NSUB == 1), "the int8 form: the wide form over whole slices");
+  // int8: |sum_f a_i a_j| < 1.2 * 2^14 per column on unit rows (Cauchy-Schwarz
+  // with |32 a| <= |H| + 16 sqrt(d_pad)), so a chain element's FOLD / 4 columns
+  // stay below 2^21 and a row's 256 below 2^23: no int32 overflow.
+  static_assert(!I8 || FOLD <= 256, "int32 row chains: at most a pair's 256 columns between folds");
+
+  // the chains' registers and the LDS row accumulator.  fp16: fp32 chains folded
+  // to multiples of 2^-32 and added as integers in fp64 (below 2^53: at most
+  // 2^21 columns of at most 2^32 each).  int8: the row sum s is an exact int32
+  // and adds s * 2^18 (gram_i8.hpp); a column may reach 1.2 * 2^32 here, so the
+  // accumulator is an int64 -- exact for any pool the int64 density itself holds.
+  using acc4 = typename std::conditional<I8, i32x4, f32x4>::type;
+  using sum_t = typename std::conditional<I8, int, float>::type;
+  using racc_t = typename std::conditional<I8, long long, double>::type;
+  static __device__ __forceinline__ acc4 mfma(f16x8 a, f16x8 b, acc4 c) {
+    if constexpr (I8)
+      return __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b), c, 0,
+                                                   0, 0);
+    else
+      return mfma16(a, b, c);
+  }
+  static __device__ __forceinline__ void row_add(racc_t* slot, sum_t x) {
+    if constexpr (I8)
+      atomicAdd(reinterpret_cast<unsigned long long*>(slot),
+                static_cast<unsigned long long>(static_cast<long long>(x) << kI8AccShift));
+    else
+      atomicAdd(slot, static_cast<double>(__builtin_rintf(x * 0x1p8f)));  // units of 2^-24 -> multiples of 2^-32
+  }
 };
 // the wide form's chains are the 4-wave form's (one bound, one set of bits per KS)
 static_assert(Cfg<128, 8, 4>::CHAIN == Cfg<128, 4>::CHAIN, "the KS-128 forms define the same chains");
@@ -259,317 +312,17 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W, HVS>::OCC)) void gram_csym_kern
     int ns_active, int64_t ldh, int slice_off, int n_slices, int chunk_j, int n_chunks,
     unsigned long long* __restrict__ acc_out, int contig, int claim_slot) {
   using C = Cfg<KS, W, HVS>;
-  constexpr int HV = C::HALVES;
-  __shared__ __attribute__((aligned(16))) float4 lds[2 * C::F4];
-  __shared__ double rowacc[HV * kSB];
-  __shared__ int claim_lds[2];  // a claimed unit index, lane 0 -> the block (two words: see claim_begin)
-
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  const int half = wave / C::WPS, wave4 = wave % C::WPS;  // the block's super block of this wave, wave within it
-  // 8-wave block: the two waves of a SIMD (w, w + 4) run the same program in
-  // lockstep; a static priority for one half settles their VALU arbitration
-  // once instead of by age at every segment (MI355X_MICROARCH.md, two waves per
-  // SIMD): waves 4-7 at priority 1, 2M x 256 1266.9 -> 1262.3 ms (waves 0-3:
-  // 1265.0; deferring waves 4-7's last column epilogue of each stage into the
-  // next one, a stagger, 1274.5)
-  if constexpr (W == 8 && DAL_GRAM_PRIO8 != 0) {
-    if (DAL_GRAM_PRIO8 > 0 ? wave >= 4 : wave < 4) __builtin_amdgcn_s_setprio(1);
-  }
-  const int li = lane & 15, lq = lane >> 4;
-  const int G = gridDim.x, g = blockIdx.x;
-  for (int e = tid; e < HV * kSB; e += C::NT) rowacc[e] = 0.0;
-
-  // the pairs this block multiplies and their order: gram_schedule.hpp
-  const GramSchedule<HV> sched(srow0, n_srb, j_lo, j_hi, skip_lo, skip_hi, ns_active, chunk_j, n_chunks, contig, G,
-                               g);
-
-  // DMA source offsets.  Piece q of wave w covers stage rows
-  // Wr + q * RPP + lane / SLOTS (Wr = w * PIECES * RPP, RPP = 64 / SLOTS rows
-  // per piece), slot (lane % SLOTS) ^ swz(row).  Wr (a multiple of
-  // PIECES * RPP), q * RPP and lane / SLOTS occupy disjoint bits, so at 8 and
-  // 16 slots swz(row) = row & SWZ = swz(Wr + lane / SLOTS) ^ swz(q * RPP): the
-  // offset is a per-lane value XOR a per-piece constant (bits 4.. of the byte
-  // offset, below the row part) plus the piece's row offset.  At 4 slots a
-  // piece is 16 rows and swz reads row bits 2-3 only: all in lane / SLOTS, the
-  // per-piece constant is 0.
-  constexpr int RPP = 64 / C::SLOTS;
-  static_assert((RPP & (RPP - 1)) == 0 && (C::PIECES & (C::PIECES - 1)) == 0, "row parts must occupy disjoint bits");
-  const unsigned rowbytes = static_cast<unsigned>(ldh * 2);
-  const unsigned dst0 = __builtin_amdgcn_readfirstlane(
-      static_cast<unsigned>(reinterpret_cast<uintptr_t>((AS3 float4*)(lds + wave * C::PIECES * 64))));
-  // stage h of 256-column block J of feature slice `slice` into LDS buffer
-  // buf.  Inline asm so the compiler does not track the DMA on vmcnt
-  // (block_sync waits for it).
-  auto issue = [&](int buf, int J, int h, int slice) {
-    // (the cursor's values are uniform, but the compiler may hold them in
-    // vector registers when the scalar ones run out: the asm needs scalars)
-    J = __builtin_amdgcn_readfirstlane(J);
-    slice = __builtin_amdgcn_readfirstlane(slice);
-    const char* sbase = reinterpret_cast<const char*>(
-        ucols + (static_cast<int64_t>(J - jcol0) * 256 + h * C::SC) * ldh + slice_off + C::sub_off(slice));
-    const unsigned fl = fresh_lane();
-    const unsigned lrow = fl / C::SLOTS + static_cast<unsigned>(wave * C::PIECES * RPP);
-    const unsigned vlane = lrow * rowbytes + (((fl % C::SLOTS) ^ static_cast<unsigned>(C::swz(lrow))) << 4);
-#pragma unroll
-    for (int q = 0; q < C::PIECES; ++q) {
-      const unsigned dst = dst0 + static_cast<unsigned>(buf * C::STAGE + q * 1024);
-      const unsigned voff = (vlane ^ (static_cast<unsigned>(C::swz(q * RPP)) << 4)) +
-                            static_cast<unsigned>(q * RPP) * rowbytes;
-      lds_dma_x4(voff, dst, sbase);
-    }
-  };
-
-  // resident A fragments: H of rows P*512 + wave4*RPW + rt*16 + (lane & 15)
-  // (P = this wave's super block of the unit), features of k-step c and lane
-  // group lq (the MFMA's N side; the staged column tile is its M side)
-  f16x8 ah[C::RT][C::NKS];
-  auto load_a = [&](int ru, int slice) {
-    const int P = sched.rowP(ru, half);
-    if (HV > 1 && !sched.live(P)) return;  // (this half idles for the unit)
-    const uint16_t* pb = urows + static_cast<int64_t>(P - srow0) * kSB * ldh + slice_off + C::sub_off(slice);
-    const unsigned fl = fresh_lane();
-    const unsigned lrow = static_cast<unsigned>((wave4 * C::RPW + (fl & 15)) * ldh + (fl >> 4) * 8);
-    const unsigned tstep = static_cast<unsigned>(16 * ldh);
-#pragma unroll
-    for (int rt = 0; rt < C::RT; ++rt)
-#pragma unroll
-      for (int c = 0; c < C::NKS; ++c)  // read once per unit: keep the column stages resident in L2
-        ah[rt][c] = __builtin_nontemporal_load(reinterpret_cast<const f16x8*>(pb + lrow + rt * tstep + c * C::LG * 8));
-  };
-  constexpr float kFold = 0x1p8f;  // units of 2^-24 -> multiples of 2^-32
-
-  // B-fragment LDS offsets (float4 units): slot (k + lq) ^ swz(li) of column
-  // row li (a stage's tiles start at multiples of 16 rows: swz(row) = swz(li)),
-  // k = c*LG a multiple of 4; the XOR splits into a lane part (low 2 bits) and
-  // a k part (k ^ (swz(li) & ~3)), so two registers cover every k-step
-  const int b_base = li * C::SLOTS + (lq ^ (C::swz(li) & 3));
-  const int b_swz = C::swz(li) & ~3;
-  auto b_off = [&](int c) { return b_base + ((c * C::LG) ^ b_swz); };
-
-  f32x4 mc[C::NCH][C::RT];
-  // one stage of SC columns; fresh = first stage of a fold group (the chains
-  // restart).  B fragments go through two register sets: k-step i+1's are
-  // read while k-step i's 16 MFMAs issue.
-  // (ct0, ct1: the stage's column tiles of this call -- the wide form runs a
-  // stage in two calls, see the pair loop; the last fragment read by the first
-  // waits in bh for the second)
-  f16x8 bh[2];
-  auto compute = [&](int buf, bool fresh_stage, int ct0 = 0, int ct1 = C::NCT) {
-    auto load_b = [&](int set, int c, int ct) {
-      bh[set] = __builtin_bit_cast(f16x8, lds[buf * C::F4 + ct * 16 * C::SLOTS + b_off(c)]);
-    };
-    if (ct0 == 0) load_b(0, 0, 0);
-#pragma unroll
-    for (int ct = ct0; ct < ct1; ++ct) {
-      __builtin_amdgcn_sched_barrier(0);
-      const bool fresh = fresh_stage && ct == 0;
-#pragma unroll
-      for (int c = 0; c < C::NKS; ++c) {
-        constexpr int KPC = C::NKS / C::NCH;  // k-steps per chain
-        const int ch = c / KPC;
-        const int i = ct * C::NKS + c, cur = i & 1;
-        if (c + 1 < C::NKS)
-          load_b(cur ^ 1, c + 1, ct);
-        else if (ct + 1 < C::NCT)
-          load_b(cur ^ 1, 0, ct + 1);
-        const f32x4 zero = {};
-#pragma unroll
-        for (int rt = 0; rt < C::RT; ++rt)
-          mc[ch][rt] = mfma16(bh[cur], ah[rt][c], (c % KPC == 0 && fresh) ? zero : mc[ch][rt]);
-      }
-      constexpr int NM = C::RT;  // MFMAs per k-step
-#pragma unroll
-      for (int c = 0; c < C::NKS; ++c) {
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // next k-step's B
-        __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);  // MFMA
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  // chains -> LDS row accumulator (exact integer fp64 adds).  The column tile
-  // is the MFMA's M side, so lane (li, lq) holds row li of the row tile at the
-  // tile's columns 4 lq .. 4 lq + 3: the 16 columns of a row are summed in the
-  // lane, (m0 + m1) + (m2 + m3), and over the four lane rows, (x0 + x2) + (x1 +
-  // x3), by a two-step reduce-scatter of eight tiles' sums that leaves each
-  // lane 2 fully summed rows, added by all 64 lanes at distinct LDS addresses
-  // (round 11; before, the rows were the M side and the 16 columns one DPP
-  // row: 30 DPP adds and 60 selects per 8 tiles, 2.5 % of the launch).
-  // Every chain is reduced and rounded on its own, eight row tiles at a time
-  // (the wide form's 16 tiles in two rounds), so a row's integer does not
-  // depend on which form held its chain.
-  auto fold_rows = [&]() {
-#pragma unroll
-    for (int ch = 0; ch < C::NCH; ++ch)
-#pragma unroll
-      for (int t0 = 0; t0 < C::RT; t0 += 8) {
-        float x[8];
-#pragma unroll
-        for (int rt = 0; rt < 8; ++rt) {
-          const f32x4 m = mc[ch][t0 + rt];
-          x[rt] = (m[0] + m[1]) + (m[2] + m[3]);
-        }
-        // lanes 0-31 keep tiles 0-3, lanes 32-63 tiles 4-7; then even rows keep k, odd rows k + 2
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] = swap_add<true>(x[k], x[k + 4]);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) x[k] = swap_add<false>(x[k], x[k + 2]);
-        const int row = wave * C::RPW + (t0 + 2 * (lq & 1) + 4 * (lq >> 1)) * 16 + li;
-        atomicAdd(&rowacc[row], static_cast<double>(__builtin_rintf(x[0] * kFold)));
-        atomicAdd(&rowacc[row + 16], static_cast<double>(__builtin_rintf(x[1] * kFold)));
-      }
-  };
-  auto flush_one = [&](double& slot, int64_t out_row) {
-    const double v = slot;
-    if (v != 0.0) atomicAdd(acc_out + out_row, static_cast<unsigned long long>(static_cast<long long>(v)));
-    slot = 0.0;
-  };
-  auto flush_rows = [&](int ru) {  // rowacc[h * 512 + r] -> row r of the unit's super block h
-    for (int e = tid; e < HV * kSB; e += C::NT) {
-      const int P = sched.rowP(ru, e / kSB);
-      if (sched.live(P)) flush_one(rowacc[e], static_cast<int64_t>(P) * kSB + e % kSB);
-    }
-  };
-  // every barrier waits for this wave's LDS adds and DMA first (hipcc may
-  // omit the lgkmcnt wait at a loop-top barrier after no-return LDS adds)
-  auto block_sync = [&]() {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-  };
-  auto stage_sync = [&]() { block_sync(); };
-
-  // Units.  The block enters unit g; every later one comes from the launch's
-  // counter (claim_slot >= 0: G + the counter's value, so the blocks take the
-  // remaining units in the order they finish -- a block's speed decides its
-  // share, and the launch ends within one unit of the last block), or from
-  // the fixed deal (claim_slot < 0: the contiguous form, no unit beyond the
-  // blocks' first, or no free counter).
-  // A claim is one lane's agent-scope add; its value reaches the block through
-  // claim_lds at the next barrier.  Two words take the claims in turn: between
-  // the block's reads of a word and lane 0's next write to it lies the barrier
-  // of the claim between them.  The counter words are touched by agent-scope
-  // atomics only (no other data is handed between blocks), so no fence is
-  // needed.
-  GramClaimCursor<HV> cur(sched, n_slices * C::NSUB);  // (the wide form's units count sub-slices)
-  const bool dyn = claim_slot >= 0;
-  int claim_par = 0;  // word of claim_lds of the next claim
-  auto claim_begin = [&]() {
-    if (dyn && tid == 0)
-      claim_lds[claim_par] =
-          G + static_cast<int>(__hip_atomic_fetch_add(&g_claim[claim_slot].next, 1u, __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_AGENT));
-  };
-  auto claim_end = [&](int last) {  // last: the unit handed over before; (behind a barrier after claim_begin)
-    const int u = dyn ? __builtin_amdgcn_readfirstlane(claim_lds[claim_par]) : cur.static_next(last);
-    claim_par ^= 1;
-    return u;
-  };
-  // hand the cursor the claim begun before the last barrier; a unit without a
-  // pair is skipped by claiming again
-  auto claim_take = [&]() {
-    while (!cur.claimed(claim_end(cur.v_next))) {
-      claim_begin();
-      if (dyn) block_sync();
-    }
-  };
-  // The last block to leave (every claim of the launch has returned by then)
-  // zeroes the counter: the next launch that uses the slot finds it ready, in
-  // stream order and under graph replay, without a memset.
-  auto leave = [&]() {
-    if (dyn && tid == 0) {
-      const unsigned before =
-          __hip_atomic_fetch_add(&g_claim[claim_slot].done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (before + 1 == static_cast<unsigned>(G)) {
-        __hip_atomic_store(&g_claim[claim_slot].next, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&g_claim[claim_slot].done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-  };
-  if (!cur.claimed(cur.first_unit())) {  // (unit g is empty)
-    claim_begin();
-    if (dyn) block_sync();
-    claim_take();
-  }
-  if (!cur.start()) {
-    leave();
-    return;
-  }
-  issue(0, cur.J, 0, cur.slice);
-  load_a(cur.ru, cur.slice);
-  claim_begin();  // read behind the next barrier, as after every advance() into a new unit
-  int buf = 0;       // LDS stage buffer of the next stage to compute
-  int flushRU = -1;  // row unit whose sums wait in rowacc
-
-  while (true) {
-    // this wave's super block takes J?  (a half whose super block does not idles)
-    const bool act = cur.acts(half);
-
-#pragma unroll
-    for (int s = 0; s < C::SPP; ++s) {
-      stage_sync();
-      if constexpr (C::WIDE && DAL_GRAM_STAGGER > 0) {
-        // The wide form's look-ahead (the claim, peek() and the next stage's
-        // DMA issue: ~165 scalar instructions, ~1,300 cycles when both waves
-        // of a SIMD run them at once behind the barrier with the matrix pipe
-        // empty -- stamped, round 12) sits at two places of the pair: waves
-        // 0-3 run it behind the barrier, their SIMD partners 4-7 behind their
-        // first DAL_GRAM_STAGGER column tiles, so each runs under the other's
-        // MFMAs.  Nothing of it is read by the pair's own MFMAs; the DMA goes
-        // to the buffer every wave left before the barrier, the claim word
-        // read here is next written two claims on, and the rare barriers in
-        // claim_take() are the same in number for every wave.  The flush needs
-        // only the unit noted at the last change of rows and stays behind the
-        // barrier in every wave.
-        if (flushRU >= 0) {
-          flush_rows(flushRU);
-          flushRU = -1;
-        }
-        auto look_ahead = [&]() {
-          if (cur.new_unit) claim_take();
-          cur.peek();
-          if (cur.has_next) issue(buf ^ 1, cur.next_J, 0, cur.next_slice());
-        };
-        const bool lead = lookahead_tiles(wave, W, DAL_GRAM_STAGGER) == 0;  // (gram_schedule.hpp)
-        if (!act) {
-          look_ahead();
-        } else {
-          if (lead) look_ahead();
-          compute(buf, true, 0, DAL_GRAM_STAGGER);
-          if (!lead) look_ahead();
-          compute(buf, true, DAL_GRAM_STAGGER, C::NCT);
-          fold_rows();
-        }
-        buf ^= 1;
-        continue;
-      }
-      if (s == 0) {
-        if (cur.new_unit) claim_take();
-        cur.peek();
-        if (flushRU >= 0) {
-          flush_rows(flushRU);
-          flushRU = -1;
-        }
-      }
-      if (s + 1 < C::SPP) {
-        issue(buf ^ 1, cur.J, s + 1, cur.slice);
-      } else if (cur.has_next) {
-        issue(buf ^ 1, cur.next_J, 0, cur.next_slice());
-      }
-      if (act) {  // (wave-uniform)
-        compute(buf, s % C::SPF == 0);
-        if (s % C::SPF == C::SPF - 1) fold_rows();
-      }
-      buf ^= 1;
-    }
-
-    if (cur.rows_change) flushRU = cur.ru;
-    if (!cur.has_next) break;
-    if (cur.advance()) load_a(cur.ru, cur.slice);
-    if (cur.new_unit) claim_begin();
-  }
-  block_sync();
-  if (flushRU >= 0) flush_rows(flushRU);
-  leave();
+#include "gram_csym_body.inc"
+}
+// The int8 instance of the wide form (Cfg's I8): the same body, schedule, claim
+// and flush protocols; int8 operands, int32 chains, an int64 row accumulator.
+__global__ __launch_bounds__(512, 1) void gram_i8sym_kernel(
+    const uint16_t* __restrict__ urows, int srow0, int n_srb,
+    const uint16_t* __restrict__ ucols, int jcol0, int j_lo, int j_hi, int skip_lo, int skip_hi,
+    int ns_active, int64_t ldh, int slice_off, int n_slices, int chunk_j, int n_chunks,
+    unsigned long long* __restrict__ acc_out, int contig, int claim_slot) {
+  using C = Cfg<128, 8, 4, true>;
+#include "gram_csym_body.inc"
 }
 // ---------------------------------------------------------------------------
 // Residual of the compensation (see the header).  Three launches:
@@ -599,6 +352,9 @@ __global__ __launch_bounds__(64 * W, (Cfg<KS, W, HVS>::OCC)) void gram_csym_kern
 // over the whole walk and reach S^L with one add per block and feature -- S^L
 // is d_pad addresses for the whole pool, and one add per super block and row
 // slice (15,628 per address at config 4) made this kernel 2.85 ms, from 0.55.
+// kI8: the int8 form's terms (h', l') of gram_i8.hpp in place of (h, l) -- an L
+// chunk column also reads its H chunk (ks halves before it) for h - h'.
+template <bool kI8>
 __global__ __launch_bounds__(256) void csym_sigma_kernel(const uint16_t* __restrict__ ops, int64_t ldh, int ks,
                                                          int d_pad, int ns, int qg, long long* __restrict__ sig_u,
                                                          long long* __restrict__ sl) {
@@ -631,9 +387,29 @@ __global__ __launch_bounds__(256) void csym_sigma_kernel(const uint16_t* __restr
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           q[j] = r + j * rstep < re ? base[static_cast<int64_t>(r + j * rstep) * cpr] : uint4{};
+        [[maybe_unused]] uint4 qh[8];  // int8 form, L column: the H chunk of the same features
+        if constexpr (kI8) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            qh[j] = l_col && r + j * rstep < re ? base[static_cast<int64_t>(r + j * rstep) * cpr - hpc] : uint4{};
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const uint32_t w[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
+          if constexpr (kI8) {
+            const uint32_t wh[4] = {qh[j].x, qh[j].y, qh[j].z, qh[j].w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              const auto term = [e](const uint32_t* v) {
+                const uint16_t b = static_cast<uint16_t>(e & 1 ? v[e >> 1] >> 16 : v[e >> 1] & 0xFFFFu);
+                return static_cast<double>(static_cast<float>(__builtin_bit_cast(_Float16, b)));
+              };
+              double h = l_col ? term(wh) : term(w), l = l_col ? term(w) : 0.0;
+              requant_i8(h, l);
+              acc[e] += l_col ? l : h;
+            }
+            continue;
+          }
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             acc[2 * e] += static_cast<double>(
@@ -788,7 +564,8 @@ constexpr int kResLd = kResQ + 1;            // LDS row stride in 16-B chunks (+
 // tile): read in place from the scan's output, uniform addresses.
 constexpr int kResStaged = 0, kResFused = 1, kResGlobal = 2;
 constexpr int kResLdsMaxFeat = 1024;  // 16 KiB of S~ | D_B + the 36 KiB tile: within 64 KiB per block
-template <int kMode>
+// kI8: (h, l) -> the int8 form's (h', l') (gram_i8.hpp), nothing else.
+template <int kMode, bool kI8 = false>
 __global__ __launch_bounds__(kResRows) void csym_residual_kernel(const uint16_t* __restrict__ rows, int64_t ldh, int ks,
                                                                  int d_pad, int b0, int n_rows,
                                                                  const double* __restrict__ st,
@@ -895,6 +672,13 @@ __global__ __launch_bounds__(kResRows) void csym_residual_kernel(const uint16_t*
           const uint16_t lb = static_cast<uint16_t>(e & 1 ? lw[e >> 1] >> 16 : lw[e >> 1] & 0xFFFFu);
           const double h = static_cast<double>(static_cast<float>(__builtin_bit_cast(_Float16, hb)));
           const double l = static_cast<double>(static_cast<float>(__builtin_bit_cast(_Float16, lb)));
+          if constexpr (kI8) {
+            double h8 = h, l8 = l;
+            requant_i8(h8, l8);
+            t = t + l8 * Sv[f];
+            t = t + h8 * Dv[f];
+            continue;
+          }
           t = t + l * Sv[f];
           t = t + h * Dv[f];
         }
@@ -905,6 +689,35 @@ __global__ __launch_bounds__(kResRows) void csym_residual_kernel(const uint16_t*
   // fixed point (2^32): t * 2^-24 (operand units^2 = 2^24 x value) * 2^8
   if (tid < live_rows && t != 0.0)
     acc[static_cast<int64_t>(b0) * kSB + r0 + tid] += static_cast<long long>(__builtin_rint(t * 0x1p-16));
+}
+
+// ---------------------------------------------------------------------------
+// a(H) of the split operand (gram_i8.hpp): thread t takes 16 features of a row
+// -- 32 B of its slice's H run in, 16 B out, rows [n_rows][d_pad] int8 in
+// feature order.
+__global__ __launch_bounds__(256) void quant_i8_kernel(const uint16_t* __restrict__ ops, int64_t n_chunks, int d_pad,
+                                                       int ks, int8_t* __restrict__ out) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= n_chunks) return;
+  const int cpr = d_pad / 16;
+  const int64_t row = t / cpr;
+  const int f0 = static_cast<int>(t % cpr) * 16;
+  const uint4* src = reinterpret_cast<const uint4*>(ops + row * 2 * d_pad + (f0 / ks) * 2 * ks + f0 % ks);
+  const uint4 q[2] = {src[0], src[1]};
+  uint32_t o[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint4 v = q[k >> 1];
+    const uint32_t w[2] = {k & 1 ? v.z : v.x, k & 1 ? v.w : v.y};
+    uint32_t b = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const uint16_t hb = static_cast<uint16_t>(e & 1 ? w[e >> 1] >> 16 : w[e >> 1] & 0xFFFFu);
+      b |= static_cast<uint32_t>(quant_i8(static_cast<float>(__builtin_bit_cast(_Float16, hb))) & 0xFF) << (8 * e);
+    }
+    o[k] = b;
+  }
+  reinterpret_cast<uint4*>(out)[t] = uint4{o[0], o[1], o[2], o[3]};
 }
 
 // ---------------------------------------------------------------------------
@@ -986,6 +799,29 @@ int launch_csym_w(const uint16_t* rows, int64_t srow0, int64_t n_srb, const uint
                      static_cast<int>(j_lo), static_cast<int>(j_hi), static_cast<int>(skip_lo),
                      static_cast<int>(skip_hi), static_cast<int>(ns_active), ldh, slice_off, n_slices, L.chunk_j,
                      L.n_chunks, reinterpret_cast<unsigned long long*>(acc), contig, slot);
+  DAL_RETURN_IF_LAUNCH_FAILED();
+  return DAL_OK;
+}
+
+// The int8 form: every slice in one round-robin launch of gram_i8sym_kernel
+// (units count whole slices), also for a small column range.  ld2: the int8
+// operand's row stride in 2-byte units (d_pad / 2).
+int launch_i8sym(const int8_t* rows, int64_t srow0, int64_t n_srb, const int8_t* cols, int64_t jcol0, int64_t j_lo,
+                 int64_t j_hi, int64_t skip_lo, int64_t skip_hi, int64_t ns_active, int64_t ld2, int n_slices,
+                 int64_t* acc, int grid_blocks, int64_t min_chunks, hipStream_t stream) {
+  using C = Cfg<128, 8, 4, true>;
+  const int G0r = (grid_blocks > 0 ? grid_blocks : 2 * device_cus()) / 2;  // grid_blocks counts 4-wave blocks
+  const int G0 = G0r > 0 ? G0r : 1;
+  const GramLaunch L = plan_launch<C::HALVES>(srow0, n_srb, j_lo, j_hi, skip_lo, skip_hi, ns_active, G0, 0, min_chunks,
+                                              n_slices * C::NSUB);
+  if (L.G <= 0) return DAL_OK;
+  const int slot = L.units > L.G ? claim_slot_of(stream) : -1;
+  hipLaunchKernelGGL(gram_i8sym_kernel, dim3(static_cast<unsigned>(L.G)), dim3(C::NT), 0, stream,
+                     reinterpret_cast<const uint16_t*>(rows), static_cast<int>(srow0), static_cast<int>(n_srb),
+                     reinterpret_cast<const uint16_t*>(cols), static_cast<int>(jcol0), static_cast<int>(j_lo),
+                     static_cast<int>(j_hi), static_cast<int>(skip_lo), static_cast<int>(skip_hi),
+                     static_cast<int>(ns_active), ld2, 0, n_slices, L.chunk_j, L.n_chunks,
+                     reinterpret_cast<unsigned long long*>(acc), 0, slot);
   DAL_RETURN_IF_LAUNCH_FAILED();
   return DAL_OK;
 }
@@ -1141,8 +977,11 @@ extern "C" size_t dal_gram_sym_residual_workspace_bytes(int64_t nb_active, int64
   return residual_layout(nb_active / 2, n_row_blocks / 2, d_pad).total;
 }
 
-extern "C" int dal_gram_sym_residual(const uint16_t* ops, int64_t nb_active, int64_t row_block0, int64_t n_row_blocks,
-                                     int64_t d_pad, int64_t* acc, void* ws, size_t ws_bytes, dal_stream_t stream) {
+namespace {
+// kI8: the closed form of the int8 form's terms (h', l'), gram_i8.hpp
+template <bool kI8>
+int gram_sym_residual(const uint16_t* ops, int64_t nb_active, int64_t row_block0, int64_t n_row_blocks, int64_t d_pad,
+                      int64_t* acc, void* ws, size_t ws_bytes, dal_stream_t stream) {
   if (!ops || !acc || !ws) return DAL_ERR_ARG;
   if (nb_active <= 0 || row_block0 < 0 || n_row_blocks <= 0 || ((row_block0 | n_row_blocks | nb_active) & 1))
     return DAL_ERR_SHAPE;
@@ -1170,7 +1009,7 @@ extern "C" int dal_gram_sym_residual(const uint16_t* ops, int64_t nb_active, int
   // super blocks per block: what leaves about four blocks per CU, at most 32
   const int64_t ny = ceil_div(ldh / 8, 256);
   const int64_t qg0 = na * ny * 4 / (4 * device_cus()), qg = qg0 < 1 ? 1 : qg0 > 32 ? 32 : qg0;
-  hipLaunchKernelGGL(csym_sigma_kernel,
+  hipLaunchKernelGGL(csym_sigma_kernel<kI8>,
                      dim3(static_cast<unsigned>(ceil_div(na, qg)), static_cast<unsigned>(ny), 4), dim3(256), 0, st,
                      ops, ldh, ks, static_cast<int>(d_pad), static_cast<int>(na), static_cast<int>(qg), sig_u, sl);
   DAL_RETURN_IF_LAUNCH_FAILED();
@@ -1178,7 +1017,7 @@ extern "C" int dal_gram_sym_residual(const uint16_t* ops, int64_t nb_active, int
   const dim3 grid(static_cast<unsigned>(ceil_div(n_rows, kResRows)));
   const size_t smem = static_cast<size_t>(2 * d_pad) * 8;
   const uint16_t* rows = ops + s0 * kSB * ldh;
-  if (d_pad <= 64 && na * d_pad <= DAL_CSYM_FUSED_MAX) {  // the blocks form S~, D_B themselves
+  if (!kI8 && d_pad <= 64 && na * d_pad <= DAL_CSYM_FUSED_MAX) {  // the blocks form S~, D_B themselves
     hipLaunchKernelGGL(csym_residual_kernel<kResFused>, grid, dim3(kResRows), smem, st, rows, ldh, ks,
                        static_cast<int>(d_pad), static_cast<int>(s0), static_cast<int>(n_rows), rb, cb, sig_u,
                        static_cast<int>(na), reinterpret_cast<long long*>(acc));
@@ -1188,15 +1027,60 @@ extern "C" int dal_gram_sym_residual(const uint16_t* ops, int64_t nb_active, int
                        static_cast<int>(s0 + ns), sl, rb, cb);
     DAL_RETURN_IF_LAUNCH_FAILED();
     if (d_pad <= kResLdsMaxFeat) {
-      hipLaunchKernelGGL(csym_residual_kernel<kResStaged>, grid, dim3(kResRows), smem, st, rows, ldh, ks,
+      hipLaunchKernelGGL((csym_residual_kernel<kResStaged, kI8>), grid, dim3(kResRows), smem, st, rows, ldh, ks,
                          static_cast<int>(d_pad), static_cast<int>(s0), static_cast<int>(n_rows), rb, cb, sig_u,
                          static_cast<int>(na), reinterpret_cast<long long*>(acc));
     } else {  // wide pools: S~, D_B read in place (they would not fit in LDS beside the tile)
-      hipLaunchKernelGGL(csym_residual_kernel<kResGlobal>, grid, dim3(kResRows), 0, st, rows, ldh, ks,
+      hipLaunchKernelGGL((csym_residual_kernel<kResGlobal, kI8>), grid, dim3(kResRows), 0, st, rows, ldh, ks,
                          static_cast<int>(d_pad), static_cast<int>(s0), static_cast<int>(n_rows), rb, cb, sig_u,
                          static_cast<int>(na), reinterpret_cast<long long*>(acc));
     }
   }
   DAL_RETURN_IF_LAUNCH_FAILED();
   return DAL_OK;
+}
+}  // namespace
+
+extern "C" int dal_gram_sym_residual(const uint16_t* ops, int64_t nb_active, int64_t row_block0, int64_t n_row_blocks,
+                                     int64_t d_pad, int64_t* acc, void* ws, size_t ws_bytes, dal_stream_t stream) {
+  return gram_sym_residual<false>(ops, nb_active, row_block0, n_row_blocks, d_pad, acc, ws, ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------
+// The int8 form (gram_i8.hpp; KS 128 pools).
+extern "C" int dal_quant_i8(const uint16_t* ops, int64_t n_rows, int64_t d_pad, int8_t* out_i8, dal_stream_t stream) {
+  if (!ops || !out_i8) return DAL_ERR_ARG;
+  if (n_rows < 0 || d_pad <= 0 || d_pad % 128 || d_pad != dal_pad_features(d_pad)) return DAL_ERR_SHAPE;
+  if ((reinterpret_cast<uintptr_t>(ops) | reinterpret_cast<uintptr_t>(out_i8)) & 15) return DAL_ERR_SHAPE;
+  if (n_rows == 0) return DAL_OK;
+  const int64_t n_chunks = n_rows * (d_pad / 16);
+  hipLaunchKernelGGL(quant_i8_kernel, dim3(static_cast<unsigned>(ceil_div(n_chunks, 256))), dim3(256), 0,
+                     as_stream(stream), ops, n_chunks, static_cast<int>(d_pad), split_ks(d_pad), out_i8);
+  DAL_RETURN_IF_LAUNCH_FAILED();
+  return DAL_OK;
+}
+
+extern "C" int dal_gram_rowsum_sym_i8_skip(const int8_t* rows_i8, int64_t row_block0, int64_t n_row_blocks,
+                                           const int8_t* cols_i8, int64_t col_block0, int64_t j_lo, int64_t j_hi,
+                                           int64_t skip_lo, int64_t skip_hi, int64_t nb_active, int64_t d_pad,
+                                           int64_t* acc, int grid_blocks, dal_stream_t stream) {
+  if (!rows_i8 || !cols_i8 || !acc) return DAL_ERR_ARG;
+  if (row_block0 < 0 || n_row_blocks <= 0 || col_block0 < 0 || nb_active <= 0) return DAL_ERR_SHAPE;
+  if (j_lo < col_block0 || j_hi < j_lo || j_hi > nb_active || skip_hi < skip_lo) return DAL_ERR_SHAPE;
+  if (d_pad <= 0 || d_pad % 128 || d_pad != dal_pad_features(d_pad)) return DAL_ERR_SHAPE;
+  if ((row_block0 | n_row_blocks | nb_active) & 1) return DAL_ERR_SHAPE;  // whole 512-row super blocks
+  if ((reinterpret_cast<uintptr_t>(rows_i8) | reinterpret_cast<uintptr_t>(cols_i8)) & 15) return DAL_ERR_SHAPE;
+  if (j_hi == j_lo || row_block0 >= nb_active) return DAL_OK;
+  // (the chunk rule of the fp16 form, by the split operand's bytes)
+  const bool small = (j_hi - j_lo) * 256 * d_pad * 4 <= (int64_t{DAL_GRAM_SMALL_MB} << 20);
+  return launch_i8sym(rows_i8, row_block0 / 2, n_row_blocks / 2, cols_i8, col_block0, j_lo, j_hi, skip_lo, skip_hi,
+                      nb_active / 2, d_pad / 2, static_cast<int>(d_pad / 128), acc, grid_blocks,
+                      small ? DAL_GRAM_MIN_CHUNKS_SMALL : DAL_GRAM_MIN_CHUNKS, as_stream(stream));
+}
+
+extern "C" int dal_gram_sym_residual_i8(const uint16_t* ops, int64_t nb_active, int64_t row_block0,
+                                        int64_t n_row_blocks, int64_t d_pad, int64_t* acc, void* ws, size_t ws_bytes,
+                                        dal_stream_t stream) {
+  if (d_pad % 128) return DAL_ERR_SHAPE;
+  return gram_sym_residual<true>(ops, nb_active, row_block0, n_row_blocks, d_pad, acc, ws, ws_bytes, stream);
 }

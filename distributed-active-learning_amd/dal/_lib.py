@@ -77,6 +77,11 @@ SIGNATURES = {
     "dal_gram_sym_residual_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "dal_gram_sym_residual": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                       c_size_t, c_void_p]),
+    "dal_quant_i8": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "dal_gram_rowsum_sym_i8_skip": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                            c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p]),
+    "dal_gram_sym_residual_i8": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                         c_size_t, c_void_p]),
     "dal_forest_score": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32,
                                  c_int32, c_void_p, c_void_p, c_int, c_double, c_void_p, c_double,
                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

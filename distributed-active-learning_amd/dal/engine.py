@@ -136,7 +136,7 @@ class PoolState:
     """
 
     def __init__(self, pool, excluded=None, device=None, row_base: int = 0, n_total=None,
-                 n_pad=None, gram: str = None):
+                 n_pad=None, gram: str = None, gram_i8=None):
         torch = _torch()
         self.gram = _gram_kind(gram)
         dev = _require_cuda(device)
@@ -156,6 +156,18 @@ class PoolState:
         if self.n_pad < self.n or self.n_pad % 512:
             raise ValueError("n_pad must be a multiple of 512 and >= the row count")
         self.d_pad = int(lib.dal_pad_features(self.d))
+        # The int8 form of the "sym" Gram (int8 MFMA row sums of a(H), the rest
+        # in closed form: csrc/gram_i8.hpp).  A property of the pool, not of a
+        # call: gram_accumulate and gram_residual must agree, on every shard.
+        # None: pools of 128-feature slices whose whole split operand exceeds
+        # the contiguous schedule's 32 MB; True / False: tests and A/B runs.
+        if gram_i8 is None:
+            n_all = (self.n_total + 511) // 512 * 512
+            gram_i8 = self.gram == "sym" and self.d_pad % 128 == 0 and n_all * 2 * self.d_pad * 2 > GRAM_I8_MIN_BYTES
+        elif gram_i8 and (self.gram != "sym" or self.d_pad % 128):
+            raise ValueError("gram_i8 needs gram 'sym' and a feature count padded to a multiple of 128")
+        self.gram_i8 = bool(gram_i8)
+        self._split_i8 = None
         self.flags = torch.zeros(self.n, dtype=torch.uint8, device=dev)
         self.excluded = np.zeros(0, dtype=np.int64)
         self.set_excluded(excluded)
@@ -200,7 +212,7 @@ class PoolState:
         """Drop normalised rows, density, column sums and the blocked copy
         (forces a cold step)."""
         self._u = self._norm64 = self._density = self._colsum = self._colsum_partials = None
-        self._split = self._density_exact = self._xb = None
+        self._split = self._density_exact = self._xb = self._split_i8 = None
         self._graphs = {}
 
     def blocked_pool(self, forest, build: bool = True, multiclass: bool = None):
@@ -257,7 +269,7 @@ class PoolState:
         if local.size:
             self.flags[torch.from_numpy(local).to(self.device)] = DAL_ROW_EXCLUDED
         self._u = self._norm64 = self._density = self._colsum = self._colsum_partials = None
-        self._split = self._density_exact = None
+        self._split = self._density_exact = self._split_i8 = None
         self._graphs = {}
 
     def n_excluded_global(self) -> int:
@@ -327,6 +339,23 @@ class PoolState:
         if acc_zero is not None and not zeroed:
             acc_zero.zero_()
         return self._split
+
+    def gram_operand_i8(self, ops=None, n_rows=None):
+        """The int8 form's MFMA operand a(H) [rows, d_pad] of the first
+        ``n_rows`` rows of the split operand ``ops`` (dal_quant_i8).  This
+        shard's own operand (the default) is quantised once and kept with the
+        pool's caches; any other -- a gathered operand or a slice -- per call."""
+        torch = _torch()
+        own = self.gram_operand()
+        if ops is None or ops is own or _ptr(ops) == _ptr(own):  # (a row prefix of the own operand included)
+            if self._split_i8 is None:
+                self._split_i8 = torch.empty((self.n_pad, self.d_pad), dtype=torch.int8, device=self.device)
+                call("dal_quant_i8", _ptr(own), self.n_pad, self.d_pad, _ptr(self._split_i8), _stream(self.device))
+            return self._split_i8
+        n_rows = int(ops.shape[0]) if n_rows is None else int(n_rows)
+        q = torch.empty((n_rows, self.d_pad), dtype=torch.int8, device=self.device)
+        call("dal_quant_i8", _ptr(ops), n_rows, self.d_pad, _ptr(q), _stream(self.device))
+        return q
 
     def colsum_partials(self):
         """Canonical fp64 column-sum partials of this shard ([chunks, d])."""
@@ -403,7 +432,12 @@ class PoolState:
             j_lo = col_row0 // 256
             j_hi = min(j_lo + int(n_cols_pad) // 256, nb)
             s_lo, s_hi = (0, 0) if skip is None else (skip[0] // 256, skip[1] // 256)
-            if j_hi > j_lo and self.row_base // 256 < nb:
+            if j_hi > j_lo and self.row_base // 256 < nb and self.gram_i8:
+                cols_i8 = self.gram_operand_i8(cols, (j_hi - j_lo) * 256)
+                call("dal_gram_rowsum_sym_i8_skip", _ptr(self.gram_operand_i8()), self.row_base // 256,
+                     self.n_pad // 256, _ptr(cols_i8), j_lo, j_lo, j_hi, s_lo, s_hi, nb, self.d_pad, _ptr(acc),
+                     int(grid_blocks), _stream(self.device))
+            elif j_hi > j_lo and self.row_base // 256 < nb:
                 call("dal_gram_rowsum_sym_skip", _ptr(op), self.row_base // 256, self.n_pad // 256,
                      _ptr(cols), j_lo, j_lo, j_hi, s_lo, s_hi, nb, self.d_pad, _ptr(acc), int(grid_blocks),
                      _stream(self.device))
@@ -434,8 +468,8 @@ class PoolState:
         if self.gram_events is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
-        call("dal_gram_sym_residual", _ptr(ops), nb, rb0, nrb, self.d_pad, _ptr(acc), wsp, wsb,
-             _stream(self.device))
+        call("dal_gram_sym_residual_i8" if self.gram_i8 else "dal_gram_sym_residual", _ptr(ops), nb, rb0, nrb,
+             self.d_pad, _ptr(acc), wsp, wsb, _stream(self.device))
         if ev is not None:
             ev[1].record()
             self.residual_events.append(ev)
@@ -510,6 +544,7 @@ class PoolState:
 
 
 GRAM_KINDS = ("sym", "f32")
+GRAM_I8_MIN_BYTES = 32 << 20  # split operands above the contiguous schedule's limit take the int8 form
 
 
 def _gram_kind(gram) -> str:

@@ -206,6 +206,26 @@ int dal_gram_rowsum_sym_skip(const uint16_t* rows, int64_t row_block0, int64_t n
 size_t dal_gram_sym_residual_workspace_bytes(int64_t nb_active, int64_t n_row_blocks, int64_t d_pad);
 int dal_gram_sym_residual(const uint16_t* ops, int64_t nb_active, int64_t row_block0, int64_t n_row_blocks,
                           int64_t d_pad, int64_t* acc, void* ws, size_t ws_bytes, dal_stream_t stream);
+/* The int8 form of the same density (pools with d_pad % 128 == 0; new symbols
+ * of ABI v10).  With a(h) = clamp(rint(h / 32), -127, 127) of the operand's H
+ * terms (dal_quant_i8: [n_rows][d_pad] int8, features in natural order, from
+ * the split operand -- a pure function of it) the MFMAs
+ * (v_mfma_i32_16x16x64_i8) form the exact int32 row sums of <a_i, a_j> over
+ * the taken pairs, and acc receives them times 2^18; dal_gram_sym_residual_i8
+ * adds everything else in closed form, decoding every operand element as h' =
+ * 32 a(h), l' = (h - h') + l where dal_gram_sym_residual decodes (h, l).  The
+ * two belong together: acc holds the density after dal_gram_rowsum_sym_i8_skip
+ * AND dal_gram_sym_residual_i8, within the same dal_density_error_bound_sym_d.
+ * Arguments as dal_gram_rowsum_sym_skip (rows_i8 / cols_i8: the int8 operands
+ * of the same row ranges, 16-byte aligned) and dal_gram_sym_residual (the
+ * split operand, the same workspace); always the round-robin schedule. */
+int dal_quant_i8(const uint16_t* ops, int64_t n_rows, int64_t d_pad, int8_t* out_i8, dal_stream_t stream);
+int dal_gram_rowsum_sym_i8_skip(const int8_t* rows_i8, int64_t row_block0, int64_t n_row_blocks,
+                                const int8_t* cols_i8, int64_t col_block0, int64_t j_lo, int64_t j_hi,
+                                int64_t skip_lo, int64_t skip_hi, int64_t nb_active, int64_t d_pad, int64_t* acc,
+                                int grid_blocks, dal_stream_t stream);
+int dal_gram_sym_residual_i8(const uint16_t* ops, int64_t nb_active, int64_t row_block0, int64_t n_row_blocks,
+                             int64_t d_pad, int64_t* acc, void* ws, size_t ws_bytes, dal_stream_t stream);
 double dal_density_error_bound_sym(int64_t n_cols);
 /* The same bound for the kernel that runs features padded to d_pad (ABI v8):
  * the row-side chain length charged depends on the slice width KS (1,024
