@@ -1,6 +1,6 @@
 // The body of the symmetric Gram kernels (gram_sym.hip): included by
-// gram_csym_kernel<KS, W, HVS> and by the int8 instance gram_i8sym_kernel
-// behind `using C = Cfg<...>;`, with the kernels' argument names.
+// gram_csym_kernel<KS, W, HVS> and by the int8 and fp4 instances
+// gram_i8sym_kernel and gram_fp4sym_kernel behind `using C = Cfg<...>;`, with the kernels' argument names.
   constexpr int HV = C::HALVES;
   __shared__ __attribute__((aligned(16))) float4 lds[2 * C::F4];
   __shared__ typename C::racc_t rowacc[HV * kSB];
@@ -88,6 +88,8 @@
   auto b_off = [&](int c) { return b_base + ((c * C::LG) ^ b_swz); };
 
   typename C::acc4 mc[C::NCH][C::RT];
+  // the fp4 form's scale register, the same for both operands (read by no other form)
+  [[maybe_unused]] const int mx_scale = kFp4ScaleWord;
   // one stage of SC columns; fresh = first stage of a fold group (the chains
   // restart).  B fragments go through two register sets: k-step i+1's are
   // read while k-step i's 16 MFMAs issue.
@@ -116,7 +118,7 @@
         const typename C::acc4 zero = {};
 #pragma unroll
         for (int rt = 0; rt < C::RT; ++rt)
-          mc[ch][rt] = C::mfma(bh[cur], ah[rt][c], (c % KPC == 0 && fresh) ? zero : mc[ch][rt]);
+          mc[ch][rt] = C::mfma(bh[cur], ah[rt][c], (c % KPC == 0 && fresh) ? zero : mc[ch][rt], mx_scale);
       }
       constexpr int NM = C::RT;  // MFMAs per k-step
 #pragma unroll
@@ -128,7 +130,8 @@
     }
   };
   // chains -> LDS row accumulator (exact integer adds: fp64, or int64 for the
-  // int8 form's int32 chains -- Cfg::row_add).  The column tile
+  // int8 form's int32 chains and the fp4 form's fp32 chains of integers,
+  // converted in Cfg::lane_sum -- Cfg::row_add).  The column tile
   // is the MFMA's M side, so lane (li, lq) holds row li of the row tile at the
   // tile's columns 4 lq .. 4 lq + 3: the 16 columns of a row are summed in the
   // lane, (m0 + m1) + (m2 + m3), and over the four lane rows, (x0 + x2) + (x1 +
@@ -148,7 +151,7 @@
 #pragma unroll
         for (int rt = 0; rt < 8; ++rt) {
           const typename C::acc4 m = mc[ch][t0 + rt];
-          x[rt] = (m[0] + m[1]) + (m[2] + m[3]);
+          x[rt] = C::lane_sum(m);
         }
         // lanes 0-31 keep tiles 0-3, lanes 32-63 tiles 4-7; then even rows keep k, odd rows k + 2
 #pragma unroll

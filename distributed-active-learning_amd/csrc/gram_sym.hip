@@ -102,12 +102,29 @@
 // gram_i8sym_kernel is the wide form's body (gram_csym_body.inc) on the int8
 // operand (dal_quant_i8): the same stages, swizzle, DMA pieces, B reads,
 // look-ahead, claim and flush, byte for byte.
+//
+// The fp4 form (round 14; gram_fp4.hpp, dal_gram_rowsum_sym_fp4_skip +
+// dal_gram_sym_residual_fp4: the int8 form's pools whose d_pad is a multiple
+// of 256).  On the flagship pool a(H) only takes 0..15: the int8 MFMA spends
+// 8-bit lanes on 4-bit numbers.  a4(H), the element of +-{0, 1, 2, 3, 4, 6, 8,
+// 12} nearest to H / 32, is twice an e2m1 value, and
+// v_mfma_scale_f32_16x16x128_f8f6f4 with e2m1 on both sides takes the cycles
+// of the int8 instruction at twice the K.  A slice is 256 features here: its
+// staged row is 128 B and a 16-byte fragment one K = 128 operand, so
+// gram_fp4sym_kernel is the int8 instance byte for byte -- stages, swizzle, DMA
+// pieces, B reads, 2 k-steps x 16 row tiles per column tile, 128 resident A
+// registers, 512 MFMAs per wave and pair -- over half as many units.  The
+// chains are fp32 holding exact integers (below 589,824 < 2^24 whatever the
+// data; scripts/mfma_rate_probe.py checks the instruction's adder on chains
+// of this length), converted to int32 at the fold; from there on the int8
+// form's integers.  The closed form is fed h' = 32 a4, l' = (H - h') + L.
 #include <stdlib.h>
 
 #include <mutex>
 #include <type_traits>
 
 #include "common.hpp"
+#include "gram_fp4.hpp"
 #include "gram_i8.hpp"
 #include "gram_schedule.hpp"
 
@@ -118,6 +135,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
 #define AS3 __attribute__((address_space(3)))
 
 constexpr int kSB = 512;       // super block rows
@@ -188,23 +206,40 @@ __device__ __forceinline__ unsigned fresh_lane() {
 // the kernel forms sum_j <a_i, a_j> in int32 by v_mfma_i32_16x16x64_i8 -- a
 // whole 128-feature slice per pass of 512 MFMAs, where the fp16 form takes
 // two.  Offsets stay in 2-byte units (ldh = d_pad / 2).
-template <int KS, int W = 4, int HVS = W / 4, bool I8F = false>
+// FP4 (the wide form only, KS 256): the operands are the e2m1 codes of a4(H)
+// (gram_fp4.hpp), [rows][d_pad / 2] bytes in feature order, two features per
+// byte; v_mfma_scale_f32_16x16x128_f8f6f4 forms sum_j <a4_i, a4_j> in fp32
+// chains that hold exact integers -- a whole 256-feature slice per pass of 512
+// MFMAs.  ldh = d_pad / 4.
+constexpr int kFormF16 = 0, kFormI8 = 1, kFormFp4 = 2;
+// The fp4 form's scale word: E8M0 128 (a factor 2) in every byte, for both
+// operands.  An e2m1 value is half its element of G, so with scales of 2 the
+// accumulator holds sum a4 a4 itself -- an integer that v_cvt_i32_f32 takes as
+// it is; unit scales (127) would leave a quarter of it and a multiply at every
+// fold.  The probe found both exact.
+constexpr int kFp4ScaleWord = static_cast<int>(0x80808080u);
+template <int KS, int W = 4, int HVS = W / 4, int FORM = kFormF16>
 struct Cfg {
-  static constexpr bool I8 = I8F;
+  static constexpr bool I8 = FORM == kFormI8;
+  static constexpr bool FP4 = FORM == kFormFp4;
+  static constexpr bool INT = I8 || FP4;            // exact integer row sums, the rest in closed form
   static constexpr int WAVES = W;                   // 4: one super block per block; 8: two (P, P + 2) or four
   static constexpr int HALVES = HVS;                // super blocks per block
   // the wide form: 8 waves hold four super blocks (P, P + 2, P + 4, P + 6), 256
   // rows per wave, over sub-slices of half the slice's features -- the same
   // A registers as 128 rows x KS features, twice the rows per staged B byte
   static constexpr bool WIDE = HVS == 4;
-  static constexpr int KW = WIDE && !I8 ? KS / 2 : KS;  // features of the resident A fragments, of a staged row
+  static constexpr int KW = WIDE && !INT ? KS / 2 : KS;  // features of the resident A fragments, of a staged row
   static constexpr int NSUB = KS / KW;              // sub-slices per slice
   static constexpr int WPS = W / HVS;               // waves per super block: 4, or 2
   static constexpr int RPW = kSB / WPS;             // rows per wave: 128, or 256
   static constexpr int NT = 64 * W;                 // threads
-  static constexpr int ROWB = KW * (I8 ? 1 : 2);    // bytes per staged operand row of a sub-slice (its H run)
+  // bytes per staged operand row of a sub-slice (its H run)
+  static constexpr int ROWB = FP4 ? KW / 2 : KW * (I8 ? 1 : 2);
   // halves from the launch's first slice to sub-slice q: the operand keeps H run | L run per KS-slice
-  static constexpr int sub_off(int q) { return I8 ? q * KS / 2 : (q / NSUB) * 2 * KS + (q % NSUB) * KW; }
+  static constexpr int sub_off(int q) {
+    return FP4 ? q * KS / 4 : I8 ? q * KS / 2 : (q / NSUB) * 2 * KS + (q % NSUB) * KW;
+  }
   static constexpr int SLOTS = ROWB / 16;           // 16-B slots per row: 4 / 8 / 16
   // three 4-wave blocks per CU at KS 64 (OCC3): 16 KiB stages so three fit the LDS
   static constexpr int OCC = W == 8 ? (KS == 64 ? DAL_GRAM_W8_OCC64 : 1)
@@ -213,7 +248,7 @@ struct Cfg {
   static constexpr int SC = STAGE / ROWB;           // columns per stage: 64 / 128 / 256
   static constexpr int SPP = 256 / SC;              // stages per 512 x 256 pair: 4 / 2 / 1
   static_assert(SC >= 16 && SC <= 256, "a stage holds 16 to 256 whole columns");
-  static constexpr int FOLD = KS == 128 ? DAL_GRAM_FOLD128 : DAL_GRAM_FOLD64;  // columns per row fold
+  static constexpr int FOLD = KS >= 128 ? DAL_GRAM_FOLD128 : DAL_GRAM_FOLD64;  // columns per row fold
   static constexpr int SPF = FOLD / SC;             // stages per fold group
   static constexpr int F4 = STAGE / 16;
   static constexpr int SWZ = SLOTS - 1;
@@ -235,8 +270,9 @@ struct Cfg {
   static constexpr int PIECES = STAGE / (W * 1024);  // 1-KiB DMA pieces per wave per stage
   static constexpr int RT = RPW / 16;               // 16-row tiles per wave
   static constexpr int LG = 4;
-  // k-steps of v_mfma_f32_16x16x32_f16 (int8: v_mfma_i32_16x16x64_i8) per column tile
-  static constexpr int NKS = KW / (I8 ? 64 : 32);
+  // k-steps of v_mfma_f32_16x16x32_f16 (int8: v_mfma_i32_16x16x64_i8, fp4: the
+  // scaled 16x16x128) per column tile
+  static constexpr int NKS = KW / (FP4 ? 128 : I8 ? 64 : 32);
   static constexpr int NCT = SC / 16;               // column tiles per stage
   // Row-sum chains per row tile.  KS 128: one chain per 64-feature half of the
   // slice (k-steps 2h, 2h + 1 of every column tile, tiles in column order),
@@ -255,15 +291,22 @@ struct Cfg {
   static constexpr int CHARGED = KS == 32 ? DAL_GRAM_CHAIN_MAX / 2 : DAL_GRAM_CHAIN_MAX;
   static_assert(SPF >= 1 && SPP % SPF == 0 && PIECES >= 1 && NKS >= 1, "bad slice");
   static_assert(W == 4 || (W == 8 && KS >= 64), "several super blocks per block: KS >= 64 only");
-  static_assert(!WIDE || (W == 8 && KS == 128), "the wide form: 8 waves at KS 128");
-  static_assert(I8 || (NKS % NCH == 0 && KW / NCH == 64 / (KS == 32 ? 2 : 1)),
+  static_assert(!WIDE || (W == 8 && KS == (FP4 ? 256 : 128)), "the wide form: 8 waves at KS 128 (fp4: 256)");
+  static_assert(FP4 == (KS == 256), "256-feature slices are the fp4 form's");
+  static_assert(INT || (NKS % NCH == 0 && KW / NCH == 64 / (KS == 32 ? 2 : 1)),
                 "a chain is 64 features of every tile (KS 32: 32)");
-  static_assert(I8 || CHAIN <= CHARGED, "row chain longer than the density bound charges");
-  static_assert(!I8 || (WIDE && ROWB == 128 && NSUB == 1), "the int8 form: the wide form over whole slices");
+  static_assert(INT || CHAIN <= CHARGED, "row chain longer than the density bound charges");
+  static_assert(!INT || (WIDE && ROWB == 128 && NSUB == 1 && NKS == 2 && NCH == 1),
+                "the int8 and fp4 forms: the wide form over whole slices");
   // int8: |sum_f a_i a_j| < 1.2 * 2^14 per column on unit rows (Cauchy-Schwarz
   // with |32 a| <= |H| + 16 sqrt(d_pad)), so a chain element's FOLD / 4 columns
   // stay below 2^21 and a row's 256 below 2^23: no int32 overflow.
   static_assert(!I8 || FOLD <= 256, "int32 row chains: at most a pair's 256 columns between folds");
+  // fp4: a chain element sums FOLD / 16 column tiles x KW features of |a4 a4| <=
+  // 144, exact in fp32 whatever the data (gram_fp4.hpp)
+  static_assert(!FP4 || (FOLD / 16 * KW * kFp4Max * kFp4Max == kFp4ChainMax &&
+                         FOLD * KW * kFp4Max * kFp4Max == kFp4RowMax),
+                "fp32 chains of exact integers, int32 row sums");
 
   // the chains' registers and the LDS row accumulator.  fp16: fp32 chains folded
   // to multiples of 2^-32 and added as integers in fp64 (below 2^53: at most
@@ -271,17 +314,32 @@ struct Cfg {
   // and adds s * 2^18 (gram_i8.hpp); a column may reach 1.2 * 2^32 here, so the
   // accumulator is an int64 -- exact for any pool the int64 density itself holds.
   using acc4 = typename std::conditional<I8, i32x4, f32x4>::type;
-  using sum_t = typename std::conditional<I8, int, float>::type;
-  using racc_t = typename std::conditional<I8, long long, double>::type;
-  static __device__ __forceinline__ acc4 mfma(f16x8 a, f16x8 b, acc4 c) {
-    if constexpr (I8)
+  // (fp4: fp32 chains, converted to int32 at the fold)
+  using sum_t = typename std::conditional<INT, int, float>::type;
+  using racc_t = typename std::conditional<INT, long long, double>::type;
+  // scale: the fp4 form's scale register (kFp4ScaleWord, set once before the pair loop)
+  static __device__ __forceinline__ acc4 mfma(f16x8 a, f16x8 b, acc4 c, [[maybe_unused]] int scale) {
+    if constexpr (FP4) {
+      // (with fp4 on both sides the instruction reads the first four registers of each operand)
+      const i32x4 a4 = __builtin_bit_cast(i32x4, a), b4 = __builtin_bit_cast(i32x4, b);
+      const i32x8 a8 = {a4[0], a4[1], a4[2], a4[3], 0, 0, 0, 0}, b8 = {b4[0], b4[1], b4[2], b4[3], 0, 0, 0, 0};
+      return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b8, c, 4, 4, 0, scale, 0, scale);
+    } else if constexpr (I8) {
       return __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b), c, 0,
                                                    0, 0);
-    else
+    } else {
       return mfma16(a, b, c);
+    }
+  }
+  // A lane's four columns of a row tile.  fp4: every partial sum is an integer
+  // of at most 4 x 589,824 = 2,359,296 < 2^24 = 16,777,216, so the fp32 adds are
+  // exact (no assumption on the data: kFp4ChainMax) and one v_cvt_i32_f32 per
+  // tile takes the sum as it is -- converting each element first would be four.
+  static __device__ __forceinline__ sum_t lane_sum(acc4 m) {
+    return static_cast<sum_t>((m[0] + m[1]) + (m[2] + m[3]));
   }
   static __device__ __forceinline__ void row_add(racc_t* slot, sum_t x) {
-    if constexpr (I8)
+    if constexpr (INT)
       atomicAdd(reinterpret_cast<unsigned long long*>(slot),
                 static_cast<unsigned long long>(static_cast<long long>(x) << kI8AccShift));
     else
@@ -321,7 +379,18 @@ __global__ __launch_bounds__(512, 1) void gram_i8sym_kernel(
     const uint16_t* __restrict__ ucols, int jcol0, int j_lo, int j_hi, int skip_lo, int skip_hi,
     int ns_active, int64_t ldh, int slice_off, int n_slices, int chunk_j, int n_chunks,
     unsigned long long* __restrict__ acc_out, int contig, int claim_slot) {
-  using C = Cfg<128, 8, 4, true>;
+  using C = Cfg<128, 8, 4, kFormI8>;
+#include "gram_csym_body.inc"
+}
+// The fp4 instance: the int8 instance's stages and schedule over 256-feature
+// slices; e2m1 operands, fp32 chains of exact integers, the same int64 row
+// accumulator.
+__global__ __launch_bounds__(512, 1) void gram_fp4sym_kernel(
+    const uint16_t* __restrict__ urows, int srow0, int n_srb,
+    const uint16_t* __restrict__ ucols, int jcol0, int j_lo, int j_hi, int skip_lo, int skip_hi,
+    int ns_active, int64_t ldh, int slice_off, int n_slices, int chunk_j, int n_chunks,
+    unsigned long long* __restrict__ acc_out, int contig, int claim_slot) {
+  using C = Cfg<256, 8, 4, kFormFp4>;
 #include "gram_csym_body.inc"
 }
 // ---------------------------------------------------------------------------
@@ -352,9 +421,17 @@ __global__ __launch_bounds__(512, 1) void gram_i8sym_kernel(
 // over the whole walk and reach S^L with one add per block and feature -- S^L
 // is d_pad addresses for the whole pool, and one add per super block and row
 // slice (15,628 per address at config 4) made this kernel 2.85 ms, from 0.55.
-// kI8: the int8 form's terms (h', l') of gram_i8.hpp in place of (h, l) -- an L
-// chunk column also reads its H chunk (ks halves before it) for h - h'.
-template <bool kI8>
+// kForm != fp16: the int8 form's terms (h', l') of gram_i8.hpp, or the fp4
+// form's of gram_fp4.hpp, in place of (h, l) -- an L chunk column also reads
+// its H chunk (ks halves before it) for h - h'.
+template <int kForm>
+__device__ __forceinline__ void requant(double& h, double& l) {
+  if constexpr (kForm == kFormFp4)
+    requant_fp4(h, l);
+  else
+    requant_i8(h, l);
+}
+template <int kForm>
 __global__ __launch_bounds__(256) void csym_sigma_kernel(const uint16_t* __restrict__ ops, int64_t ldh, int ks,
                                                          int d_pad, int ns, int qg, long long* __restrict__ sig_u,
                                                          long long* __restrict__ sl) {
@@ -387,8 +464,8 @@ __global__ __launch_bounds__(256) void csym_sigma_kernel(const uint16_t* __restr
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           q[j] = r + j * rstep < re ? base[static_cast<int64_t>(r + j * rstep) * cpr] : uint4{};
-        [[maybe_unused]] uint4 qh[8];  // int8 form, L column: the H chunk of the same features
-        if constexpr (kI8) {
+        [[maybe_unused]] uint4 qh[8];  // int8 and fp4 forms, L column: the H chunk of the same features
+        if constexpr (kForm != kFormF16) {
 #pragma unroll
           for (int j = 0; j < 8; ++j)
             qh[j] = l_col && r + j * rstep < re ? base[static_cast<int64_t>(r + j * rstep) * cpr - hpc] : uint4{};
@@ -396,7 +473,7 @@ __global__ __launch_bounds__(256) void csym_sigma_kernel(const uint16_t* __restr
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const uint32_t w[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
-          if constexpr (kI8) {
+          if constexpr (kForm != kFormF16) {
             const uint32_t wh[4] = {qh[j].x, qh[j].y, qh[j].z, qh[j].w};
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -405,7 +482,7 @@ __global__ __launch_bounds__(256) void csym_sigma_kernel(const uint16_t* __restr
                 return static_cast<double>(static_cast<float>(__builtin_bit_cast(_Float16, b)));
               };
               double h = l_col ? term(wh) : term(w), l = l_col ? term(w) : 0.0;
-              requant_i8(h, l);
+              requant<kForm>(h, l);
               acc[e] += l_col ? l : h;
             }
             continue;
@@ -564,8 +641,8 @@ constexpr int kResLd = kResQ + 1;            // LDS row stride in 16-B chunks (+
 // tile): read in place from the scan's output, uniform addresses.
 constexpr int kResStaged = 0, kResFused = 1, kResGlobal = 2;
 constexpr int kResLdsMaxFeat = 1024;  // 16 KiB of S~ | D_B + the 36 KiB tile: within 64 KiB per block
-// kI8: (h, l) -> the int8 form's (h', l') (gram_i8.hpp), nothing else.
-template <int kMode, bool kI8 = false>
+// kForm != fp16: (h, l) -> the int8 or fp4 form's (h', l') (gram_i8.hpp, gram_fp4.hpp), nothing else.
+template <int kMode, int kForm = kFormF16>
 __global__ __launch_bounds__(kResRows) void csym_residual_kernel(const uint16_t* __restrict__ rows, int64_t ldh, int ks,
                                                                  int d_pad, int b0, int n_rows,
                                                                  const double* __restrict__ st,
@@ -672,9 +749,9 @@ __global__ __launch_bounds__(kResRows) void csym_residual_kernel(const uint16_t*
           const uint16_t lb = static_cast<uint16_t>(e & 1 ? lw[e >> 1] >> 16 : lw[e >> 1] & 0xFFFFu);
           const double h = static_cast<double>(static_cast<float>(__builtin_bit_cast(_Float16, hb)));
           const double l = static_cast<double>(static_cast<float>(__builtin_bit_cast(_Float16, lb)));
-          if constexpr (kI8) {
+          if constexpr (kForm != kFormF16) {
             double h8 = h, l8 = l;
-            requant_i8(h8, l8);
+            requant<kForm>(h8, l8);
             t = t + l8 * Sv[f];
             t = t + h8 * Dv[f];
             continue;
@@ -714,6 +791,33 @@ __global__ __launch_bounds__(256) void quant_i8_kernel(const uint16_t* __restric
     for (int e = 0; e < 4; ++e) {
       const uint16_t hb = static_cast<uint16_t>(e & 1 ? w[e >> 1] >> 16 : w[e >> 1] & 0xFFFFu);
       b |= static_cast<uint32_t>(quant_i8(static_cast<float>(__builtin_bit_cast(_Float16, hb))) & 0xFF) << (8 * e);
+    }
+    o[k] = b;
+  }
+  reinterpret_cast<uint4*>(out)[t] = uint4{o[0], o[1], o[2], o[3]};
+}
+
+// The e2m1 codes of a4(H) (gram_fp4.hpp): thread t takes 32 features of a row
+// -- 64 B of its 128-slice's H run in, 16 B out, rows [n_rows][d_pad / 2] bytes
+// in feature order, the even feature in the low nibble.
+__global__ __launch_bounds__(256) void quant_fp4_kernel(const uint16_t* __restrict__ ops, int64_t n_chunks, int d_pad,
+                                                        int ks, uint8_t* __restrict__ out) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= n_chunks) return;
+  const int cpr = d_pad / 32;
+  const int64_t row = t / cpr;
+  const int f0 = static_cast<int>(t % cpr) * 32;
+  const uint4* src = reinterpret_cast<const uint4*>(ops + row * 2 * d_pad + (f0 / ks) * 2 * ks + f0 % ks);
+  const uint4 q[4] = {src[0], src[1], src[2], src[3]};
+  uint32_t o[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {  // 8 features -> one word
+    const uint32_t w[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
+    uint32_t b = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const uint16_t hb = static_cast<uint16_t>(e & 1 ? w[e >> 1] >> 16 : w[e >> 1] & 0xFFFFu);
+      b |= code_fp4(quant_fp4(static_cast<float>(__builtin_bit_cast(_Float16, hb)))) << (4 * e);
     }
     o[k] = b;
   }
@@ -803,20 +907,23 @@ int launch_csym_w(const uint16_t* rows, int64_t srow0, int64_t n_srb, const uint
   return DAL_OK;
 }
 
-// The int8 form: every slice in one round-robin launch of gram_i8sym_kernel
-// (units count whole slices), also for a small column range.  ld2: the int8
-// operand's row stride in 2-byte units (d_pad / 2).
-int launch_i8sym(const int8_t* rows, int64_t srow0, int64_t n_srb, const int8_t* cols, int64_t jcol0, int64_t j_lo,
-                 int64_t j_hi, int64_t skip_lo, int64_t skip_hi, int64_t ns_active, int64_t ld2, int n_slices,
-                 int64_t* acc, int grid_blocks, int64_t min_chunks, hipStream_t stream) {
-  using C = Cfg<128, 8, 4, true>;
+// The int8 and fp4 forms: every slice in one round-robin launch of
+// gram_i8sym_kernel or gram_fp4sym_kernel (units count whole slices), also for
+// a small column range.  ld2: the operand's row stride in 2-byte units (int8:
+// d_pad / 2, fp4: d_pad / 4).
+template <int FORM>
+int launch_intsym(const void* rows, int64_t srow0, int64_t n_srb, const void* cols, int64_t jcol0, int64_t j_lo,
+                  int64_t j_hi, int64_t skip_lo, int64_t skip_hi, int64_t ns_active, int64_t ld2, int n_slices,
+                  int64_t* acc, int grid_blocks, int64_t min_chunks, hipStream_t stream) {
+  using C = Cfg<FORM == kFormFp4 ? 256 : 128, 8, 4, FORM>;
   const int G0r = (grid_blocks > 0 ? grid_blocks : 2 * device_cus()) / 2;  // grid_blocks counts 4-wave blocks
   const int G0 = G0r > 0 ? G0r : 1;
   const GramLaunch L = plan_launch<C::HALVES>(srow0, n_srb, j_lo, j_hi, skip_lo, skip_hi, ns_active, G0, 0, min_chunks,
                                               n_slices * C::NSUB);
   if (L.G <= 0) return DAL_OK;
   const int slot = L.units > L.G ? claim_slot_of(stream) : -1;
-  hipLaunchKernelGGL(gram_i8sym_kernel, dim3(static_cast<unsigned>(L.G)), dim3(C::NT), 0, stream,
+  hipLaunchKernelGGL(FORM == kFormFp4 ? gram_fp4sym_kernel : gram_i8sym_kernel, dim3(static_cast<unsigned>(L.G)),
+                     dim3(C::NT), 0, stream,
                      reinterpret_cast<const uint16_t*>(rows), static_cast<int>(srow0), static_cast<int>(n_srb),
                      reinterpret_cast<const uint16_t*>(cols), static_cast<int>(jcol0), static_cast<int>(j_lo),
                      static_cast<int>(j_hi), static_cast<int>(skip_lo), static_cast<int>(skip_hi),
@@ -978,8 +1085,8 @@ extern "C" size_t dal_gram_sym_residual_workspace_bytes(int64_t nb_active, int64
 }
 
 namespace {
-// kI8: the closed form of the int8 form's terms (h', l'), gram_i8.hpp
-template <bool kI8>
+// kForm != fp16: the closed form of the int8 or fp4 form's terms (h', l'), gram_i8.hpp / gram_fp4.hpp
+template <int kForm>
 int gram_sym_residual(const uint16_t* ops, int64_t nb_active, int64_t row_block0, int64_t n_row_blocks, int64_t d_pad,
                       int64_t* acc, void* ws, size_t ws_bytes, dal_stream_t stream) {
   if (!ops || !acc || !ws) return DAL_ERR_ARG;
@@ -1009,7 +1116,7 @@ int gram_sym_residual(const uint16_t* ops, int64_t nb_active, int64_t row_block0
   // super blocks per block: what leaves about four blocks per CU, at most 32
   const int64_t ny = ceil_div(ldh / 8, 256);
   const int64_t qg0 = na * ny * 4 / (4 * device_cus()), qg = qg0 < 1 ? 1 : qg0 > 32 ? 32 : qg0;
-  hipLaunchKernelGGL(csym_sigma_kernel<kI8>,
+  hipLaunchKernelGGL(csym_sigma_kernel<kForm>,
                      dim3(static_cast<unsigned>(ceil_div(na, qg)), static_cast<unsigned>(ny), 4), dim3(256), 0, st,
                      ops, ldh, ks, static_cast<int>(d_pad), static_cast<int>(na), static_cast<int>(qg), sig_u, sl);
   DAL_RETURN_IF_LAUNCH_FAILED();
@@ -1017,7 +1124,7 @@ int gram_sym_residual(const uint16_t* ops, int64_t nb_active, int64_t row_block0
   const dim3 grid(static_cast<unsigned>(ceil_div(n_rows, kResRows)));
   const size_t smem = static_cast<size_t>(2 * d_pad) * 8;
   const uint16_t* rows = ops + s0 * kSB * ldh;
-  if (!kI8 && d_pad <= 64 && na * d_pad <= DAL_CSYM_FUSED_MAX) {  // the blocks form S~, D_B themselves
+  if (kForm == kFormF16 && d_pad <= 64 && na * d_pad <= DAL_CSYM_FUSED_MAX) {  // the blocks form S~, D_B themselves
     hipLaunchKernelGGL(csym_residual_kernel<kResFused>, grid, dim3(kResRows), smem, st, rows, ldh, ks,
                        static_cast<int>(d_pad), static_cast<int>(s0), static_cast<int>(n_rows), rb, cb, sig_u,
                        static_cast<int>(na), reinterpret_cast<long long*>(acc));
@@ -1027,11 +1134,11 @@ int gram_sym_residual(const uint16_t* ops, int64_t nb_active, int64_t row_block0
                        static_cast<int>(s0 + ns), sl, rb, cb);
     DAL_RETURN_IF_LAUNCH_FAILED();
     if (d_pad <= kResLdsMaxFeat) {
-      hipLaunchKernelGGL((csym_residual_kernel<kResStaged, kI8>), grid, dim3(kResRows), smem, st, rows, ldh, ks,
+      hipLaunchKernelGGL((csym_residual_kernel<kResStaged, kForm>), grid, dim3(kResRows), smem, st, rows, ldh, ks,
                          static_cast<int>(d_pad), static_cast<int>(s0), static_cast<int>(n_rows), rb, cb, sig_u,
                          static_cast<int>(na), reinterpret_cast<long long*>(acc));
     } else {  // wide pools: S~, D_B read in place (they would not fit in LDS beside the tile)
-      hipLaunchKernelGGL((csym_residual_kernel<kResGlobal, kI8>), grid, dim3(kResRows), 0, st, rows, ldh, ks,
+      hipLaunchKernelGGL((csym_residual_kernel<kResGlobal, kForm>), grid, dim3(kResRows), 0, st, rows, ldh, ks,
                          static_cast<int>(d_pad), static_cast<int>(s0), static_cast<int>(n_rows), rb, cb, sig_u,
                          static_cast<int>(na), reinterpret_cast<long long*>(acc));
     }
@@ -1043,7 +1150,7 @@ int gram_sym_residual(const uint16_t* ops, int64_t nb_active, int64_t row_block0
 
 extern "C" int dal_gram_sym_residual(const uint16_t* ops, int64_t nb_active, int64_t row_block0, int64_t n_row_blocks,
                                      int64_t d_pad, int64_t* acc, void* ws, size_t ws_bytes, dal_stream_t stream) {
-  return gram_sym_residual<false>(ops, nb_active, row_block0, n_row_blocks, d_pad, acc, ws, ws_bytes, stream);
+  return gram_sym_residual<kFormF16>(ops, nb_active, row_block0, n_row_blocks, d_pad, acc, ws, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1073,14 +1180,54 @@ extern "C" int dal_gram_rowsum_sym_i8_skip(const int8_t* rows_i8, int64_t row_bl
   if (j_hi == j_lo || row_block0 >= nb_active) return DAL_OK;
   // (the chunk rule of the fp16 form, by the split operand's bytes)
   const bool small = (j_hi - j_lo) * 256 * d_pad * 4 <= (int64_t{DAL_GRAM_SMALL_MB} << 20);
-  return launch_i8sym(rows_i8, row_block0 / 2, n_row_blocks / 2, cols_i8, col_block0, j_lo, j_hi, skip_lo, skip_hi,
-                      nb_active / 2, d_pad / 2, static_cast<int>(d_pad / 128), acc, grid_blocks,
-                      small ? DAL_GRAM_MIN_CHUNKS_SMALL : DAL_GRAM_MIN_CHUNKS, as_stream(stream));
+  return launch_intsym<kFormI8>(rows_i8, row_block0 / 2, n_row_blocks / 2, cols_i8, col_block0, j_lo, j_hi, skip_lo,
+                                skip_hi, nb_active / 2, d_pad / 2, static_cast<int>(d_pad / 128), acc, grid_blocks,
+                                small ? DAL_GRAM_MIN_CHUNKS_SMALL : DAL_GRAM_MIN_CHUNKS, as_stream(stream));
 }
 
 extern "C" int dal_gram_sym_residual_i8(const uint16_t* ops, int64_t nb_active, int64_t row_block0,
                                         int64_t n_row_blocks, int64_t d_pad, int64_t* acc, void* ws, size_t ws_bytes,
                                         dal_stream_t stream) {
   if (d_pad % 128) return DAL_ERR_SHAPE;
-  return gram_sym_residual<true>(ops, nb_active, row_block0, n_row_blocks, d_pad, acc, ws, ws_bytes, stream);
+  return gram_sym_residual<kFormI8>(ops, nb_active, row_block0, n_row_blocks, d_pad, acc, ws, ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------
+// The fp4 form (gram_fp4.hpp; pools with d_pad % 256 == 0).
+extern "C" int dal_quant_fp4(const uint16_t* ops, int64_t n_rows, int64_t d_pad, uint8_t* out_fp4,
+                             dal_stream_t stream) {
+  if (!ops || !out_fp4) return DAL_ERR_ARG;
+  if (n_rows < 0 || d_pad <= 0 || d_pad % 256 || d_pad != dal_pad_features(d_pad)) return DAL_ERR_SHAPE;
+  if ((reinterpret_cast<uintptr_t>(ops) | reinterpret_cast<uintptr_t>(out_fp4)) & 15) return DAL_ERR_SHAPE;
+  if (n_rows == 0) return DAL_OK;
+  const int64_t n_chunks = n_rows * (d_pad / 32);
+  hipLaunchKernelGGL(quant_fp4_kernel, dim3(static_cast<unsigned>(ceil_div(n_chunks, 256))), dim3(256), 0,
+                     as_stream(stream), ops, n_chunks, static_cast<int>(d_pad), split_ks(d_pad), out_fp4);
+  DAL_RETURN_IF_LAUNCH_FAILED();
+  return DAL_OK;
+}
+
+extern "C" int dal_gram_rowsum_sym_fp4_skip(const uint8_t* rows_fp4, int64_t row_block0, int64_t n_row_blocks,
+                                            const uint8_t* cols_fp4, int64_t col_block0, int64_t j_lo, int64_t j_hi,
+                                            int64_t skip_lo, int64_t skip_hi, int64_t nb_active, int64_t d_pad,
+                                            int64_t* acc, int grid_blocks, dal_stream_t stream) {
+  if (!rows_fp4 || !cols_fp4 || !acc) return DAL_ERR_ARG;
+  if (row_block0 < 0 || n_row_blocks <= 0 || col_block0 < 0 || nb_active <= 0) return DAL_ERR_SHAPE;
+  if (j_lo < col_block0 || j_hi < j_lo || j_hi > nb_active || skip_hi < skip_lo) return DAL_ERR_SHAPE;
+  if (d_pad <= 0 || d_pad % 256 || d_pad != dal_pad_features(d_pad)) return DAL_ERR_SHAPE;
+  if ((row_block0 | n_row_blocks | nb_active) & 1) return DAL_ERR_SHAPE;  // whole 512-row super blocks
+  if ((reinterpret_cast<uintptr_t>(rows_fp4) | reinterpret_cast<uintptr_t>(cols_fp4)) & 15) return DAL_ERR_SHAPE;
+  if (j_hi == j_lo || row_block0 >= nb_active) return DAL_OK;
+  // (the chunk rule of the fp16 form, by the split operand's bytes)
+  const bool small = (j_hi - j_lo) * 256 * d_pad * 4 <= (int64_t{DAL_GRAM_SMALL_MB} << 20);
+  return launch_intsym<kFormFp4>(rows_fp4, row_block0 / 2, n_row_blocks / 2, cols_fp4, col_block0, j_lo, j_hi, skip_lo,
+                                 skip_hi, nb_active / 2, d_pad / 4, static_cast<int>(d_pad / 256), acc, grid_blocks,
+                                 small ? DAL_GRAM_MIN_CHUNKS_SMALL : DAL_GRAM_MIN_CHUNKS, as_stream(stream));
+}
+
+extern "C" int dal_gram_sym_residual_fp4(const uint16_t* ops, int64_t nb_active, int64_t row_block0,
+                                         int64_t n_row_blocks, int64_t d_pad, int64_t* acc, void* ws, size_t ws_bytes,
+                                         dal_stream_t stream) {
+  if (d_pad % 256) return DAL_ERR_SHAPE;
+  return gram_sym_residual<kFormFp4>(ops, nb_active, row_block0, n_row_blocks, d_pad, acc, ws, ws_bytes, stream);
 }

@@ -82,6 +82,11 @@ SIGNATURES = {
                                             c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p]),
     "dal_gram_sym_residual_i8": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                          c_size_t, c_void_p]),
+    "dal_quant_fp4": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "dal_gram_rowsum_sym_fp4_skip": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                             c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p]),
+    "dal_gram_sym_residual_fp4": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                          c_size_t, c_void_p]),
     "dal_forest_score": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32,
                                  c_int32, c_void_p, c_void_p, c_int, c_double, c_void_p, c_double,
                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -136,7 +136,7 @@ class PoolState:
     """
 
     def __init__(self, pool, excluded=None, device=None, row_base: int = 0, n_total=None,
-                 n_pad=None, gram: str = None, gram_i8=None):
+                 n_pad=None, gram: str = None, gram_i8=None, gram_fp4=None):
         torch = _torch()
         self.gram = _gram_kind(gram)
         dev = _require_cuda(device)
@@ -161,13 +161,27 @@ class PoolState:
         # call: gram_accumulate and gram_residual must agree, on every shard.
         # None: pools of 128-feature slices whose whole split operand exceeds
         # the contiguous schedule's 32 MB; True / False: tests and A/B runs.
+        # The fp4 form (e2m1 MFMA row sums of a4(H) over 256-feature slices:
+        # csrc/gram_fp4.hpp) takes the int8 form's place where the rule above
+        # picks that one and d_pad is a multiple of 256.  An explicit gram_i8
+        # (True or False) with gram_fp4=None means no fp4: tests and A/B runs
+        # force the other two forms that way.  Both rules read n_total, so
+        # every shard agrees.
+        i8_given = gram_i8 is not None
         if gram_i8 is None:
             n_all = (self.n_total + 511) // 512 * 512
             gram_i8 = self.gram == "sym" and self.d_pad % 128 == 0 and n_all * 2 * self.d_pad * 2 > GRAM_I8_MIN_BYTES
         elif gram_i8 and (self.gram != "sym" or self.d_pad % 128):
             raise ValueError("gram_i8 needs gram 'sym' and a feature count padded to a multiple of 128")
-        self.gram_i8 = bool(gram_i8)
-        self._split_i8 = None
+        if gram_fp4 is None:
+            gram_fp4 = bool(gram_i8) and not i8_given and self.d_pad % 256 == 0
+        elif gram_fp4 and (self.gram != "sym" or self.d_pad % 256):
+            raise ValueError("gram_fp4 needs gram 'sym' and a feature count padded to a multiple of 256")
+        elif gram_fp4 and i8_given and gram_i8:
+            raise ValueError("gram_i8 and gram_fp4 are two forms of one Gram: force one")
+        self.gram_fp4 = bool(gram_fp4)
+        self.gram_i8 = bool(gram_i8) and not self.gram_fp4  # (one form runs)
+        self._split_i8 = self._split_fp4 = None
         self.flags = torch.zeros(self.n, dtype=torch.uint8, device=dev)
         self.excluded = np.zeros(0, dtype=np.int64)
         self.set_excluded(excluded)
@@ -212,7 +226,7 @@ class PoolState:
         """Drop normalised rows, density, column sums and the blocked copy
         (forces a cold step)."""
         self._u = self._norm64 = self._density = self._colsum = self._colsum_partials = None
-        self._split = self._density_exact = self._xb = self._split_i8 = None
+        self._split = self._density_exact = self._xb = self._split_i8 = self._split_fp4 = None
         self._graphs = {}
 
     def blocked_pool(self, forest, build: bool = True, multiclass: bool = None):
@@ -269,7 +283,7 @@ class PoolState:
         if local.size:
             self.flags[torch.from_numpy(local).to(self.device)] = DAL_ROW_EXCLUDED
         self._u = self._norm64 = self._density = self._colsum = self._colsum_partials = None
-        self._split = self._density_exact = self._split_i8 = None
+        self._split = self._density_exact = self._split_i8 = self._split_fp4 = None
         self._graphs = {}
 
     def n_excluded_global(self) -> int:
@@ -357,6 +371,23 @@ class PoolState:
         call("dal_quant_i8", _ptr(ops), n_rows, self.d_pad, _ptr(q), _stream(self.device))
         return q
 
+    def gram_operand_fp4(self, ops=None, n_rows=None):
+        """The fp4 form's MFMA operand, the e2m1 codes of a4(H) [rows, d_pad / 2]
+        bytes (feature f in byte f / 2, the even one in the low nibble), of the
+        first ``n_rows`` rows of the split operand ``ops`` (dal_quant_fp4).
+        Cached and per call as gram_operand_i8."""
+        torch = _torch()
+        own = self.gram_operand()
+        if ops is None or ops is own or _ptr(ops) == _ptr(own):  # (a row prefix of the own operand included)
+            if self._split_fp4 is None:
+                self._split_fp4 = torch.empty((self.n_pad, self.d_pad // 2), dtype=torch.uint8, device=self.device)
+                call("dal_quant_fp4", _ptr(own), self.n_pad, self.d_pad, _ptr(self._split_fp4), _stream(self.device))
+            return self._split_fp4
+        n_rows = int(ops.shape[0]) if n_rows is None else int(n_rows)
+        q = torch.empty((n_rows, self.d_pad // 2), dtype=torch.uint8, device=self.device)
+        call("dal_quant_fp4", _ptr(ops), n_rows, self.d_pad, _ptr(q), _stream(self.device))
+        return q
+
     def colsum_partials(self):
         """Canonical fp64 column-sum partials of this shard ([chunks, d])."""
         if self._colsum_partials is None:
@@ -432,7 +463,12 @@ class PoolState:
             j_lo = col_row0 // 256
             j_hi = min(j_lo + int(n_cols_pad) // 256, nb)
             s_lo, s_hi = (0, 0) if skip is None else (skip[0] // 256, skip[1] // 256)
-            if j_hi > j_lo and self.row_base // 256 < nb and self.gram_i8:
+            if j_hi > j_lo and self.row_base // 256 < nb and self.gram_fp4:
+                cols_fp4 = self.gram_operand_fp4(cols, (j_hi - j_lo) * 256)
+                call("dal_gram_rowsum_sym_fp4_skip", _ptr(self.gram_operand_fp4()), self.row_base // 256,
+                     self.n_pad // 256, _ptr(cols_fp4), j_lo, j_lo, j_hi, s_lo, s_hi, nb, self.d_pad, _ptr(acc),
+                     int(grid_blocks), _stream(self.device))
+            elif j_hi > j_lo and self.row_base // 256 < nb and self.gram_i8:
                 cols_i8 = self.gram_operand_i8(cols, (j_hi - j_lo) * 256)
                 call("dal_gram_rowsum_sym_i8_skip", _ptr(self.gram_operand_i8()), self.row_base // 256,
                      self.n_pad // 256, _ptr(cols_i8), j_lo, j_lo, j_hi, s_lo, s_hi, nb, self.d_pad, _ptr(acc),
@@ -468,8 +504,9 @@ class PoolState:
         if self.gram_events is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
-        call("dal_gram_sym_residual_i8" if self.gram_i8 else "dal_gram_sym_residual", _ptr(ops), nb, rb0, nrb,
-             self.d_pad, _ptr(acc), wsp, wsb, _stream(self.device))
+        name = ("dal_gram_sym_residual_fp4" if self.gram_fp4 else
+                "dal_gram_sym_residual_i8" if self.gram_i8 else "dal_gram_sym_residual")
+        call(name, _ptr(ops), nb, rb0, nrb, self.d_pad, _ptr(acc), wsp, wsb, _stream(self.device))
         if ev is not None:
             ev[1].record()
             self.residual_events.append(ev)

@@ -94,7 +94,7 @@ class ShardedSelector:
     """One rank's shard of the pool and its share of a selection step."""
 
     def __init__(self, x_local, n_total: int, rank: int, world: int, excluded=None, device=None,
-                 gram: str = None, gram_i8=None):
+                 gram: str = None, gram_i8=None, gram_fp4=None):
         from .engine import PoolState
 
         self.n_total, self.rank, self.world = int(n_total), int(rank), int(world)
@@ -102,7 +102,7 @@ class ShardedSelector:
         if int(x_local.shape[0]) != self.hi - self.lo:
             raise ValueError(f"rank {rank}: expected {self.hi - self.lo} rows, got {x_local.shape[0]}")
         self.state = PoolState(x_local, excluded=excluded, device=device, row_base=self.lo,
-                               n_total=self.n_total, n_pad=self.shard, gram=gram, gram_i8=gram_i8)
+                               n_total=self.n_total, n_pad=self.shard, gram=gram, gram_i8=gram_i8, gram_fp4=gram_fp4)
         self._density = None
         self._parts_full = None  # all ranks' canonical column-sum partials (cached with the density)
         self._colsum = None      # the global canonical column sum reduced from them (cached)

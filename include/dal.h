@@ -226,6 +226,26 @@ int dal_gram_rowsum_sym_i8_skip(const int8_t* rows_i8, int64_t row_block0, int64
                                 int grid_blocks, dal_stream_t stream);
 int dal_gram_sym_residual_i8(const uint16_t* ops, int64_t nb_active, int64_t row_block0, int64_t n_row_blocks,
                              int64_t d_pad, int64_t* acc, void* ws, size_t ws_bytes, dal_stream_t stream);
+/* The fp4 form of the same density (pools with d_pad % 256 == 0; new symbols,
+ * the ABI number stays).  With a4(h) = the element of +-{0, 1, 2, 3, 4, 6, 8, 12}
+ * nearest to h / 32 (ties to the smaller magnitude; twice an e2m1 value) of
+ * the operand's H terms (dal_quant_fp4: [n_rows][d_pad / 2] bytes of 4-bit
+ * e2m1 codes, features in natural order, feature f in byte f / 2, the even
+ * one in the low nibble -- a pure function of the split operand) the MFMAs
+ * (v_mfma_scale_f32_16x16x128_f8f6f4, fp4 on both sides) form the exact
+ * integer row sums of <a4_i, a4_j> over the taken pairs, and acc receives them
+ * times 2^18; dal_gram_sym_residual_fp4 adds everything else in closed form,
+ * decoding every operand element as h' = 32 a4(h), l' = (h - h') + l.  The two
+ * belong together as the int8 pair does, within the same
+ * dal_density_error_bound_sym_d.  Arguments as the _i8 pair; always the
+ * round-robin schedule. */
+int dal_quant_fp4(const uint16_t* ops, int64_t n_rows, int64_t d_pad, uint8_t* out_fp4, dal_stream_t stream);
+int dal_gram_rowsum_sym_fp4_skip(const uint8_t* rows_fp4, int64_t row_block0, int64_t n_row_blocks,
+                                 const uint8_t* cols_fp4, int64_t col_block0, int64_t j_lo, int64_t j_hi,
+                                 int64_t skip_lo, int64_t skip_hi, int64_t nb_active, int64_t d_pad, int64_t* acc,
+                                 int grid_blocks, dal_stream_t stream);
+int dal_gram_sym_residual_fp4(const uint16_t* ops, int64_t nb_active, int64_t row_block0, int64_t n_row_blocks,
+                              int64_t d_pad, int64_t* acc, void* ws, size_t ws_bytes, dal_stream_t stream);
 double dal_density_error_bound_sym(int64_t n_cols);
 /* The same bound for the kernel that runs features padded to d_pad (ABI v8):
  * the row-side chain length charged depends on the slice width KS (1,024
