@@ -47,6 +47,10 @@ DAL_MC_MAX_TREES = 255
 DAL_MC_LEAST_CONFIDENCE = 0
 DAL_MC_MARGIN = 1
 DAL_MC_ENTROPY = 2
+DAL_REG_MAX_DEPTH = 10
+DAL_X_F32 = 0
+DAL_X_F64 = 1
+DAL_LAL_MAX_TREES = 4095
 
 # name -> (restype, argtypes); every symbol of include/dal.h
 SIGNATURES = {
@@ -195,6 +199,13 @@ SIGNATURES = {
     "dal_rf_train_multiclass": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32,
                                         c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_int32,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dal_forest_regress_chunk_trees": (c_int, [c_int32]),
+    "dal_forest_regress": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                   c_int32, c_int32, c_void_p, c_void_p]),
+    "dal_vote_histogram": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "dal_lal_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_double, c_double, c_void_p, c_void_p]),
+    "dal_votes_rescore": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int, c_void_p, c_void_p,
+                                  c_void_p]),
 }
 
 _lib = None

@@ -68,6 +68,8 @@ class Selection:
                     (None for a multiclass step)
     counts          uint8 [U, C]: per-class forest votes of every unlabeled row
                     (a multiclass step; None otherwise)
+    lut             fp64 [T+1]: a LAL step (lal_step) also sets this attribute,
+                    the regressor's prediction per vote count
 
     ``scores`` / ``votes`` / ``counts`` may be given as (per-row tensor, positions): they are
     gathered into unlabeled order on first access (the per-row arrays are
@@ -1383,3 +1385,96 @@ def _density_step_separable(state: PoolState, unlabeled_idx, forest: Forest, k: 
     sel_scores = scores[idx - state.row_base]
     state.check_status()
     return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, votes=(votes, loc))
+
+
+# ------------------------------------------------------------------ LAL --
+def forest_regress(model, x, n: int, d: int, ldx: int, device, f64: bool):
+    """Launch dal_forest_regress over n rows of ``x`` (a device tensor, fp32
+    or fp64 by ``f64``): the regression forest's prediction, fp64 [n]."""
+    torch = _torch()
+    model.check_features(d)
+    feat, thr, leaf = model.device(device)
+    out = torch.empty(n, dtype=torch.float64, device=device)
+    call("dal_forest_regress", _ptr(x), _lib.DAL_X_F64 if f64 else _lib.DAL_X_F32, n, d, ldx, _ptr(feat), _ptr(thr),
+         _ptr(leaf), model.n_trees, model.depth, _ptr(out), _stream(device))
+    return out
+
+
+def device_lal_tables(n_trees: int, device):
+    """(f1, f2) of dal.active_learner.lal_tables on the device, uploaded once
+    per (T, device)."""
+    torch = _torch()
+    key = ("lal", int(n_trees), str(device))
+    if key not in _LUT_CACHE:
+        from .active_learner import lal_tables
+
+        _LUT_CACHE[key] = tuple(torch.from_numpy(t).to(device) for t in lal_tables(n_trees))
+    return _LUT_CACHE[key]
+
+
+def lal_votes(state: PoolState, forest: Forest, flags):
+    """The LAL step's first half on one shard: the forest votes of every row
+    (dal_forest_score; its scores and keys, written for a stand-in LUT, are
+    dropped) and the vote histogram of the candidates, int64 [T + 1]."""
+    torch = _torch()
+    T = forest.n_trees
+    lut0 = device_lut("least_confidence", T, state.device)  # any LUT: only the votes are kept
+    votes, _, _, _ = forest_score(state, forest, lut0, flags, DAL_ASCENDING, xb=uncertainty_blocked(state, forest))
+    hist = torch.zeros(T + 1, dtype=torch.int64, device=state.device)
+    call("dal_vote_histogram", _ptr(votes), _ptr(flags), state.n, T, _ptr(hist), _stream(state.device))
+    return votes, hist
+
+
+def lal_scores(state: PoolState, forest: Forest, lal_model, flags, votes, hist, n_labeled: int, n_positive: int):
+    """The LAL step's second half, from the (all-reduced) histogram: the T + 1
+    feature rows, the regressor over them (the LUT), and every row's score and
+    descending key.  Returns (lut [T + 1], scores [n], keys [n])."""
+    torch = _torch()
+    dev = state.device
+    T = forest.n_trees
+    f1, f2 = device_lal_tables(T, dev)
+    rows = torch.empty((T + 1, 5), dtype=torch.float64, device=dev)
+    call("dal_lal_rows", _ptr(hist), _ptr(f1), _ptr(f2), T, float(n_positive) / n_labeled, float(n_labeled),
+         _ptr(rows), _stream(dev))
+    lut = forest_regress(lal_model, rows, T + 1, 5, 5, dev, f64=True)
+    scores = torch.empty(state.n, dtype=torch.float64, device=dev)
+    keys = torch.empty(state.n, dtype=torch.int64, device=dev)
+    call("dal_votes_rescore", _ptr(votes), _ptr(flags), state.n, _ptr(lut), T, DAL_DESCENDING, _ptr(scores),
+         _ptr(keys), _stream(dev))
+    return lut, scores, keys
+
+
+def check_lal_inputs(forest: Forest, lal_model, n_labeled, n_positive):
+    """The LAL step's argument rules (pure host code)."""
+    if forest.n_classes > 2:
+        raise ValueError(f"LAL is binary only: the forest has {forest.n_classes} classes")
+    if not 2 <= forest.n_trees <= _lib.DAL_LAL_MAX_TREES:
+        raise ValueError(f"LAL needs a forest of 2..{_lib.DAL_LAL_MAX_TREES} trees (getSD divides by T - 1), "
+                         f"not {forest.n_trees}")
+    if int(n_labeled) < 1:
+        raise ValueError("n_labeled must be at least 1")
+    if not 0 <= int(n_positive) <= int(n_labeled):
+        raise ValueError("n_positive must lie in [0, n_labeled]")
+    lal_model.check_features(5)
+
+
+def lal_step(state: PoolState, unlabeled_idx, forest: Forest, lal_model, k: int, n_labeled: int,
+             n_positive: int) -> Selection:
+    """One iteration of ActiveLearnerLAL.selectNext (active_learner.py:247-334)
+    on the GPU: votes -> histogram -> feature rows -> regressor -> rescore ->
+    top-k (descending, the largest predicted error reduction), every launch
+    stream-ordered.  The Selection also carries ``lut`` (fp64 [T + 1])."""
+    check_lal_inputs(forest, lal_model, n_labeled, n_positive)
+    flags, unl, n_cand = state.row_flags(unlabeled_idx)
+    if n_cand == 0:
+        raise ValueError("unlabeled set is empty (the reference loop breaks here)")
+    kk = min(int(k), n_cand)
+    loc = state.local_positions(unl)
+    votes, hist = lal_votes(state, forest, flags)
+    lut, scores, keys = lal_scores(state, forest, lal_model, flags, votes, hist, n_labeled, n_positive)
+    idx, _ = topk_keys(keys, kk, state.row_base)
+    sel_scores = scores[idx - state.row_base]
+    state.check_status()
+    sel = Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, votes=(votes, loc))
+    sel.lut = lut
+    return sel

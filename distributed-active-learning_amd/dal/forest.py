@@ -28,7 +28,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import DAL_MAX_TREE_DEPTH, DAL_MC_MAX_CLASSES
+from ._lib import DAL_MAX_TREE_DEPTH, DAL_MC_MAX_CLASSES, DAL_REG_MAX_DEPTH
 
 _POS_INF_BITS = np.array([np.inf], dtype=np.float32).view(np.int32)[0]
 
@@ -226,56 +226,8 @@ class Forest:
         n_classes None: the binary mapping (``Predict: 1.0`` is class 1, any
         other label class 0); else ``Predict: c`` is class id int(c) of a
         forest of n_classes (trainClassifier's numClasses)."""
-        import re
-
-        lines = [ln.strip() for ln in text.splitlines() if ln.strip()]
-        trees, cur = [], None
-        for ln in lines:
-            if re.match(r"^Tree \d+:$", ln):
-                cur = []
-                trees.append(cur)
-            elif cur is not None and (ln.startswith("If ") or ln.startswith("Else ")
-                                      or ln.startswith("Predict:")):
-                cur.append(ln)
-        if not trees:
-            raise ValueError("no 'Tree k:' sections found in the debug string")
-        feat, thr, lft, rgt, val, roots = [], [], [], [], [], []
-        if_re = re.compile(r"^If \(feature (\d+) <= ([^)]+)\)$")
-        else_re = re.compile(r"^Else \(feature (\d+) > ([^)]+)\)$")
-
-        def new_node():
-            feat.append(-1)
-            thr.append(0.0)
-            lft.append(-1)
-            rgt.append(-1)
-            val.append(0)
-            return len(feat) - 1
-
-        for body in trees:
-            pos = 0
-
-            def parse():
-                nonlocal pos
-                ln = body[pos]
-                pos += 1
-                nd = new_node()
-                if ln.startswith("Predict:"):
-                    val[nd] = _mllib_class(float(ln.split(":", 1)[1]), n_classes)
-                    return nd
-                m = if_re.match(ln)
-                if not m:
-                    raise ValueError(f"unsupported split line {ln!r} (only continuous splits)")
-                feat[nd], thr[nd] = int(m.group(1)), float(m.group(2))
-                lft[nd] = parse()
-                m2 = else_re.match(body[pos])
-                if not m2 or int(m2.group(1)) != feat[nd]:
-                    raise ValueError(f"malformed Else line {body[pos]!r}")
-                pos += 1
-                rgt[nd] = parse()
-                return nd
-
-            roots.append(parse())
-        return cls._from_mllib_nodes(feat, thr, lft, rgt, val, roots, n_classes)
+        nodes = _parse_mllib_debug_string(text, lambda c: _mllib_class(c, n_classes))
+        return cls._from_mllib_nodes(*nodes, n_classes)
 
     @classmethod
     def _from_mllib_nodes(cls, feat, thr, lft, rgt, val, roots, n_classes) -> "Forest":
@@ -292,44 +244,8 @@ class Forest:
         isLeaf, split{feature, threshold, featureType, categories}, leftNodeId,
         rightNodeId, infoGain) under ``path/data``; continuous splits only.
         n_classes: as from_mllib_debug_string."""
-        import glob
-        import os
-
-        import pyarrow.parquet as pq
-
-        data = os.path.join(path, "data") if os.path.isdir(os.path.join(path, "data")) else path
-        files = sorted(glob.glob(os.path.join(data, "*.parquet")))
-        if not files:
-            raise ValueError(f"no parquet files under {data}")
-        rows = []
-        for f in files:
-            rows.extend(pq.read_table(f).to_pylist())
-        by_tree = {}
-        for r in rows:
-            by_tree.setdefault(int(r["treeId"]), {})[int(r["nodeId"])] = r
-        feat, thr, lft, rgt, val, roots = [], [], [], [], [], []
-        for t in sorted(by_tree):
-            nodes = by_tree[t]
-            gid = {nid: len(feat) + i for i, nid in enumerate(sorted(nodes))}
-            for nid in sorted(nodes):
-                r = nodes[nid]
-                if r["isLeaf"]:
-                    feat.append(-1)
-                    thr.append(0.0)
-                    lft.append(-1)
-                    rgt.append(-1)
-                    val.append(_mllib_class(float(r["predict"]["predict"]), n_classes))
-                else:
-                    sp = r["split"]
-                    if int(sp.get("featureType", 0)) != 0:
-                        raise ValueError("categorical splits are not supported")
-                    feat.append(int(sp["feature"]))
-                    thr.append(float(sp["threshold"]))
-                    lft.append(gid[int(r["leftNodeId"])])
-                    rgt.append(gid[int(r["rightNodeId"])])
-                    val.append(0)
-            roots.append(gid[min(nodes)])  # MLlib root node id = 1 (smallest)
-        return cls._from_mllib_nodes(feat, thr, lft, rgt, val, roots, n_classes)
+        nodes = _read_mllib_saved(path, lambda c: _mllib_class(c, n_classes))
+        return cls._from_mllib_nodes(*nodes, n_classes)
 
     @classmethod
     def synthetic(cls, n_trees: int, depth: int, n_features: int, seed: int = 1,
@@ -370,3 +286,248 @@ def _mllib_class(label: float, n_classes) -> int:
     if label != int(label) or not 0 <= int(label) < int(n_classes):
         raise ValueError(f"leaf label {label} is not a class id in [0, {int(n_classes)})")
     return int(label)
+
+
+def _parse_mllib_debug_string(text: str, leaf_value):
+    """The node arrays (feature, threshold, left, right, value, roots) of
+    MLlib's ``toDebugString()`` text; ``leaf_value`` maps a leaf's ``Predict:``
+    double to the value kept (a class id, or the double itself)."""
+    import re
+
+    lines = [ln.strip() for ln in text.splitlines() if ln.strip()]
+    trees, cur = [], None
+    for ln in lines:
+        if re.match(r"^Tree \d+:$", ln):
+            cur = []
+            trees.append(cur)
+        elif cur is not None and (ln.startswith("If ") or ln.startswith("Else ")
+                                  or ln.startswith("Predict:")):
+            cur.append(ln)
+    if not trees:
+        raise ValueError("no 'Tree k:' sections found in the debug string")
+    feat, thr, lft, rgt, val, roots = [], [], [], [], [], []
+    if_re = re.compile(r"^If \(feature (\d+) <= ([^)]+)\)$")
+    else_re = re.compile(r"^Else \(feature (\d+) > ([^)]+)\)$")
+
+    def new_node():
+        feat.append(-1)
+        thr.append(0.0)
+        lft.append(-1)
+        rgt.append(-1)
+        val.append(0)
+        return len(feat) - 1
+
+    for body in trees:
+        pos = 0
+
+        def parse():
+            nonlocal pos
+            ln = body[pos]
+            pos += 1
+            nd = new_node()
+            if ln.startswith("Predict:"):
+                val[nd] = leaf_value(float(ln.split(":", 1)[1]))
+                return nd
+            m = if_re.match(ln)
+            if not m:
+                raise ValueError(f"unsupported split line {ln!r} (only continuous splits)")
+            feat[nd], thr[nd] = int(m.group(1)), float(m.group(2))
+            lft[nd] = parse()
+            m2 = else_re.match(body[pos])
+            if not m2 or int(m2.group(1)) != feat[nd]:
+                raise ValueError(f"malformed Else line {body[pos]!r}")
+            pos += 1
+            rgt[nd] = parse()
+            return nd
+
+        roots.append(parse())
+    return feat, thr, lft, rgt, val, roots
+
+
+def _read_mllib_saved(path: str, leaf_value):
+    """The node arrays of an MLlib ``RandomForestModel.save`` directory
+    (Parquet NodeData rows); ``leaf_value`` as _parse_mllib_debug_string."""
+    import glob
+    import os
+
+    import pyarrow.parquet as pq
+
+    data = os.path.join(path, "data") if os.path.isdir(os.path.join(path, "data")) else path
+    files = sorted(glob.glob(os.path.join(data, "*.parquet")))
+    if not files:
+        raise ValueError(f"no parquet files under {data}")
+    rows = []
+    for f in files:
+        rows.extend(pq.read_table(f).to_pylist())
+    by_tree = {}
+    for r in rows:
+        by_tree.setdefault(int(r["treeId"]), {})[int(r["nodeId"])] = r
+    feat, thr, lft, rgt, val, roots = [], [], [], [], [], []
+    for t in sorted(by_tree):
+        nodes = by_tree[t]
+        gid = {nid: len(feat) + i for i, nid in enumerate(sorted(nodes))}
+        for nid in sorted(nodes):
+            r = nodes[nid]
+            if r["isLeaf"]:
+                feat.append(-1)
+                thr.append(0.0)
+                lft.append(-1)
+                rgt.append(-1)
+                val.append(leaf_value(float(r["predict"]["predict"])))
+            else:
+                sp = r["split"]
+                if int(sp.get("featureType", 0)) != 0:
+                    raise ValueError("categorical splits are not supported")
+                feat.append(int(sp["feature"]))
+                thr.append(float(sp["threshold"]))
+                lft.append(gid[int(r["leftNodeId"])])
+                rgt.append(gid[int(r["rightNodeId"])])
+                val.append(0)
+        roots.append(gid[min(nodes)])  # MLlib root node id = 1 (smallest)
+    return feat, thr, lft, rgt, val, roots
+
+
+@dataclass
+class RegressionForest:
+    """A regression forest, MLlib's ``RandomForest.trainRegressor`` model: the
+    prediction is the mean of the trees' real-valued leaves
+    (``RandomForestModel.predict``; the LAL model of
+    lal_direct_mllib_implementation/classes/active_learner.py:319, :354-365).
+
+    Layout: Forest's complete heap of the maximum depth D, padded the same way
+    (a shallow leaf's subtree gets always-left splits, threshold +inf, and its
+    value fills the subtree's leaves), with
+      inner_feature    int32   [TR, 2^D - 1]
+      inner_threshold  float64 [TR, 2^D - 1]   the model's value, NOT rounded
+      leaf             float64 [TR, 2^D]
+    The compare is fp64, ``row[feature] <= threshold`` goes left: LAL's rows
+    (v/T, an SD, ...) are not fp32-representable, so Forest's fp32 thresholds
+    rounded toward -inf would not keep MLlib's branches."""
+
+    inner_feature: np.ndarray
+    inner_threshold: np.ndarray
+    leaf: np.ndarray
+    depth: int
+    _dev: dict = field(default_factory=dict, repr=False)
+
+    @property
+    def n_trees(self) -> int:
+        return int(self.inner_feature.shape[0])
+
+    def check_features(self, d: int):
+        """Raise unless every inner node tests a feature in [0, d)."""
+        if "range" not in self._dev:
+            f = self.inner_feature
+            self._dev["range"] = (int(f.min()), int(f.max())) if f.size else (0, 0)
+        lo, hi = self._dev["range"]
+        if lo < 0 or hi >= d:
+            raise ValueError(f"forest tests feature {lo if lo < 0 else hi}, outside the rows' {d} features")
+
+    def device(self, device):
+        """(inner_feature, inner_threshold, leaf) as device tensors, uploaded
+        once per device."""
+        import torch
+
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device)
+                                   for a in (self.inner_feature, self.inner_threshold, self.leaf))
+        return self._dev[key]
+
+    # ------------------------------------------------------------ builders
+    @classmethod
+    def from_nodes(cls, feature, threshold, left, right, value, roots) -> "RegressionForest":
+        """Flattened node arrays (global node ids), as Forest.from_nodes:
+        feature < 0 marks a leaf whose prediction is value[node] (a double)."""
+        feature = np.asarray(feature, dtype=np.int64)
+        threshold = np.asarray(threshold, dtype=np.float64)
+        left = np.asarray(left, dtype=np.int64)
+        right = np.asarray(right, dtype=np.int64)
+        value = np.asarray(value, dtype=np.float64)
+        roots = np.asarray(roots, dtype=np.int64)
+        if roots.size == 0:
+            raise ValueError("forest has no trees")
+        placed = []  # (tree, node, heap index, level)
+        D = 1
+        for t, root in enumerate(roots):
+            stack = [(int(root), 0, 0)]
+            while stack:
+                nd, h, lv = stack.pop()
+                placed.append((t, nd, h, lv))
+                if feature[nd] < 0:
+                    D = max(D, lv)
+                    continue
+                if lv >= DAL_REG_MAX_DEPTH:
+                    raise ValueError(f"tree depth exceeds DAL_REG_MAX_DEPTH={DAL_REG_MAX_DEPTH}")
+                stack.append((int(left[nd]), 2 * h + 1, lv + 1))
+                stack.append((int(right[nd]), 2 * h + 2, lv + 1))
+        n_inner, n_leaf = (1 << D) - 1, 1 << D
+        T = roots.size
+        inner_feature = np.zeros((T, n_inner), dtype=np.int32)
+        inner_threshold = np.full((T, n_inner), np.inf, dtype=np.float64)
+        leaf = np.zeros((T, n_leaf), dtype=np.float64)
+        for t, nd, h, lv in placed:
+            if feature[nd] < 0:
+                span = 1 << (D - lv)  # the leaves below heap position h
+                first_leaf = (h + 1) * span - 1 - n_inner
+                leaf[t, first_leaf:first_leaf + span] = value[nd]
+            else:
+                inner_feature[t, h] = feature[nd]
+                inner_threshold[t, h] = threshold[nd]
+        return cls(inner_feature=inner_feature, inner_threshold=inner_threshold, leaf=leaf, depth=D)
+
+    @classmethod
+    def from_sklearn(cls, rf) -> "RegressionForest":
+        """From a fitted ``sklearn.ensemble.RandomForestRegressor`` (single
+        output): a leaf predicts ``tree_.value[node, 0, 0]``."""
+        feat, thr, lft, rgt, val, roots = [], [], [], [], [], []
+        base = 0
+        for est in rf.estimators_:
+            tr = est.tree_
+            roots.append(base)
+            cl = np.asarray(tr.children_left)
+            cr = np.asarray(tr.children_right)
+            is_leaf = cl < 0
+            feat.append(np.where(is_leaf, -1, tr.feature))
+            thr.append(np.where(is_leaf, 0.0, tr.threshold))
+            lft.append(np.where(is_leaf, -1, cl + base))
+            rgt.append(np.where(is_leaf, -1, cr + base))
+            val.append(np.asarray(tr.value[:, 0, 0], dtype=np.float64))
+            base += tr.node_count
+        return cls.from_nodes(np.concatenate(feat), np.concatenate(thr), np.concatenate(lft), np.concatenate(rgt),
+                              np.concatenate(val), np.array(roots))
+
+    @classmethod
+    def from_mllib_debug_string(cls, text: str) -> "RegressionForest":
+        """Parse ``RandomForestModel.toDebugString()`` of a regression model:
+        the classifier's grammar (Forest.from_mllib_debug_string) with
+        ``Predict: <double>`` at the leaves; continuous splits only."""
+        return cls.from_nodes(*_parse_mllib_debug_string(text, float))
+
+    @classmethod
+    def from_mllib_saved(cls, path: str) -> "RegressionForest":
+        """Read an MLlib ``RandomForestModel.save(sc, path)`` directory of a
+        regression model (what ``RandomForestModel.load`` reads,
+        active_learner.py:361): NodeData ``predict.predict`` is the leaf's
+        double."""
+        return cls.from_nodes(*_read_mllib_saved(path, float))
+
+    @classmethod
+    def synthetic(cls, n_trees: int, depth: int, n_features: int, seed: int = 1,
+                  dist: str = "uniform") -> "RegressionForest":
+        """TR complete depth-``depth`` trees for tests and scripts: feature ~
+        U{0..n_features-1}, threshold ~ U(0,1) ("uniform") or N(0,1) in fp64,
+        leaf = +-10^e with e ~ U{-8..3} and a random sign -- magnitudes 11
+        decades apart, so a sum taken in another order differs in its bits."""
+        if not 1 <= depth <= DAL_REG_MAX_DEPTH:
+            raise ValueError(f"depth must lie in [1, {DAL_REG_MAX_DEPTH}], not {depth}")
+        rng = np.random.default_rng(seed)
+        n_inner, n_leaf = (1 << depth) - 1, 1 << depth
+        inner_feature = rng.integers(0, n_features, size=(n_trees, n_inner)).astype(np.int32)
+        inner_threshold = rng.random((n_trees, n_inner)) if dist == "uniform" \
+            else rng.standard_normal((n_trees, n_inner))
+        e = rng.integers(-8, 4, size=(n_trees, n_leaf))
+        sign = np.where(rng.random((n_trees, n_leaf)) < 0.5, -1.0, 1.0)
+        leaf = sign * np.power(10.0, e.astype(np.float64))
+        return cls(inner_feature=inner_feature, inner_threshold=inner_threshold.astype(np.float64),
+                   leaf=leaf, depth=depth)

@@ -94,11 +94,16 @@ class LoopResult:
 def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
              window_size: int = 10, n_estimators: int = 10, max_iterations=None,
              seed: int = 0, select_fn=None, device=None, beta: float = 1.0,
-             verbose: bool = False, trainer="gpu", num_classes=None) -> LoopResult:
+             verbose: bool = False, trainer="gpu", num_classes=None, lal_model=None) -> LoopResult:
     """Run the AL loop.  strategy: "uncertainty" (uncertainty_sampling.py),
     "density" (density_weighting.py, E = L0 = range(window_size)),
     "information_density" (class entropy x density, E = L0;
-    density_weighting.select_multiclass) or "random".
+    density_weighting.select_multiclass), "lal" (ActiveLearnerLAL.selectNext,
+    lal_direct_mllib_implementation/classes/active_learner.py:240-343:
+    dal.active_learner.select_lal with ``lal_model``, a
+    dal.forest.RegressionForest over the five LAL features; binary only; the
+    labeled count and its positives come from the current labeled set) or
+    "random".
     trainer: see train_forest.  Labels of more than two values: "uncertainty"
     and "information_density" score the C-class forest
     (Forest.from_sklearn(rf, multiclass=True)) and need trainer="sklearn" or a
@@ -129,6 +134,11 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     if (multiclass or (num_classes is not None and int(num_classes) > 2)) and strategy == "density":
         raise ValueError("strategy='density' is binary only: y holds more than two label values "
                          "(use strategy='uncertainty')")
+    if strategy == "lal":
+        if multiclass or (num_classes is not None and int(num_classes) > 2):
+            raise ValueError("strategy='lal' is binary only: y holds more than two label values")
+        if lal_model is None and select_fn is None:
+            raise ValueError("strategy='lal' needs lal_model= (a dal.forest.RegressionForest)")
     if multiclass and trainer == "gpu" and num_classes is None:
         raise ValueError("trainer='gpu' (dal.random_forest) trains binary forests only unless num_classes= is "
                          "given: y holds more than two label values (pass num_classes=, or use "
@@ -188,6 +198,10 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
             elif strategy == "information_density":
                 from .density_weighting import select_multiclass
                 sel = select_multiclass(state, unlabeled, forest, k, beta=beta)
+            elif strategy == "lal":
+                from .active_learner import select_lal
+                sel = select_lal(state, unlabeled, forest, lal_model, k, n_labeled=len(labeled),
+                                 n_positive=int(np.asarray(y)[lab].sum()))
             else:
                 raise ValueError(f"unknown strategy {strategy!r}")
             chosen = sel.indices.cpu().numpy()

@@ -699,3 +699,86 @@ def _score_keys_asc(s):
     s = torch.where(s == 0, torch.zeros_like(s), s)
     b = s.view(torch.int64)
     return torch.where(b < 0, ~b, b | (-(1 << 63)))
+
+
+# ------------------------------------------------------------------ LAL --
+def _lal_local_topk(sel: ShardedSelector, flags, votes, hist_global, forest, lal_model, k: int, n_labeled: int,
+                    n_positive: int) -> LocalTopk:
+    """A rank's LAL scores from the GLOBAL vote histogram (every rank computes
+    the same T + 1 rows and the same LUT) and its exact local top-k."""
+    from .engine import lal_scores, topk_keys
+
+    torch = __import__("torch")
+    st = sel.state
+    out = LocalTopk(torch.full((k,), _as_i64(DAL_KEY_NONE), dtype=torch.int64, device=st.device),
+                    torch.full((k,), -1, dtype=torch.int64, device=st.device),
+                    torch.full((k,), float("nan"), dtype=torch.float64, device=st.device))
+    if st.n == 0:
+        return out
+    _, sc, kys = lal_scores(st, forest, lal_model, flags, votes, hist_global, n_labeled, n_positive)
+    kk = min(k, st.n)
+    i, kk_keys = topk_keys(kys, kk, st.row_base)
+    out.keys[:kk], out.idx[:kk], out.scores[:kk] = kk_keys, i, sc[i - st.row_base]
+    return out
+
+
+def _lal_local_votes(sel: ShardedSelector, unl, forest):
+    """(flags, votes, local vote histogram int64 [T + 1]) of a rank's shard."""
+    from .engine import lal_votes
+
+    torch = __import__("torch")
+    st = sel.state
+    if st.n == 0:
+        return None, None, torch.zeros(forest.n_trees + 1, dtype=torch.int64, device=st.device)
+    flags, _, _ = st.row_flags(unl)
+    votes, hist = lal_votes(st, forest, flags)
+    return flags, votes, hist
+
+
+def select_lal(sel: ShardedSelector, comm, unlabeled_idx, forest, lal_model, k: int, n_labeled: int,
+               n_positive: int, sort_fn=hip_sort_positions):
+    """One LAL selection step across all ranks (dal.active_learner.select_lal
+    row-sharded); returns (indices [k], scores [k]), identical on every rank
+    and for every P.  Each rank takes its shard's votes and vote histogram;
+    the histograms are summed by ONE all_reduce of T + 1 int64 (integers: the
+    same bits in any order); every rank then builds the same rows and LUT,
+    rescores its rows and keeps its local top-k, merged as mode "us" does."""
+    from .engine import check_lal_inputs
+
+    check_lal_inputs(forest, lal_model, n_labeled, n_positive)
+    unl = sel.index_tensor(unlabeled_idx)
+    n_unl_global = int(unl.shape[0])
+    if n_unl_global == 0:
+        raise ValueError("unlabeled set is empty (the reference loop breaks here)")
+    flags, votes, hist = _lal_local_votes(sel, unl, forest)
+    comm.dist.all_reduce(hist, group=comm.group)  # SUM
+    top = _lal_local_topk(sel, flags, votes, hist, forest, lal_model, k, n_labeled, n_positive)
+    if sort_fn is hip_sort_positions and sel.world * k <= _lib.DAL_SORT_CAP and top.keys.is_cuda:
+        out, _ = merge_packed(comm, top, sel.status_word(), k, all_valid=n_unl_global >= k)
+        return out
+    keys_all, idx_all, sc_all = gather_topk(comm, top)
+    return merge_topk(keys_all, idx_all, sc_all, k, sort_fn, all_valid=n_unl_global >= k)
+
+
+def emulate_lal(selectors, unlabeled_idx, forest, lal_model, k: int, n_labeled: int, n_positive: int,
+                sort_fn=hip_sort_positions):
+    """select_lal with P shards in one process (tests): the all_reduce becomes
+    a sum, the all-gather a concatenation."""
+    from .engine import check_lal_inputs
+
+    torch = __import__("torch")
+    check_lal_inputs(forest, lal_model, n_labeled, n_positive)
+    unls = [s.index_tensor(unlabeled_idx) for s in selectors]
+    n_unl = int(unls[0].shape[0])
+    if n_unl == 0:
+        raise ValueError("unlabeled set is empty (the reference loop breaks here)")
+    local = [_lal_local_votes(s, u, forest) for s, u in zip(selectors, unls)]
+    hist = local[0][2].clone()
+    for _, _, h in local[1:]:
+        hist += h.to(hist.device)
+    tops = [_lal_local_topk(s, fl, v, hist.to(s.state.device), forest, lal_model, k, n_labeled, n_positive)
+            for s, (fl, v, _) in zip(selectors, local)]
+    keys_all = torch.cat([t.keys for t in tops])
+    idx_all = torch.cat([t.idx for t in tops])
+    sc_all = torch.cat([t.scores for t in tops])
+    return merge_topk(keys_all, idx_all, sc_all, k, sort_fn, all_valid=n_unl >= k)

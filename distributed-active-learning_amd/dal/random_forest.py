@@ -224,3 +224,26 @@ def predict(forest: Forest, X, device=None):
     lut = engine.device_lut("least_confidence", forest.n_trees, state.device)
     votes, _, _, _ = engine.forest_score(state, forest, lut, state.flags, DAL_ASCENDING)
     return (2 * votes > forest.n_trees).to(torch.uint8), votes
+
+
+def predict_regression(model, X, device=None):
+    """RandomForestModel.predict of a regression model (MLlib's
+    ``trees.map(predict).sum / numTrees``, active_learner.py:319) on the GPU:
+    fp64 [n], sequential fp64 sum in tree order.  ``model``: a
+    dal.forest.RegressionForest; X: a PoolState, or an fp32 or fp64 [n, d]
+    array or tensor (compared as fp64 against the model's fp64 thresholds)."""
+    import torch
+
+    from . import engine
+
+    if isinstance(X, engine.PoolState):
+        return engine.forest_regress(model, X.x, X.n, X.d, X.d, X.device, f64=False)
+    dev = engine._require_cuda(device)
+    x = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X))
+    if x.dim() != 2:
+        raise ValueError("X must be a 2-D [rows, features] array")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise ValueError("X must be fp32 or fp64")
+    x = x.to(dev).contiguous()
+    return engine.forest_regress(model, x, int(x.shape[0]), int(x.shape[1]), int(x.shape[1]), dev,
+                                 f64=x.dtype == torch.float64)

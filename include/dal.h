@@ -798,6 +798,78 @@ int dal_rf_train_multiclass(const float* x, int64_t n, int64_t d, int64_t ldx, c
                             int32_t* out_inner, uint8_t* out_leaf, void* ws, size_t ws_bytes,
                             dal_stream_t stream);
 
+/* ---- regression forests: RandomForestModel.predict of a regressor ---------
+ * lal_direct_mllib_implementation/classes/active_learner.py:319 (the LAL
+ * model, RandomForest.trainRegressor(numTrees=2000) at :363) and MLlib's
+ * trees.map(predict).sum / numTrees.  New symbols only: dal_abi_version()
+ * stays 10 (absent from older libraries; probe with
+ * dal_forest_regress_chunk_trees).  The forest is a complete heap of depth
+ * ``depth`` <= DAL_REG_MAX_DEPTH per tree (dal.forest.RegressionForest):
+ *   inner_feature[t][h] int32, inner_threshold[t][h] fp64 (the model's value,
+ *   NOT rounded), h < 2^depth - 1;  leaf[t][l] fp64, l < 2^depth;
+ *   row[feature] <= threshold -> child 2h+1, else 2h+2 (an fp64 compare: a NaN
+ *   feature goes right); a shallow leaf's subtree is padded with (0, +inf)
+ *   splits and carries its value.
+ * x: n rows of d features, row stride ldx elements, fp32 (DAL_X_F32, compared
+ * as (double)x <= threshold) or fp64 (DAL_X_F64).
+ *   out[i] = (((0.0 + leaf_0(x_i)) + leaf_1(x_i)) + ... + leaf_{T-1}(x_i)) / (double)T
+ * sequential fp64 adds in tree order, one division: bit for bit the Python
+ * float loop, for every n, d and n_trees.  The kernel streams the forest
+ * through LDS dal_forest_regress_chunk_trees(depth) trees at a time (0 for a
+ * depth outside [1, DAL_REG_MAX_DEPTH]; non-increasing in depth); a row is
+ * summed by one lane from the first tree to the last.
+ * n == 0 returns DAL_OK and launches nothing.  Before any launch: a null
+ * pointer or an x_dtype other than the two is DAL_ERR_ARG, depth outside
+ * [1, DAL_REG_MAX_DEPTH] DAL_ERR_UNSUPPORTED, n_trees < 1, n < 0, d < 1 or
+ * ldx < d DAL_ERR_SHAPE.  A feature outside [0, d) is the caller's error (the
+ * forest is device data; RegressionForest.check_features checks it before
+ * upload): the kernel clamps it into [0, d - 1]. */
+#define DAL_REG_MAX_DEPTH 10
+#define DAL_X_F32 0
+#define DAL_X_F64 1
+int dal_forest_regress_chunk_trees(int32_t depth);
+int dal_forest_regress(const void* x, int x_dtype, int64_t n, int64_t d, int64_t ldx,
+                       const int32_t* inner_feature, const double* inner_threshold, const double* leaf,
+                       int32_t n_trees, int32_t depth, double* out, dal_stream_t stream);
+
+/* ---- LAL query scores from the forest votes --------------------------------
+ * active_learner.py:240-343 (ActiveLearnerLAL.selectNext).  The regressor's
+ * five features depend on an unlabeled row through its vote count v alone, so
+ * its prediction is a table of T + 1 entries (T = n_trees of the classifier,
+ * 1 <= T <= DAL_LAL_MAX_TREES, else DAL_ERR_UNSUPPORTED):
+ *   votes (dal_forest_score) -> dal_vote_histogram -> dal_lal_rows ->
+ *   dal_forest_regress over the T + 1 rows -> dal_votes_rescore -> dal_topk,
+ * stream-ordered.  New symbols only: dal_abi_version() stays 10.
+ *
+ * dal_vote_histogram: hist[v] += #{ i < n : votes[i] == v, row i a
+ * DAL_ROW_CANDIDATE } (row_flags NULL: every row counts).  It ACCUMULATES (the
+ * caller zeroes hist [T + 1] first), so shards and repeated calls compose;
+ * integer atomics, exact in any order.  A vote outside [0, T] is counted
+ * nowhere.
+ *
+ * dal_lal_rows: rows[v] = {f1[v], f2[v], f3, f6, f8} for v = 0..T (the column
+ * order of active_learner.py:356) from the (all-reduced) histogram, with
+ *   nU = sum_v hist[v] (int64),
+ *   f6 = (((0.0 + (double)hist[0] * f2[0]) + (double)hist[1] * f2[1]) + ...
+ *         + (double)hist[T] * f2[T]) / (double)nU
+ * multiply then add, no FMA, ascending v (:292 in histogram form); nU == 0
+ * writes NaN.  f1, f2: fp64 [T + 1] (dal.active_learner.lal_tables).
+ *
+ * dal_votes_rescore: scores[i] = lut[votes[i]] (fp64 [T + 1]; NaN for a vote
+ * outside [0, T]) and keys[i] = dal_forest_score's key of that score for
+ * ``order``, DAL_KEY_NONE when the row is not DAL_ROW_CANDIDATE (row_flags
+ * NULL: every row is one).  5 bytes read per row: no second forest pass.
+ * n == 0 returns DAL_OK and launches nothing; a null pointer or a bad order
+ * is DAL_ERR_ARG, n_trees < 1 DAL_ERR_SHAPE (dal_votes_rescore) or
+ * DAL_ERR_UNSUPPORTED (the other two), before any launch. */
+#define DAL_LAL_MAX_TREES 4095
+int dal_vote_histogram(const int32_t* votes, const uint8_t* row_flags, int64_t n, int32_t n_trees,
+                       int64_t* hist, dal_stream_t stream);
+int dal_lal_rows(const int64_t* hist, const double* f1, const double* f2, int32_t n_trees, double f3, double f8,
+                 double* rows, dal_stream_t stream);
+int dal_votes_rescore(const int32_t* votes, const uint8_t* row_flags, int64_t n, const double* lut,
+                      int32_t n_trees, int order, double* scores, uint64_t* keys, dal_stream_t stream);
+
 /* ---- standalone similarity kernels --------------------------------------
  * cosine_similarity.py:42-45: every entry of U.U^T (fp32 MFMA), written to
  * out[n_pad][n_pad] (fp32).  similarity.py:38 (columnSimilarities, i<j) is
