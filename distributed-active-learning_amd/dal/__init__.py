@@ -16,5 +16,7 @@ include/dal.h); importing this package does not require a GPU, calling it does.
 """
 from .forest import Forest, RegressionForest  # noqa: F401
 from .luts import STRATEGIES, lut  # noqa: F401
+from .random_forest import train_regressor  # noqa: F401
+from .active_learner import train_lal_model  # noqa: F401
 
 __version__ = "0.1.0"

@@ -51,6 +51,8 @@ DAL_REG_MAX_DEPTH = 10
 DAL_X_F32 = 0
 DAL_X_F64 = 1
 DAL_LAL_MAX_TREES = 4095
+DAL_RF_REG_MAX_LIMBS = 8
+DAL_RF_MAX_SPLIT_SAMPLE_F64 = 8192
 
 # name -> (restype, argtypes); every symbol of include/dal.h
 SIGNATURES = {
@@ -202,6 +204,16 @@ SIGNATURES = {
     "dal_forest_regress_chunk_trees": (c_int, [c_int32]),
     "dal_forest_regress": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                    c_int32, c_int32, c_void_p, c_void_p]),
+    "dal_rf_find_splits_f64": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dal_rf_bin_rows": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
+    "dal_rf_train_regressor_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                                          c_int32]),
+    "dal_rf_train_regressor": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                       c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_int32, c_int32,
+                                       c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                       c_void_p]),
     "dal_vote_histogram": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "dal_lal_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_double, c_double, c_void_p, c_void_p]),
     "dal_votes_rescore": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int, c_void_p, c_void_p,

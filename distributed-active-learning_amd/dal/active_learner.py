@@ -75,4 +75,31 @@ def select_lal(pool, unlabeled_idx, forest: Forest, lal_model: RegressionForest,
     return lal_step(state, unlabeled_idx, forest, lal_model, k, n_labeled, n_positive)
 
 
-__all__ = ["lal_tables", "select_lal", "Selection", "RegressionForest"]
+LAL_FEATURE_COLUMNS = (0, 1, 2, 5, 7)  # active_learner.py:356; the label is the last column
+
+
+def lal_training_set(table):
+    """(X fp64 [n, 5], y fp64 [n]) from the LAL regression table
+    (active_learner.py:354-356): an [n, >= 9] array, or the path of a text
+    file of whitespace-separated numbers, one row per line.  Features are
+    columns 0, 1, 2, 5, 7 and the label is the last column."""
+    is_path = isinstance(table, (str, bytes)) or hasattr(table, "__fspath__")
+    t = np.loadtxt(table, dtype=np.float64, ndmin=2) if is_path else np.asarray(table, dtype=np.float64)
+    if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 9:
+        raise ValueError("the LAL table must be a non-empty [n, >= 9] array")
+    return np.ascontiguousarray(t[:, list(LAL_FEATURE_COLUMNS)]), np.ascontiguousarray(t[:, -1])
+
+
+def train_lal_model(table, num_trees: int = 2000, **kwargs) -> RegressionForest:
+    """The LAL regressor of active_learner.py:354-363,
+    ``RandomForest.trainRegressor(reg, numTrees=2000, categoricalFeaturesInfo={})``,
+    trained on the GPU (dal.random_forest.train_regressor; ``kwargs`` are its
+    keyword arguments).  The result is what ``select_lal`` and
+    ``run_loop(strategy="lal", lal_model=...)`` take."""
+    from .random_forest import train_regressor
+
+    X, y = lal_training_set(table)
+    return train_regressor(X, y, num_trees=num_trees, **kwargs)
+
+
+__all__ = ["lal_tables", "select_lal", "train_lal_model", "lal_training_set", "Selection", "RegressionForest"]

@@ -20,6 +20,12 @@ layout the selection kernels consume, already resident on the device.
 ``num_classes`` > 2 (MLlib's numClasses) takes the C-class level kernels of
 csrc/rf_train_multi.hip (dal_rf_train_multiclass): up to DAL_MC_MAX_CLASSES
 classes and DAL_MC_MAX_TREES trees; the binary path is untouched.
+
+``train_regressor`` is MLlib's ``RandomForest.trainRegressor`` (variance
+impurity; the LAL model of lal_direct_mllib_implementation/classes/
+active_learner.py:354-363) through csrc/rf_train_regress.hip: the same growth
+with exact variance sums (include/dal.h), fp32 or fp64 rows and fp64
+thresholds, into a ``dal.forest.RegressionForest``.
 """
 from __future__ import annotations
 
@@ -29,8 +35,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import (DAL_FLAG_RF_SPLITS, DAL_MC_MAX_CLASSES, DAL_MC_MAX_TREES, DAL_RF_MAX_DEPTH,
-                   DAL_RF_MAX_SPLIT_SAMPLE, DAL_RF_MAX_SPLITS, DAL_RF_SPLIT_LDS_BYTES, call)
-from .forest import Forest
+                   DAL_RF_MAX_SPLIT_SAMPLE, DAL_RF_MAX_SPLIT_SAMPLE_F64, DAL_RF_MAX_SPLITS, DAL_RF_REG_MAX_LIMBS,
+                   DAL_RF_SPLIT_LDS_BYTES, call)
+from .forest import Forest, RegressionForest
 
 
 def feature_subset_size(n_features: int, n_trees: int, strategy: str = "auto") -> int:
@@ -202,6 +209,189 @@ def train_classifier(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: in
     forest._dev[str(dev)] = (inner, leaf)
     forest.split_thresholds = (thresholds, n_splits)
     return forest
+
+
+# ---------------------------------------------------------------- regression
+LIMB_BITS = 31  # csrc/rf_exact_sum.hpp
+
+
+def regression_subset_strategy(n_trees: int, strategy: str = "auto") -> str:
+    """featureSubsetStrategy of trainRegressor: "auto" is "all" for one tree
+    and "onethird" for a forest; every other name stands for itself."""
+    if strategy == "auto":
+        return "all" if n_trees == 1 else "onethird"
+    return strategy
+
+
+def regression_subset_size(n_features: int, n_trees: int, strategy: str = "auto") -> int:
+    """Features per node of a regression forest: ceil(d / 3) for "auto" with
+    more than one tree, d for one tree; the other names as feature_subset_size."""
+    return feature_subset_size(n_features, n_trees, regression_subset_strategy(n_trees, strategy))
+
+
+def exact_sum_format(values):
+    """(Q, K, span) of a vector of finite doubles for the exact accumulator
+    (csrc/rf_exact_sum.hpp): Q the exponent of the lowest set bit over the
+    nonzero values, span = (the exponent above the highest set bit) - Q, K =
+    max(1, ceil(span / 31)) limbs.  (0, 1, 0) when every value is zero."""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    v = v[v != 0.0]
+    if v.size == 0:
+        return 0, 1, 0
+    mant, exp = np.frexp(v)  # |mant| in [0.5, 1): the highest set bit has exponent exp - 1
+    m = np.abs(mant * 9007199254740992.0).astype(np.int64)  # 53-bit integers, exact
+    low_bit = m & -m
+    tz = np.log2(low_bit.astype(np.float64)).astype(np.int64)  # powers of two: exact
+    q = int((exp.astype(np.int64) - 53 + tz).min())
+    span = int(exp.max()) - q
+    return q, max(1, -(-span // LIMB_BITS)), span
+
+
+def check_regression_labels(y, n: int):
+    """The labels as n finite doubles and the two accumulator formats
+    ((Q, K) of y, (Q, K) of fl(y * y)), or ValueError.  Pure host code."""
+    yv = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+    if yv.shape[0] != n:
+        raise ValueError(f"labels must be {n} values, one per row")
+    if not np.isfinite(yv).all():
+        raise ValueError("labels must be finite")
+    with np.errstate(over="ignore"):
+        sq = yv * yv
+    if not np.isfinite(sq).all():
+        raise ValueError("a label's square overflows fp64")
+    fmt = []
+    for what, v in (("labels", yv), ("squared labels", sq)):
+        q, k, span = exact_sum_format(v)
+        if k > DAL_RF_REG_MAX_LIMBS:
+            raise ValueError(f"the {what} span {span} bits between their highest and lowest set bit, more than the "
+                             f"{DAL_RF_REG_MAX_LIMBS * LIMB_BITS} the exact variance sums hold")
+        if q + span + LIMB_BITS > 1023:
+            raise ValueError(f"a weighted sum of the {what} could overflow fp64")
+        fmt.append((q, k))
+    return yv, fmt[0], fmt[1]
+
+
+def check_tree_weights(weights) -> np.ndarray:
+    """Bagging weights as int32 [T, n] >= 0 whose per-tree sums stay below
+    2^31 (the exact sums' 64-bit words cannot overflow then), or ValueError."""
+    w = np.asarray(weights)
+    if w.ndim != 2 or (w.size and w.min() < 0):
+        raise ValueError("weights must be a non-negative [T, n] array")
+    tot = w.sum(axis=1, dtype=np.int64)
+    if tot.size and int(tot.max()) >= 1 << 31:
+        raise ValueError(f"a tree's weights sum to {int(tot.max())}: the GPU trainer needs less than 2^31")
+    return np.ascontiguousarray(w, dtype=np.int32)
+
+
+def regression_split_sample_rows(n: int, max_bins: int, seed: int, f64: bool):
+    """split_sample_rows with the row limit of the fp64 threshold search."""
+    cap = DAL_RF_MAX_SPLIT_SAMPLE_F64 if f64 else DAL_RF_MAX_SPLIT_SAMPLE
+    required = max(max_bins * max_bins, 10000)
+    if n <= required and n <= cap:
+        return None
+    rng = np.random.default_rng(seed + 0x5EED)
+    rows = np.nonzero(rng.random(n) < min(required, cap) / float(n))[0]
+    return rows[:cap].astype(np.int64)
+
+
+def train_regressor(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: int = 32, seed: int = 0,
+                    feature_subset_strategy: str = "auto", weights=None, feature_subsets=None,
+                    min_instances_per_node: int = 1, min_info_gain: float = 0.0, device=None,
+                    tree_chunk=None) -> RegressionForest:
+    """RandomForest.trainRegressor(categoricalFeaturesInfo={},
+    impurity="variance") on the GPU (csrc/rf_train_regress.hip): X [n, d] fp32
+    or fp64 (numpy or torch; fp64 rows train unrounded), y [n] real labels.
+    ``weights`` [T, n] / ``feature_subsets`` [T, 2^max_depth - 1, m] override
+    the seeded draws (bagging_inputs with regression's "auto" = onethird).
+    The variance sums are exact (include/dal.h), so the result is the same
+    bytes on every run and for every ``tree_chunk`` (trees per launch; None
+    bounds the workspace at about 256 MiB).  The RegressionForest is resident
+    on the device; ``split_thresholds`` holds (thresholds fp64 [d, 255],
+    n_splits int32 [d]) there."""
+    import torch
+
+    is_t = isinstance(X, torch.Tensor)
+    xs = X if is_t else np.asarray(X)
+    if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] < 1:
+        raise ValueError("training set must be a non-empty 2-D [rows, features] array")
+    n, d = int(xs.shape[0]), int(xs.shape[1])
+    if not 1 <= max_depth <= DAL_RF_MAX_DEPTH:
+        raise ValueError(f"max_depth must lie in [1, {DAL_RF_MAX_DEPTH}]")
+    if not 2 <= max_bins <= DAL_RF_MAX_SPLITS:
+        raise ValueError(f"max_bins must lie in [2, {DAL_RF_MAX_SPLITS}]")
+    yv, (q_y, k_y), (q_sq, k_sq) = check_regression_labels(y.cpu().numpy() if isinstance(y, torch.Tensor) else y, n)
+    if weights is None or feature_subsets is None:
+        w_draw, s_draw = bagging_inputs(n, d, num_trees, max_depth, seed,
+                                        regression_subset_strategy(num_trees, feature_subset_strategy))
+        weights = w_draw if weights is None else weights
+        feature_subsets = s_draw if feature_subsets is None else feature_subsets
+    w_np = check_tree_weights(weights)
+    sub_np = np.ascontiguousarray(feature_subsets, dtype=np.int32)
+    T = int(w_np.shape[0])
+    n_inner = (1 << max_depth) - 1
+    if T < 1 or w_np.shape != (T, n) or sub_np.ndim != 3 or sub_np.shape[:2] != (T, n_inner):
+        raise ValueError(f"weights must be [T, {n}] and feature_subsets [T, {n_inner}, m]")
+    m = int(sub_np.shape[2])
+    if not 1 <= m <= d or sub_np.min() < 0 or sub_np.max() >= d:
+        raise ValueError("feature subsets must hold 1..d features in [0, d)")
+    ns = num_splits(n, max_bins)
+    W = 1 + k_y + k_sq
+    need = m * (ns + 2) * W * 8
+    if need > DAL_RF_SPLIT_LDS_BYTES:
+        raise ValueError(f"{m} candidate features per node x {ns + 1} thresholds x {W} words need {need} bytes of "
+                         f"split histogram, more than the GPU trainer's {DAL_RF_SPLIT_LDS_BYTES} "
+                         "(lower max_bins or use a smaller feature subset)")
+
+    from .engine import _require_cuda
+
+    dev = _require_cuda(device)
+    lib = _lib.load()
+    if is_t:
+        x = X.to(dev) if X.dtype == torch.float64 else X.to(device=dev, dtype=torch.float32)
+    else:
+        host_dtype = np.float64 if xs.dtype == np.float64 else np.float32
+        x = torch.from_numpy(np.ascontiguousarray(xs, dtype=host_dtype)).to(dev)
+    x = x.contiguous()
+    f64 = x.dtype == torch.float64
+    x_dtype = _lib.DAL_X_F64 if f64 else _lib.DAL_X_F32
+    rows = regression_split_sample_rows(n, max_bins, seed, f64)
+    n_sample = n if rows is None else int(rows.shape[0])
+    rows_t = None if rows is None else torch.from_numpy(rows).to(dev)
+    thresholds = torch.empty((d, DAL_RF_MAX_SPLITS), dtype=torch.float64, device=dev)
+    n_splits = torch.empty(d, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    bins = torch.empty((n, d), dtype=torch.uint8, device=dev)
+    s = _stream(dev)
+    call("dal_rf_find_splits_f64", x.data_ptr(), x_dtype, n, d, d, 0 if rows_t is None else rows_t.data_ptr(),
+         n_sample, ns, thresholds.data_ptr(), n_splits.data_ptr(), status.data_ptr(), s)
+    call("dal_rf_bin_rows", x.data_ptr(), x_dtype, n, d, d, thresholds.data_ptr(), n_splits.data_ptr(),
+         bins.data_ptr(), s)
+    y_t = torch.from_numpy(yv).to(dev)
+    if tree_chunk is None:
+        per_tree = int(lib.dal_rf_train_regressor_workspace_bytes(n, 1, max_depth, m, ns, k_y, k_sq)) + 4 * n
+        tree_chunk = max(1, (256 << 20) // per_tree)
+    tree_chunk = max(1, min(int(tree_chunk), T))
+    wsb = int(lib.dal_rf_train_regressor_workspace_bytes(n, tree_chunk, max_depth, m, ns, k_y, k_sq))
+    ws = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
+    wsp = (ws.data_ptr() + 255) // 256 * 256
+    feat = torch.empty((T, n_inner), dtype=torch.int32, device=dev)
+    thr = torch.empty((T, n_inner), dtype=torch.float64, device=dev)
+    leaf = torch.empty((T, n_inner + 1), dtype=torch.float64, device=dev)
+    for t0 in range(0, T, tree_chunk):
+        t1 = min(T, t0 + tree_chunk)
+        w_t = torch.from_numpy(w_np[t0:t1]).to(dev)
+        sub_t = torch.from_numpy(sub_np[t0:t1]).to(dev)
+        call("dal_rf_train_regressor", bins.data_ptr(), n, d, y_t.data_ptr(), thresholds.data_ptr(),
+             n_splits.data_ptr(), ns, w_t.data_ptr(), sub_t.data_ptr(), m, t1 - t0, max_depth,
+             int(min_instances_per_node), float(min_info_gain), q_y, k_y, q_sq, k_sq, feat[t0:t1].data_ptr(),
+             thr[t0:t1].data_ptr(), leaf[t0:t1].data_ptr(), wsp, wsb, s)
+    if int(status.item()) & DAL_FLAG_RF_SPLITS:
+        raise _lib.DalError("threshold search emitted more than num_splits + 1 thresholds")
+    model = RegressionForest(inner_feature=feat.cpu().numpy(), inner_threshold=thr.cpu().numpy(),
+                             leaf=leaf.cpu().numpy(), depth=max_depth)
+    model._dev[str(dev)] = (feat, thr, leaf)
+    model.split_thresholds = (thresholds, n_splits)
+    return model
 
 
 def predict(forest: Forest, X, device=None):

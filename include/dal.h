@@ -832,6 +832,79 @@ int dal_forest_regress(const void* x, int x_dtype, int64_t n, int64_t d, int64_t
                        const int32_t* inner_feature, const double* inner_threshold, const double* leaf,
                        int32_t n_trees, int32_t depth, double* out, dal_stream_t stream);
 
+/* ---- GPU training of regression forests: exact variance histograms --------
+ * RandomForest.trainRegressor(data, categoricalFeaturesInfo={}, numTrees=T,
+ * featureSubsetStrategy="auto", impurity="variance", maxDepth=4, maxBins=32)
+ * (lal_direct_mllib_implementation/classes/active_learner.py:354-365; Spark 2.1
+ * MLlib, continuous features).  New symbols only: dal_abi_version() stays 10
+ * (absent from older libraries).
+ *
+ * As in dal_rf_train: thresholds are findSplitsForContinuousFeature, bins are
+ * #{thresholds < x}, split k sends bin <= k left; integer bagging weights
+ * [T][n] and per-node feature subsets [T][2^D - 1][m] are inputs; growth is
+ * level-wise; the best split is the first maximum over subset order then split
+ * index; a node is a leaf when gain <= 0 (or no valid split) or at max_depth; a
+ * child is created as a leaf at max_depth or when its impurity == 0.0; a child
+ * with a weighted count < min_instances makes a split invalid, and so does
+ * gain < min_info_gain.  For regression "auto" means every feature for one
+ * tree and ceil(d / 3) for a forest (the caller sizes m).
+ *
+ * Statistics of a row set R (the canonical semantics):
+ *   count = sum_R w (integer), sum = RN(sum_R w y), sumSq = RN(sum_R w fl(y y)),
+ * the sums EXACT and RN one rounding to nearest-even fp64.  Left statistics of
+ * split k: the rows with bin <= k; right: the exact node sums minus the exact
+ * left sums, rounded once (not a difference of rounded values).
+ *   impurity = 0 when count == 0, else (sumSq - (sum sum) / count) / count
+ *   gain     = impurity - (lc/tc) imp_l - (rc/tc) imp_r
+ *   leaf     = sum / count (0 when count == 0)
+ * in fp64 in that operation order, no FMA.  This departs from Spark's bits on
+ * purpose: Spark adds fl(fl(w y) y) terms in partition order, so its own sums
+ * vary in the last places from run to run (and, under cancellation such as
+ * labels 1e8 + small, so do its trees); the exact sum is the value every such
+ * order approximates, and it makes the fit independent of the order in which
+ * atomics arrive.
+ *
+ * The exact sums (csrc/rf_exact_sum.hpp): the caller describes the labels by
+ * (q_y, k_y) and their squares fl(y y) by (q_sq, k_sq): q is the exponent of
+ * the lowest set bit over the nonzero values (0 when there are none), and
+ * k = max(1, ceil(span / 31)) limbs of 31 bits cover span = (exponent above
+ * the highest set bit) - q bits.  k <= DAL_RF_REG_MAX_LIMBS (a span of 248
+ * bits; smooth labels need 2 + 3 limbs, labels eleven decades apart 3 + 5),
+ * and every tree's weights must sum to less than 2^31 so that no 64-bit word
+ * overflows.  A q above a value's lowest set bit, a k too small or a
+ * non-finite label is the caller's error (dal.random_forest.train_regressor
+ * computes and checks them).
+ *
+ * dal_rf_find_splits_f64 / dal_rf_bin_rows: dal_rf_find_splits and the binning
+ * for rows x [n][ldx] of fp32 (DAL_X_F32) or fp64 (DAL_X_F64): thresholds
+ * [d][DAL_RF_MAX_SPLITS] fp64 (the widening of fp32 values is exact; fp64 rows
+ * are never rounded), bins [n][d] uint8.  n_sample <= DAL_RF_MAX_SPLIT_SAMPLE
+ * for fp32 rows, DAL_RF_MAX_SPLIT_SAMPLE_F64 for fp64 rows (the sort's LDS).
+ *
+ * dal_rf_train_regressor: bins [n][d], y [n] fp64 -> dal_forest_regress's heap
+ * layout: out_feature int32 and out_threshold fp64 [T][2^D - 1], out_leaf fp64
+ * [T][2^D]; (0, +inf) below a leaf, a shallow leaf's value repeated over its
+ * subtree.  Limits, DAL_ERR_UNSUPPORTED before any HIP call: max_depth <=
+ * DAL_RF_MAX_DEPTH, 1 <= k <= DAL_RF_REG_MAX_LIMBS and -1074 <= q <= 1023, and
+ * one node's cells in LDS: m * (num_splits + 2) * (1 + k_y + k_sq) * 8 <=
+ * DAL_RF_SPLIT_LDS_BYTES.  ws: 256-B aligned,
+ * dal_rf_train_regressor_workspace_bytes(...) bytes (0 for bad arguments). */
+#define DAL_RF_REG_MAX_LIMBS 8            /* 31-bit limbs per exact sum: label spans up to 248 bits */
+#define DAL_RF_MAX_SPLIT_SAMPLE_F64 8192  /* rows one fp64 threshold search sorts in LDS */
+int dal_rf_find_splits_f64(const void* x, int x_dtype, int64_t n, int64_t d, int64_t ldx,
+                           const int64_t* sample_rows, int64_t n_sample, int32_t num_splits, double* thresholds,
+                           int32_t* n_splits, int32_t* dev_status, dal_stream_t stream);
+int dal_rf_bin_rows(const void* x, int x_dtype, int64_t n, int64_t d, int64_t ldx, const double* thresholds,
+                    const int32_t* n_splits, uint8_t* bins, dal_stream_t stream);
+size_t dal_rf_train_regressor_workspace_bytes(int64_t n, int32_t n_trees, int32_t max_depth, int32_t m,
+                                              int32_t num_splits, int32_t k_y, int32_t k_sq);
+int dal_rf_train_regressor(const uint8_t* bins, int64_t n, int64_t d, const double* y, const double* thresholds,
+                           const int32_t* n_splits, int32_t num_splits, const int32_t* weights,
+                           const int32_t* feature_subsets, int32_t m, int32_t n_trees, int32_t max_depth,
+                           int32_t min_instances, double min_info_gain, int32_t q_y, int32_t k_y, int32_t q_sq,
+                           int32_t k_sq, int32_t* out_feature, double* out_threshold, double* out_leaf, void* ws,
+                           size_t ws_bytes, dal_stream_t stream);
+
 /* ---- LAL query scores from the forest votes --------------------------------
  * active_learner.py:240-343 (ActiveLearnerLAL.selectNext).  The regressor's
  * five features depend on an unlabeled row through its vote count v alone, so
