@@ -19,6 +19,7 @@ DAL_FLAG_ZERO_NORM = 1
 DAL_FLAG_CAND_OVERFLOW = 2
 DAL_FLAG_RF_SPLITS = 4
 DAL_FLAG_SAMPLE_MISS = 8
+DAL_FLAG_NONFINITE = 16
 DAL_ROW_CANDIDATE = 1
 DAL_ROW_EXCLUDED = 2
 DAL_DENSITY_NONE = 0
@@ -218,6 +219,13 @@ SIGNATURES = {
     "dal_lal_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_double, c_double, c_void_p, c_void_p]),
     "dal_votes_rescore": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int, c_void_p, c_void_p,
                                   c_void_p]),
+    "dal_scaler_rows_per_block": (c_int64, [c_int64, c_int64]),
+    "dal_scaler_limbs": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dal_scaler_format": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dal_scaler_accumulate": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int32, c_int32, c_void_p,
+                                      c_void_p]),
+    "dal_scaler_transform": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int,
+                                     c_int64, c_void_p]),
 }
 
 _lib = None

@@ -94,7 +94,8 @@ class LoopResult:
 def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
              window_size: int = 10, n_estimators: int = 10, max_iterations=None,
              seed: int = 0, select_fn=None, device=None, beta: float = 1.0,
-             verbose: bool = False, trainer="gpu", num_classes=None, lal_model=None) -> LoopResult:
+             verbose: bool = False, trainer="gpu", num_classes=None, lal_model=None,
+             initial_labeled=None) -> LoopResult:
     """Run the AL loop.  strategy: "uncertainty" (uncertainty_sampling.py),
     "density" (density_weighting.py, E = L0 = range(window_size)),
     "information_density" (class entropy x density, E = L0;
@@ -119,6 +120,11 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
 
     ``select_fn(strategy, pool, unlabeled, model, k) -> indices`` can replace
     the GPU step (tests use the oracle); by default the dal GPU path runs.
+
+    initial_labeled: the rows the loop starts from, in that order (distinct
+    indices in [0, n); dal.dataset.Dataset.set_start_state gives the LAL
+    classes' start); ``unlabeled`` is the ascending remainder and, for the
+    density strategies, E is that set.  None: labeled = range(window_size).
     """
     from .forest import Forest
 
@@ -146,15 +152,22 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     # class ids for the GPU trainer: the label's position in np.unique(y)
     y_fit = np.searchsorted(classes, np.asarray(y)) if num_classes is not None and trainer == "gpu" else y
     n = X.shape[0]
-    labeled = list(range(min(window_size, n)))
-    unlabeled = np.arange(len(labeled), n, dtype=np.int64)
+    if initial_labeled is None:
+        labeled = list(range(min(window_size, n)))
+        unlabeled = np.arange(len(labeled), n, dtype=np.int64)
+    else:
+        start = np.asarray(initial_labeled, dtype=np.int64).reshape(-1)
+        if start.size == 0 or start.min() < 0 or start.max() >= n or np.unique(start).size != start.size:
+            raise ValueError("initial_labeled must hold distinct row indices in [0, n)")
+        labeled = [int(i) for i in start]
+        unlabeled = np.setdiff1d(np.arange(n, dtype=np.int64), start, assume_unique=True)
     res = LoopResult()
     rng = np.random.default_rng(seed)
     state = test_state = None
     if select_fn is None and strategy != "random":
         from .engine import PoolState
 
-        excluded = np.arange(len(labeled)) if strategy in ("density", "information_density") else None
+        excluded = np.asarray(labeled, dtype=np.int64) if strategy in ("density", "information_density") else None
         state = PoolState(X, excluded=excluded, device=device)
     it = 1
     while True:

@@ -782,3 +782,79 @@ def emulate_lal(selectors, unlabeled_idx, forest, lal_model, k: int, n_labeled: 
     idx_all = torch.cat([t.idx for t in tops])
     sc_all = torch.cat([t.scores for t in tops])
     return merge_topk(keys_all, idx_all, sc_all, k, sort_fn, all_valid=n_unl >= k)
+
+
+# --------------------------------------------------------- StandardScaler --
+def _device_moments(x_local, fmt=None):
+    """The local steps of fit_scaler on the GPU (dal.dataset): fmt None ->
+    (low, top, nonfinite) of the shard; fmt = (q, k1, k2) -> its cells."""
+    from . import dataset as ds
+
+    torch = __import__("torch")
+    x, n, d, ldx = ds._device_rows(x_local)
+    if fmt is None:
+        low, top, status = ds.device_format(x, n, d, ldx)
+        return low, top, (status & _lib.DAL_FLAG_NONFINITE).ne(0).to(torch.int32)
+    q, k1, k2 = fmt
+    return ds.device_accumulate(x, n, d, ldx, q, k1, k2)
+
+
+def _scaler_model(cells_and_n, q, k1: int, k2: int, with_mean: bool, with_std: bool):
+    """The host finish from the summed cells, the total row count in the last word."""
+    from . import dataset as ds
+
+    buf = cells_and_n.cpu().numpy()
+    n = int(buf[-1])
+    if n > ds.MAX_ROWS:
+        raise ValueError(f"{n} rows in total: the exact sums take at most {ds.MAX_ROWS}")
+    mean, std = ds.moments_from_cells(buf[:-1], q, k1, k2, n)
+    return ds.StandardScalerModel(mean, std, n, with_mean, with_std)
+
+
+def _cells_and_rows(cells, n_local: int):
+    torch = __import__("torch")
+    return torch.cat([cells.reshape(-1), torch.tensor([n_local], dtype=torch.int64, device=cells.device)])
+
+
+def fit_scaler(x_local, comm, accumulate_fn=None, with_mean: bool = True, with_std: bool = True):
+    """dal.dataset.StandardScaler.fit over row shards: the same mean and std
+    bytes on every rank and for every P.  All-reduce MIN of the columns' lowest
+    set bits and MAX of their tops (int32, with the non-finite flag), the local
+    accumulate, ONE all-reduce SUM of the int64 cells (with the row count),
+    then every rank finishes alike.  An empty shard [0, d] is legal.
+    accumulate_fn(x_local, fmt): the two local steps (tests inject the
+    restatement; None: the HIP kernels) -- fmt None returns (low, top,
+    nonfinite flag), fmt = (q, k1, k2) returns the shard's cells [d, k1 + k2]."""
+    from . import dataset as ds
+
+    torch = __import__("torch")
+    dist = comm.dist
+    fn = accumulate_fn or _device_moments
+    low, top, bad = fn(x_local, None)
+    low = low.clone()
+    hi = torch.cat([top.reshape(-1), torch.as_tensor(bad, dtype=torch.int32, device=top.device).reshape(1)])
+    dist.all_reduce(low, op=dist.ReduceOp.MIN, group=comm.group)
+    dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=comm.group)
+    hi = hi.cpu().numpy()
+    k1, k2, q = ds.check_format(low.cpu().numpy(), hi[:-1], int(hi[-1]))
+    buf = _cells_and_rows(fn(x_local, (q, k1, k2)), int(x_local.shape[0]))
+    dist.all_reduce(buf, group=comm.group)  # SUM
+    return _scaler_model(buf, q, k1, k2, with_mean, with_std)
+
+
+def emulate_fit_scaler(shards, accumulate_fn=None, with_mean: bool = True, with_std: bool = True):
+    """fit_scaler with P shards in one process (tests): each all-reduce
+    becomes an elementwise min / max / sum over the shards."""
+    from . import dataset as ds
+
+    torch = __import__("torch")
+    fn = accumulate_fn or _device_moments
+    fmts = [fn(s, None) for s in shards]
+    low = torch.stack([f[0] for f in fmts]).amin(dim=0)
+    top = torch.stack([f[1] for f in fmts]).amax(dim=0)
+    k1, k2, q = ds.check_format(low.cpu().numpy(), top.cpu().numpy(), max(int(f[2]) for f in fmts))
+    buf = None
+    for s in shards:
+        b = _cells_and_rows(fn(s, (q, k1, k2)), int(s.shape[0]))
+        buf = b.clone() if buf is None else buf + b.to(buf.device)
+    return _scaler_model(buf, q, k1, k2, with_mean, with_std)

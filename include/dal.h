@@ -56,6 +56,7 @@ enum dal_status {
 #define DAL_FLAG_CAND_OVERFLOW 2  /* re-rank candidate set exceeded capacity */
 #define DAL_FLAG_RF_SPLITS 4      /* a feature produced more than num_splits + 1 thresholds */
 #define DAL_FLAG_SAMPLE_MISS 8    /* fast top-k level 1 over capacity: re-run with level1_passes = 0 */
+#define DAL_FLAG_NONFINITE 16     /* dal_scaler_format met a NaN or an infinity */
 
 /* per-row flags (uint8 per pool row) */
 #define DAL_ROW_CANDIDATE 1 /* row is in the unlabeled set and may be selected */
@@ -942,6 +943,82 @@ int dal_lal_rows(const int64_t* hist, const double* f1, const double* f2, int32_
                  double* rows, dal_stream_t stream);
 int dal_votes_rescore(const int32_t* votes, const uint8_t* row_flags, int64_t n, const double* lut,
                       int32_t n_trees, int order, double* scores, uint64_t* keys, dal_stream_t stream);
+
+/* ---- StandardScaler: exact column moments ----------------------------------
+ * lal_direct_mllib_implementation/classes/dataset.py:163-173 (every Dataset*
+ * class): MLlib's StandardScaler(withMean=True, withStd=True) over each split.
+ * New symbols only: dal_abi_version() stays 10.
+ *
+ * Canonical semantics.  x: fp32 [n][ldx], d columns, finite.  Per column c,
+ * with S1 = sum_i x_ic and S2 = sum_i x_ic^2 as EXACT rationals (an fp32 value
+ * is a dyadic rational m 2^e, m < 2^24; its square m^2 2^(2e) has at most 48
+ * mantissa bits) and RN64 one rounding to nearest-even fp64:
+ *   mean = RN64(S1 / n)
+ *   var  = RN64((n S2 - S1^2) / (n (n - 1)))   for n >= 2;  0.0 for n == 1
+ *          (MLlib's summarizer returns zero variance when n - 1 is not
+ *          positive); the numerator is never negative, so var >= 0
+ *   std  = sqrt(var), IEEE fp64: the unbiased sample deviation, as in MLlib
+ *   z    = (double(x) - mean) * (1.0 / std)  if std != 0.0, else +0.0
+ *          (the dense withMean && withStd branch of MLlib 2.1's
+ *          StandardScalerModel.transform), fp64, two roundings, no FMA;
+ *          without the mean: double(x) * (1.0 / std); without the deviation:
+ *          double(x) - mean
+ *   out  = RN32(z) (the double rounding is the definition), or z as fp64.
+ * The bits do not depend on the row order, on chunking or on sharding: the
+ * sums are integers.  MLlib itself pins no bits (its summarizer merges
+ * partition summaries in arrival order); these values are what every such
+ * order approximates.
+ *
+ * The exact sums (csrc/scaler_exact.hpp over csrc/rf_exact_sum.hpp).  Column c
+ * is described by low[c], the minimum over its nonzero values of the lowest
+ * set bit's exponent, and top[c], the maximum of (the top bit's exponent) + 1
+ * (|x| < 2^top); a column of zeros keeps INT32_MAX / INT32_MIN.  The quantum
+ * of S1 is 2^q[c] with q[c] = low[c] (0 for a column of zeros), that of S2 is
+ * 2^(2 q[c]).  K1 = max_c ceil((top - low) / 31) limbs hold x / 2^q, K2 =
+ * max_c ceil(2 (top - low) / 31) limbs hold x^2 / 2^(2q) (each at least 1).
+ * Boundary: K2 <= DAL_RF_REG_MAX_LIMBS, i.e. top[c] - low[c] <= 124 bits
+ * between a column's lowest and highest set bit.  2^-40 beside 2^20 spans 61
+ * bits and passes; an fp32 subnormal (2^-149) beside 1.0 spans 150 and is
+ * refused with DAL_ERR_UNSUPPORTED, never answered wrongly.
+ *
+ * dal_scaler_format: low[c] = min(low[c], ...), top[c] = max(top[c], ...) over
+ * the call's rows (int32 atomics; the caller initialises them to INT32_MAX /
+ * INT32_MIN, so chunks and shards compose: MIN / MAX are the all-reduce ops),
+ * and *dev_status |= DAL_FLAG_NONFINITE when a NaN or an infinity was met.
+ *
+ * dal_scaler_limbs: host function over HOST arrays low, top [d] -> *k1, *k2,
+ * q[d] (nullable) and *bad_column (nullable; -1, or the first column over the
+ * boundary, with DAL_ERR_UNSUPPORTED as the status).
+ *
+ * dal_scaler_accumulate: cells[c][0 .. k1) += limbs of x_ic / 2^q[c] and
+ * cells[c][k1 .. k1 + k2) += limbs of x_ic^2 / 2^(2 q[c]) over the call's
+ * rows; cells int64 [d][k1 + k2], zeroed by the caller once: calls add, so a
+ * pool can be fed in chunks or by shards (SUM is the all-reduce op).  Each
+ * word stays below 2^31 * (rows in total), so the total must be <= INT32_MAX
+ * rows.  q (device) must not exceed a value's lowest set bit and k1, k2 must
+ * cover the spans: both come from the format pass; a non-finite value is the
+ * caller's error.  One 64-bit integer atomic per (block, column, word);
+ * dal_scaler_rows_per_block(n, d) gives the rows of one block (0 for bad
+ * arguments).
+ *
+ * dal_scaler_transform: out[i][c] (fp32 for DAL_X_F32, fp64 for DAL_X_F64,
+ * row stride ldo elements) = the z above with factor[c] = 1.0 / std, or 0.0
+ * where std == 0.0 (then +0.0 is written).  mean NULL: no centring; factor
+ * NULL: no scaling.
+ *
+ * Before any launch: a null pointer or a bad out_dtype is DAL_ERR_ARG; n < 0,
+ * n > INT32_MAX, d < 1, ldx < d or ldo < d DAL_ERR_SHAPE; k1 or k2 outside
+ * [1, DAL_RF_REG_MAX_LIMBS] DAL_ERR_UNSUPPORTED.  n == 0 returns DAL_OK and
+ * launches nothing (the cells are untouched). */
+int64_t dal_scaler_rows_per_block(int64_t n, int64_t d);
+int dal_scaler_limbs(const int32_t* low, const int32_t* top, int64_t d, int32_t* k1, int32_t* k2, int32_t* q,
+                     int64_t* bad_column);
+int dal_scaler_format(const float* x, int64_t n, int64_t d, int64_t ldx, int32_t* low, int32_t* top,
+                      int32_t* dev_status, dal_stream_t stream);
+int dal_scaler_accumulate(const float* x, int64_t n, int64_t d, int64_t ldx, const int32_t* q, int32_t k1,
+                          int32_t k2, int64_t* cells, dal_stream_t stream);
+int dal_scaler_transform(const float* x, int64_t n, int64_t d, int64_t ldx, const double* mean,
+                         const double* factor, void* out, int out_dtype, int64_t ldo, dal_stream_t stream);
 
 /* ---- standalone similarity kernels --------------------------------------
  * cosine_similarity.py:42-45: every entry of U.U^T (fp32 MFMA), written to
