@@ -88,18 +88,32 @@
   auto b_off = [&](int c) { return b_base + ((c * C::LG) ^ b_swz); };
 
   typename C::acc4 mc[C::NCH][C::RT];
+  constexpr bool kDefer = C::FOLD_PAIRS > 1;  // chains over several pairs (round 15, below)
   // the fp4 form's scale register, the same for both operands (read by no other form)
   [[maybe_unused]] const int mx_scale = kFp4ScaleWord;
   // one stage of SC columns; fresh = first stage of a fold group (the chains
-  // restart).  B fragments go through two register sets: k-step i+1's are
+  // restart; never with deferred folds, whose chains are zeroed at the fold
+  // instead).  B fragments go through two register sets: k-step i+1's are
   // read while k-step i's 16 MFMAs issue.
   // (ct0, ct1: the stage's column tiles of this call -- the wide form runs a
   // stage in two calls, see the pair loop; the last fragment read by the first
   // waits in bh for the second)
   f16x8 bh[2];
   auto compute = [&](int buf, bool fresh_stage, int ct0 = 0, int ct1 = C::NCT) {
+    // (deferred folds: the chains occupy their registers over the whole pair
+    // loop, so the B offsets are formed anew from the lane id here instead of
+    // being kept across it -- see fresh_lane())
+    [[maybe_unused]] int bb = 0, bs = 0;
+    if constexpr (kDefer) {
+      const int fl = static_cast<int>(fresh_lane()), fli = fl & 15, flq = fl >> 4;
+      bb = fli * C::SLOTS + (flq ^ (C::swz(fli) & 3));
+      bs = C::swz(fli) & ~3;
+    }
     auto load_b = [&](int set, int c, int ct) {
-      bh[set] = __builtin_bit_cast(f16x8, lds[buf * C::F4 + ct * 16 * C::SLOTS + b_off(c)]);
+      if constexpr (kDefer)
+        bh[set] = __builtin_bit_cast(f16x8, lds[buf * C::F4 + ct * 16 * C::SLOTS + bb + ((c * C::LG) ^ bs)]);
+      else
+        bh[set] = __builtin_bit_cast(f16x8, lds[buf * C::F4 + ct * 16 * C::SLOTS + b_off(c)]);
     };
     if (ct0 == 0) load_b(0, 0, 0);
 #pragma unroll
@@ -143,6 +157,12 @@
   // (the wide form's 16 tiles in two rounds), so a row's integer does not
   // depend on which form held its chain.
   auto fold_rows = [&]() {
+    [[maybe_unused]] int fli = 0, flq = 0;
+    if constexpr (kDefer) {  // (as in compute())
+      const int fl = static_cast<int>(fresh_lane());
+      fli = fl & 15;
+      flq = fl >> 4;
+    }
 #pragma unroll
     for (int ch = 0; ch < C::NCH; ++ch)
 #pragma unroll
@@ -158,11 +178,27 @@
         for (int k = 0; k < 4; ++k) x[k] = swap_add<true>(x[k], x[k + 4]);
 #pragma unroll
         for (int k = 0; k < 2; ++k) x[k] = swap_add<false>(x[k], x[k + 2]);
-        const int row = wave * C::RPW + (t0 + 2 * (lq & 1) + 4 * (lq >> 1)) * 16 + li;
+        const int row = kDefer ? wave * C::RPW + (t0 + 2 * (flq & 1) + 4 * (flq >> 1)) * 16 + fli
+                               : wave * C::RPW + (t0 + 2 * (lq & 1) + 4 * (lq >> 1)) * 16 + li;
         C::row_add(&rowacc[row], x[0]);
         C::row_add(&rowacc[row + 16], x[1]);
       }
   };
+  // The integer forms' chains run over up to C::FOLD_PAIRS pairs of a row unit
+  // (round 15): no stage restarts them; they are zero before the first pair
+  // and after every fold, and `pending` (wave-uniform) counts the pairs they
+  // hold.  One compute() serves every pair -- the fp16 forms keep fresh stages
+  // and the fold at the end of each pair.
+  static_assert(!kDefer || (C::WIDE && C::SPP == 1 && DAL_GRAM_STAGGER > 0), "deferred folds: the wide form's pair loop");
+  [[maybe_unused]] int pending = 0;
+  [[maybe_unused]] auto zero_chains = [&]() {
+    const typename C::acc4 zero = {};
+#pragma unroll
+    for (int ch = 0; ch < C::NCH; ++ch)
+#pragma unroll
+      for (int rt = 0; rt < C::RT; ++rt) mc[ch][rt] = zero;
+  };
+  if constexpr (kDefer) zero_chains();
   auto flush_one = [&](typename C::racc_t& slot, int64_t out_row) {
     const typename C::racc_t v = slot;
     if (v != 0) atomicAdd(acc_out + out_row, static_cast<unsigned long long>(static_cast<long long>(v)));
@@ -278,10 +314,21 @@
           look_ahead();
         } else {
           if (lead) look_ahead();
-          compute(buf, true, 0, DAL_GRAM_STAGGER);
+          compute(buf, !kDefer, 0, DAL_GRAM_STAGGER);
           if (!lead) look_ahead();
-          compute(buf, true, DAL_GRAM_STAGGER, C::NCT);
-          fold_rows();
+          compute(buf, !kDefer, DAL_GRAM_STAGGER, C::NCT);
+          if constexpr (kDefer)
+            ++pending;
+          else
+            fold_rows();
+        }
+        if constexpr (kDefer) {
+          // (every wave is past its look-ahead: rows_change is the announced pair's)
+          if (fold_due(pending, C::FOLD_PAIRS, cur.rows_change)) {  // (gram_schedule.hpp)
+            fold_rows();
+            zero_chains();
+            pending = 0;
+          }
         }
         buf ^= 1;
         continue;

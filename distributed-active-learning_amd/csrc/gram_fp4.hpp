@@ -52,6 +52,24 @@ static_assert(kFp4Step == kI8Step && kFp4AccShift == kI8AccShift, "the unit of G
 static_assert(kFp4ChainMax == 589824 && 4 * kFp4ChainMax < (1 << 24),
               "fp32 chains and a lane's four columns are exact");
 static_assert(kFp4RowMax == 9437184 && kFp4RowMax < (1LL << 31), "int32 row sums");
+// Chains that run over R pairs of one row unit before they are folded (round
+// 15; Cfg::FOLD_PAIRS in gram_sym.hip): an element is at most R kFp4ChainMax,
+// whatever the codes.  With the fold's one conversion per tile the lane's four
+// elements are added in fp32 first, so 4 R kFp4ChainMax must stay below 2^24:
+// R <= 7.  Converting each element first needs R kFp4ChainMax < 2^24 alone (R
+// <= 28), and the int32 row sum R kFp4RowMax < 2^31 is then far away as well.
+// (scripts/mfma_chain_probe.py checks the instruction's adder on chains of
+// these lengths and values.)
+constexpr long long kFp4ExactBelow = 1LL << 24;  // every integer of smaller magnitude is an fp32
+constexpr int kFp4FoldPairsMax = 7;
+constexpr int kFp4FoldPairsMaxEach = 28;
+static_assert(4LL * kFp4FoldPairsMax * kFp4ChainMax < kFp4ExactBelow &&
+                  4LL * (kFp4FoldPairsMax + 1) * kFp4ChainMax >= kFp4ExactBelow,
+              "a lane's fp32 sum of four chain elements over R pairs");
+static_assert(1LL * kFp4FoldPairsMaxEach * kFp4ChainMax < kFp4ExactBelow &&
+                  1LL * (kFp4FoldPairsMaxEach + 1) * kFp4ChainMax >= kFp4ExactBelow &&
+                  1LL * kFp4FoldPairsMaxEach * kFp4RowMax < (1LL << 31),
+              "one fp32 chain element over R pairs, and the int32 row sum");
 
 // a4(h): the signed element of G
 DAL_FP4_HD inline int quant_fp4(float h) {

@@ -23,6 +23,18 @@ namespace dal {
 constexpr float kI8Step = 32.0f;     // H units per int8 step
 constexpr int kI8AccShift = 18;      // an int32 row sum s adds s << 18 to the accumulator (32 * 32 * 2^8)
 
+// One row's int32 sum over a pair's 256 columns x 128 features, whatever the
+// bytes: dal_quant_i8 writes -127..127, but the Gram entry point takes any
+// operand, and a byte may be -128.  Chains that run over R pairs of one row
+// unit before they are folded (round 15; Cfg::FOLD_PAIRS in gram_sym.hip) need
+// R kI8RowMax < 2^31: R <= 3.  (With |a| <= 127 alone, 256 x 128 x 127^2 =
+// 528,515,072, four pairs would fit; the fourth is given up for the byte -128.)
+constexpr long long kI8RowMax = 256LL * 128 * 128 * 128;
+constexpr int kI8FoldPairsMax = 3;
+static_assert(kI8RowMax == (1LL << 29) && kI8FoldPairsMax * kI8RowMax < (1LL << 31) &&
+                  (kI8FoldPairsMax + 1) * kI8RowMax >= (1LL << 31),
+              "int32 row sums over R pairs");
+
 DAL_I8_HD inline int quant_i8(float h) {
   const float q = __builtin_rintf(h * (1.0f / kI8Step));
   return static_cast<int>(q > 127.0f ? 127.0f : q >= -127.0f ? q : -127.0f);  // (a NaN: -127, a defined value)

@@ -299,6 +299,20 @@ struct GramClaimCursor {
 // the next write to its word (tests/test_gram_pipe_schedule.py walks this).
 DAL_HD constexpr int lookahead_tiles(int wave, int waves, int stagger) { return wave < waves / 2 ? 0 : stagger; }
 
+// When a wave of the integer forms folds its row chains (round 15).  A chain
+// runs over the pairs of one row unit that the wave's half acts on; `pending`
+// counts those since the wave's last fold.  At the end of a pair's body, before
+// the barrier, the wave folds when the chain holds `cap` pairs (the most its
+// integers stay exact for: Cfg::FOLD_PAIRS) or when the rows change behind
+// this pair (peek()'s rows_change: another row unit, another slice of the same
+// rows, or the walk's end) and the chain holds anything -- also in a wave that
+// idles on this pair and acted on an earlier one of the unit.  The flush of
+// the unit's sums stays behind the next barrier, after every wave's fold
+// (tests/test_gram_fold_schedule.py walks this).
+DAL_HD constexpr bool fold_due(int pending, int cap, bool rows_change) {
+  return pending >= cap || (pending > 0 && rows_change);
+}
+
 // ---------------------------------------------------------------------------
 // Host side: pair counts and the launch's grid and column chunks.
 

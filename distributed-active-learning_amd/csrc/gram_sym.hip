@@ -118,6 +118,19 @@
 // data; scripts/mfma_rate_probe.py checks the instruction's adder on chains
 // of this length), converted to int32 at the fold; from there on the int8
 // form's integers.  The closed form is fed h' = 32 a4, l' = (H - h') + L.
+//
+// The deferred fold (round 15; the int8 and fp4 forms).  Their chains hold
+// exact integers with headroom, and a row unit's rows stay resident for a whole
+// column chunk, so a wave folds its chains once per Cfg::FOLD_PAIRS pairs it
+// acted on (fp4: 7 -- a lane's fp32 sum of four elements stays below 2^24;
+// int8: 3 -- a row's int32 sum stays below 2^31 whatever the bytes, -128
+// included) and when the rows change (fold_due in gram_schedule.hpp), instead
+// of at the end of every pair, where the fold of waves 0-3 ran with the matrix
+// pipe empty.  The chains are zeroed before the pair loop and after every fold
+// and every MFMA accumulates into them; the flush, the barriers, the ring, the
+// claims and the look-ahead are where they were, and the integers added to a
+// row are the same: the bits do not change.  The fp16 forms' fp32 chains round;
+// they fold every pair as before and compile to the same instructions.
 #include <stdlib.h>
 
 #include <mutex>
@@ -188,6 +201,15 @@ __device__ __forceinline__ unsigned fresh_lane() {
 #endif
 #ifndef DAL_GRAM_STAGGER
 #define DAL_GRAM_STAGGER 4  // wide form: column tiles waves 4-7 run before their look-ahead (waves 0-3: none); 0: every wave behind the barrier
+#endif
+#ifndef DAL_GRAM_FOLD_PAIRS_FP4
+#define DAL_GRAM_FOLD_PAIRS_FP4 7  // fp4 form: pairs of one row unit a chain takes between two folds (Cfg::FOLD_PAIRS; <= 7)
+#endif
+#ifndef DAL_GRAM_FOLD_PAIRS_I8
+#define DAL_GRAM_FOLD_PAIRS_I8 3  // int8 form: the same (<= 3)
+#endif
+#ifndef DAL_GRAM_FP4_CVT_EACH
+#define DAL_GRAM_FP4_CVT_EACH 0  // fp4 fold: convert each of a lane's four elements before the add (FOLD_PAIRS <= 28)
 #endif
 #ifndef DAL_GRAM_CHAIN_MAX
 #define DAL_GRAM_CHAIN_MAX 2048  // the longest row chain dal_density_error_bound_sym_d charges
@@ -307,6 +329,21 @@ struct Cfg {
   static_assert(!FP4 || (FOLD / 16 * KW * kFp4Max * kFp4Max == kFp4ChainMax &&
                          FOLD * KW * kFp4Max * kFp4Max == kFp4RowMax),
                 "fp32 chains of exact integers, int32 row sums");
+  // Pairs of one row unit that a chain takes between two folds (round 15).  The
+  // integer forms' chains are exact whatever their length, up to the bounds
+  // below, and a row unit's rows stay resident for a whole column chunk, so
+  // they are folded once per FOLD_PAIRS pairs (and when the rows change:
+  // fold_due in gram_schedule.hpp) instead of at the end of every pair, where
+  // the fold of waves 0-3 runs with the matrix pipe empty.  The fp32 chains of
+  // the fp16 forms round: they keep their fold per pair.  The bounds assume
+  // nothing of the operand bytes (gram_fp4.hpp, gram_i8.hpp).
+  static constexpr bool CVT_EACH = FP4 && DAL_GRAM_FP4_CVT_EACH != 0;
+  static constexpr int FOLD_PAIRS = FP4 ? DAL_GRAM_FOLD_PAIRS_FP4 : I8 ? DAL_GRAM_FOLD_PAIRS_I8 : 1;
+  static_assert(FOLD_PAIRS >= 1 && (FOLD_PAIRS == 1 || (WIDE && FOLD == 256)),
+                "chains over several pairs: the wide integer forms, one fold group per pair");
+  static_assert(!I8 || FOLD_PAIRS <= kI8FoldPairsMax, "int32 row sums over FOLD_PAIRS pairs");
+  static_assert(!FP4 || FOLD_PAIRS <= (CVT_EACH ? kFp4FoldPairsMaxEach : kFp4FoldPairsMax),
+                "fp32 chains (and a lane's fp32 sum of four) of exact integers over FOLD_PAIRS pairs");
 
   // the chains' registers and the LDS row accumulator.  fp16: fp32 chains folded
   // to multiples of 2^-32 and added as integers in fp64 (below 2^53: at most
@@ -335,8 +372,14 @@ struct Cfg {
   // of at most 4 x 589,824 = 2,359,296 < 2^24 = 16,777,216, so the fp32 adds are
   // exact (no assumption on the data: kFp4ChainMax) and one v_cvt_i32_f32 per
   // tile takes the sum as it is -- converting each element first would be four.
+  // Over FOLD_PAIRS pairs the sum of four stays below 2^24 up to 7 pairs
+  // (kFp4FoldPairsMax); CVT_EACH converts the four elements first and adds them
+  // as int32, for chains of up to kFp4FoldPairsMaxEach pairs.
   static __device__ __forceinline__ sum_t lane_sum(acc4 m) {
-    return static_cast<sum_t>((m[0] + m[1]) + (m[2] + m[3]));
+    if constexpr (CVT_EACH)
+      return (static_cast<int>(m[0]) + static_cast<int>(m[1])) + (static_cast<int>(m[2]) + static_cast<int>(m[3]));
+    else
+      return static_cast<sum_t>((m[0] + m[1]) + (m[2] + m[3]));
   }
   static __device__ __forceinline__ void row_add(racc_t* slot, sum_t x) {
     if constexpr (INT)
