@@ -226,6 +226,12 @@ SIGNATURES = {
                                       c_void_p]),
     "dal_scaler_transform": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int,
                                      c_int64, c_void_p]),
+    "dal_forest_evaluate_cells": (c_int, [c_int32, c_int32]),
+    "dal_forest_evaluate_blocked_rows": (c_int, [c_int64, c_int32, c_int32, c_int32]),
+    "dal_forest_evaluate": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                    c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dal_sq_error_format": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dal_sq_error_accumulate": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
 }
 
 _lib = None

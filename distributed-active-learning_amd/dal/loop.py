@@ -89,13 +89,14 @@ class LoopResult:
     labeled_history: list = field(default_factory=list)  # selected indices per iteration
     accuracy: list = field(default_factory=list)  # test accuracy (%) per iteration
     log: list = field(default_factory=list)
+    metrics: list = field(default_factory=list)  # dal.metrics.evaluate's dict per iteration (run_loop(measures=))
 
 
 def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
              window_size: int = 10, n_estimators: int = 10, max_iterations=None,
              seed: int = 0, select_fn=None, device=None, beta: float = 1.0,
              verbose: bool = False, trainer="gpu", num_classes=None, lal_model=None,
-             initial_labeled=None) -> LoopResult:
+             initial_labeled=None, measures=None, hist_fn=None) -> LoopResult:
     """Run the AL loop.  strategy: "uncertainty" (uncertainty_sampling.py),
     "density" (density_weighting.py, E = L0 = range(window_size)),
     "information_density" (class entropy x density, E = L0;
@@ -125,6 +126,15 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     indices in [0, n); dal.dataset.Dataset.set_start_state gives the LAL
     classes' start); ``unlabeled`` is the ascending remainder and, for the
     density strategies, E is that set.  None: labeled = range(window_size).
+
+    measures: a tuple of dal.metrics measure names ('accuracy', 'TN', 'FP',
+    'FN', 'TP', 'auc', 'confusion').  With a test split every iteration then
+    appends dal.metrics.evaluate's dict for the iteration's forest to
+    ``LoopResult.metrics`` (ActiveLearner.evaluate, active_learner.py:95-121):
+    one dal_forest_evaluate call on the test pool, uploaded once with its
+    labels; a scikit-learn model goes through Forest.from_sklearn.  hist_fn:
+    dal.metrics.evaluate's (tests inject the restatement; None: the HIP
+    kernel).  measures=None changes nothing: same calls, log and ``accuracy``.
     """
     from .forest import Forest
 
@@ -163,7 +173,7 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
         unlabeled = np.setdiff1d(np.arange(n, dtype=np.int64), start, assume_unique=True)
     res = LoopResult()
     rng = np.random.default_rng(seed)
-    state = test_state = None
+    state = test_state = test_labels = None
     if select_fn is None and strategy != "random":
         from .engine import PoolState
 
@@ -192,6 +202,27 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
                 test_state = PoolState(X_test, device=device)  # uploaded once
             pred = rf.predict(test_state if isinstance(rf, GpuForestModel) else X_test)
             acc = (1 - np.mean(pred != y_test)) * 100
+            if measures is not None:
+                from . import metrics
+
+                ev_forest = rf.forest if isinstance(rf, GpuForestModel) else rf if isinstance(rf, Forest) else \
+                    Forest.from_sklearn(rf, multiclass=True) if multiclass else Forest.from_sklearn(rf)
+                if hist_fn is not None:
+                    res.metrics.append(metrics.evaluate(ev_forest, X_test, y_test, measures, hist_fn=hist_fn))
+                else:
+                    if test_state is None:
+                        from .engine import PoolState
+
+                        test_state = PoolState(X_test, device=device)  # uploaded once
+                    if test_labels is None:  # uploaded once (the forest's classes_ do not change)
+                        import torch
+
+                        test_labels = torch.from_numpy(
+                            metrics.check_labels(y_test, test_state.n, ev_forest)).to(test_state.device)
+                    names = metrics.check_measures(measures, ev_forest.n_classes)
+                    hist = metrics.joint_histogram(ev_forest, test_state, test_labels)
+                    res.metrics.append(metrics.finish(hist.cpu().numpy(), ev_forest.n_trees, ev_forest.n_classes,
+                                                      names))
         k = min(window_size, unlabeled.size)
         if strategy == "random":
             order = np.argsort(rng.uniform(size=unlabeled.size), kind="stable")

@@ -858,3 +858,58 @@ def emulate_fit_scaler(shards, accumulate_fn=None, with_mean: bool = True, with_
         b = _cells_and_rows(fn(s, (q, k1, k2)), int(s.shape[0]))
         buf = b.clone() if buf is None else buf + b.to(buf.device)
     return _scaler_model(buf, q, k1, k2, with_mean, with_std)
+
+
+# ------------------------------------------------------------ evaluation --
+def _device_table(x_local, y_local, forest):
+    """The local step of evaluate on the GPU: the shard's joint table
+    (dal.metrics.joint_histogram), a device int64 tensor."""
+    from . import metrics
+    from .engine import PoolState
+
+    torch = __import__("torch")
+    state = x_local if isinstance(x_local, PoolState) else PoolState(x_local)
+    labels = torch.from_numpy(metrics.check_labels(y_local, state.n, forest)).to(state.device)
+    return metrics.joint_histogram(forest, state, labels, build_blocked=isinstance(x_local, PoolState))
+
+
+def _shard_table(fn, x_local, y_local, forest):
+    """One shard's table as a flat int64 tensor of the table's size."""
+    from . import metrics
+
+    torch = __import__("torch")
+    rows, cols = metrics.table_shape(forest.n_trees, forest.n_classes)
+    t = torch.as_tensor(fn(x_local, y_local, forest)).to(torch.int64).reshape(-1)
+    if t.numel() != rows * cols:
+        raise ValueError(f"a shard's table holds {t.numel()} cells, not {rows * cols}")
+    return t
+
+
+def evaluate(x_local, y_local, forest, comm, hist_fn=None, measures=("accuracy",)):
+    """dal.metrics.evaluate over row shards: every rank computes its shard's
+    joint table, ONE all_reduce SUM of the int64 cells, then every rank
+    finishes alike -- the dict is the same bytes on every rank and for every
+    P (integers: the sum does not depend on the order).  An empty shard
+    [0, d] is legal.  hist_fn(x_local, y_local, forest) -> table: the local
+    step (tests inject the restatement; None: the HIP kernel, with x_local an
+    array or a PoolState)."""
+    from . import metrics
+
+    names = metrics.check_measures(measures, forest.n_classes)
+    buf = _shard_table(hist_fn or _device_table, x_local, y_local, forest).clone()
+    comm.dist.all_reduce(buf, group=comm.group)  # SUM
+    return metrics.finish(buf.cpu().numpy(), forest.n_trees, forest.n_classes, names)
+
+
+def emulate_evaluate(shards, forest, hist_fn=None, measures=("accuracy",)):
+    """evaluate with P shards [(x, y), ...] in one process (tests): the
+    all_reduce becomes an elementwise sum over the shards."""
+    from . import metrics
+
+    names = metrics.check_measures(measures, forest.n_classes)
+    fn = hist_fn or _device_table
+    buf = None
+    for x, y in shards:
+        t = _shard_table(fn, x, y, forest)
+        buf = t.clone() if buf is None else buf + t.to(buf.device)
+    return metrics.finish(buf.cpu().numpy(), forest.n_trees, forest.n_classes, names)

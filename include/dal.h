@@ -1020,6 +1020,66 @@ int dal_scaler_accumulate(const float* x, int64_t n, int64_t d, int64_t ldx, con
 int dal_scaler_transform(const float* x, int64_t n, int64_t d, int64_t ldx, const double* mean,
                          const double* factor, void* out, int out_dtype, int64_t ldo, dal_stream_t stream);
 
+/* ---- test-set evaluation: joint histogram, exact squared error -------------
+ * lal_direct_mllib_implementation/classes/active_learner.py:95-121
+ * (ActiveLearner.evaluate: accuracy, TN / TP / FN / FP, auc) and the regressor
+ * scripts' testMSE = sum (label - prediction)^2 / count
+ * (mllib/mllib_random_forest_regressor.py:48).  New symbols only:
+ * dal_abi_version() stays 10; dal_forest_evaluate_cells is the probe (absent
+ * from older libraries).
+ *
+ * dal_forest_evaluate: one fused forest pass over the rows that writes nothing
+ * per row.  The forest, x, xb and fprep are dal_forest_score_blocked's and
+ * dal_forest_score_multiclass_blocked's (one prepared buffer serves all
+ * three); labels: one class id byte per row; a row is counted when row_flags
+ * is NULL or carries DAL_ROW_CANDIDATE (as dal_vote_histogram).  hist (int64,
+ * dal_forest_evaluate_cells(n_trees, n_classes) words):
+ *   n_classes == 2, 1 <= n_trees <= DAL_LAL_MAX_TREES: hist[T + 1][2], cell
+ *     [v][y] += rows with v trees whose leaf byte is 1 and label y;
+ *   3 <= n_classes <= DAL_MC_MAX_CLASSES, n_trees <= DAL_MC_MAX_TREES:
+ *     hist[C][C], cell [y][pred], pred = the smallest class with the most
+ *     trees (dal_forest_score_multiclass's pred);
+ *   any other (n_trees, n_classes): 0 cells, DAL_ERR_UNSUPPORTED.
+ * A row whose label is >= n_classes, or one of whose trees ends in a leaf byte
+ * >= n_classes, is counted nowhere (dal.metrics checks both before upload).
+ * The call ACCUMULATES (the caller zeroes hist), so shards and repeated calls
+ * compose: 32-bit counters per block in LDS, one 64-bit integer atomic per
+ * occupied cell per block -- exact in any order, the same words for every
+ * grid, row order and sharding.  dal_forest_evaluate_blocked_rows is the rule
+ * that picks the kernel: 64 when the score entries' rule holds
+ * (dal_forest_blocked_rows; for n_classes > 2 dal_forest_multiclass_blocked_
+ * rows) and the block's LDS with the table stays within 96 KiB; the blocked
+ * kernel then reads only the features the forest tests and needs fprep.  xb
+ * NULL, or a rule value of 0, runs the row-major kernel on x.
+ * Before any launch: a null x, inner, leaf, labels or hist is DAL_ERR_ARG;
+ * n < 0, n >= 2^32, d < 1, d > 2^30 or ldx < d DAL_ERR_SHAPE; a depth outside
+ * [1, DAL_MAX_TREE_DEPTH] or 0 cells DAL_ERR_UNSUPPORTED; then a misaligned xb
+ * (16 B), or a null or misaligned fprep where the blocked rule holds,
+ * DAL_ERR_ARG.  n == 0 returns DAL_OK and launches nothing.
+ *
+ * dal_sq_error_format / dal_sq_error_accumulate: with e_i = fl(y_i - pred_i)
+ * and s_i = fl(e_i * e_i) (two roundings, no FMA), format takes the atomic min
+ * of the lowest set bit's exponent into *low and the atomic max of the
+ * exponent above the highest set bit into *top over the nonzero s_i (the
+ * caller initialises INT32_MAX / INT32_MIN) and raises DAL_FLAG_NONFINITE in
+ * *dev_status for a non-finite s_i; accumulate adds the k limbs
+ * (csrc/rf_exact_sum.hpp) of every s_i for the quantum 2^q into cells[k] with
+ * 64-bit integer atomics (the caller zeroes; q <= *low and 31 k >= *top - q,
+ * as dal.random_forest.exact_sum_format derives them).  The exact sum is
+ * 2^q sum_j cells[j] 2^(31 j).  A null pointer is DAL_ERR_ARG, n < 0 or
+ * n > INT32_MAX DAL_ERR_SHAPE, k outside [1, DAL_RF_REG_MAX_LIMBS]
+ * DAL_ERR_UNSUPPORTED; n == 0 returns DAL_OK and launches nothing. */
+int dal_forest_evaluate_cells(int32_t n_trees, int32_t n_classes);
+int dal_forest_evaluate_blocked_rows(int64_t d, int32_t n_trees, int32_t depth, int32_t n_classes);
+int dal_forest_evaluate(const float* x, const float* xb, const void* fprep, int64_t n, int64_t d, int64_t ldx,
+                        const int32_t* inner, const uint8_t* leaf, int32_t n_trees, int32_t depth,
+                        int32_t n_classes, const uint8_t* labels, const uint8_t* row_flags, int64_t* hist,
+                        dal_stream_t stream);
+int dal_sq_error_format(const double* pred, const double* y, int64_t n, int32_t* low, int32_t* top,
+                        int32_t* dev_status, dal_stream_t stream);
+int dal_sq_error_accumulate(const double* pred, const double* y, int64_t n, int32_t q, int32_t k, int64_t* cells,
+                            dal_stream_t stream);
+
 /* ---- standalone similarity kernels --------------------------------------
  * cosine_similarity.py:42-45: every entry of U.U^T (fp32 MFMA), written to
  * out[n_pad][n_pad] (fp32).  similarity.py:38 (columnSimilarities, i<j) is
