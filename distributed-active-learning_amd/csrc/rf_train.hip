@@ -375,9 +375,11 @@ __global__ void rf_init_status_kernel(uint8_t* status, int T, int64_t n_all) {
 
 int rf_launch_bin_and_reset(const float* x, int64_t ldx, const RfArgs& A, hipStream_t st) {
   const int64_t n_inner = (int64_t{1} << A.max_depth) - 1;
-  hipLaunchKernelGGL(rf_bin_kernel, dim3(static_cast<unsigned>(std::min<int64_t>(ceil_div(A.n * A.d, 256), 4096))),
-                     dim3(256), 0, st, x, A.n, A.d, ldx, A.thresholds, A.n_splits, const_cast<uint8_t*>(A.bins));
-  DAL_RETURN_IF_LAUNCH_FAILED();
+  if (A.n > 0) {
+    hipLaunchKernelGGL(rf_bin_kernel, dim3(static_cast<unsigned>(std::min<int64_t>(ceil_div(A.n * A.d, 256), 4096))),
+                       dim3(256), 0, st, x, A.n, A.d, ldx, A.thresholds, A.n_splits, const_cast<uint8_t*>(A.bins));
+    DAL_RETURN_IF_LAUNCH_FAILED();
+  }
   // root open, everything else absent
   if (hipMemsetAsync(A.status, 0, static_cast<size_t>(A.T) * (2 * n_inner + 1), st) != hipSuccess)
     return DAL_ERR_HIP;
@@ -427,24 +429,32 @@ extern "C" size_t dal_rf_train_workspace_bytes(int64_t n, int64_t d, int32_t n_t
   return rf_layout(n, d, n_trees, max_depth, m, num_splits + 2, 2, 0).total;
 }
 
-extern "C" int dal_rf_train(const float* x, int64_t n, int64_t d, int64_t ldx, const uint8_t* labels,
-                            const float* thresholds, const int32_t* n_splits, int32_t num_splits,
-                            const int32_t* weights, const int32_t* feature_subsets, int32_t m, int32_t n_trees,
-                            int32_t max_depth, int32_t min_instances, double min_info_gain, int32_t* out_inner,
-                            uint8_t* out_leaf, void* ws, size_t ws_bytes, dal_stream_t stream) {
-  if (!x || !labels || !thresholds || !n_splits || !weights || !feature_subsets || !out_inner || !out_leaf || !ws)
-    return DAL_ERR_ARG;
-  if (n < 1 || d < 1 || ldx < d || n_trees < 1 || m < 1 || m > d) return DAL_ERR_SHAPE;
+
+namespace dal {
+
+int rf_job_setup(RfJob* J, int32_t kind, int32_t C, int64_t red_bytes, const float* x, int64_t n, int64_t d,
+                 int64_t ldx, const uint8_t* labels, const float* thresholds, const int32_t* n_splits,
+                 int32_t num_splits, const int32_t* weights, const int32_t* feature_subsets, int32_t m,
+                 int32_t n_trees, int32_t max_depth, int32_t min_instances, double min_info_gain,
+                 int32_t* out_inner, uint8_t* out_leaf, void* ws, size_t ws_bytes, int64_t min_n) {
+  if (!J || !thresholds || !n_splits || !feature_subsets || !out_inner || !out_leaf || !ws) return DAL_ERR_ARG;
+  if ((n > 0 || min_n > 0) && (!x || !labels || !weights)) return DAL_ERR_ARG;  // an empty shard has no rows to point at
+  if (n < min_n || d < 1 || ldx < d || n_trees < 1 || m < 1 || m > d) return DAL_ERR_SHAPE;
   if (max_depth < 1 || max_depth > DAL_RF_MAX_DEPTH) return DAL_ERR_UNSUPPORTED;
+  if (C < 2 || C > DAL_MC_MAX_CLASSES) return DAL_ERR_UNSUPPORTED;  // as dal_forest_score_multiclass
   if (num_splits < 0 || num_splits >= DAL_RF_MAX_SPLITS) return DAL_ERR_SHAPE;
   const int hb = num_splits + 2;  // find_splits emits at most num_splits + 1 thresholds
   // the split kernel keeps one node's whole (slot, bin, class) histogram in LDS
-  if (static_cast<int64_t>(m) * hb * 2 * 4 > DAL_RF_SPLIT_LDS_BYTES) return DAL_ERR_UNSUPPORTED;
-  const RfLayout L = rf_layout(n, d, n_trees, max_depth, m, hb, 2, 0);
+  if (static_cast<int64_t>(m) * hb * C * 4 > DAL_RF_SPLIT_LDS_BYTES) return DAL_ERR_UNSUPPORTED;
+  const RfLayout L = rf_layout(n, d, n_trees, max_depth, m, hb, C, red_bytes);
   if (ws_bytes < L.total || reinterpret_cast<uintptr_t>(ws) % 256) return DAL_ERR_SHAPE;
-  hipStream_t st = as_stream(stream);
   unsigned char* w = static_cast<unsigned char*>(ws);
-  RfArgs A{};
+  *J = RfJob{};
+  J->magic = kRfJobMagic;
+  J->kind = kind;
+  J->C = C;
+  J->red = red_bytes ? w + L.red : nullptr;
+  RfArgs& A = J->A;
   A.bins = w + L.bins;
   A.labels = labels;
   A.weights = weights;
@@ -465,35 +475,125 @@ extern "C" int dal_rf_train(const float* x, int64_t n, int64_t d, int64_t ldx, c
   A.split_f = reinterpret_cast<int32_t*>(w + L.split_f);
   A.split_b = reinterpret_cast<int32_t*>(w + L.split_b);
   A.hist = reinterpret_cast<int32_t*>(w + L.hist);
-  A.cls = reinterpret_cast<int32_t*>(w + L.cls);
+  A.cls = A.hist;
   A.out_inner = out_inner;
   A.out_leaf = out_leaf;
+  return DAL_OK;
+}
 
-  if (const int rc = rf_launch_bin_and_reset(x, ldx, A, st)) return rc;
+int rf_level_span(const void* job, int32_t kind, int32_t level, void** ptr, int32_t* elem_type, int64_t* count) {
+  RfJob J;
+  if (!ptr || !elem_type || !count) return DAL_ERR_ARG;
+  if (const int rc = rf_job_load(job, kind, level, &J)) return rc;
+  const RfArgs A = rf_at_level(J, level, count);
+  *ptr = A.cls;
+  *elem_type = DAL_RF_SPAN_I32;
+  return DAL_OK;
+}
+
+namespace {
+
+// *J is the job; it is also copied to the caller's descriptor `job` (nullable)
+// before the first device call.
+int binary_begin(RfJob* J, void* job, const float* x, int64_t n, int64_t d, int64_t ldx, const uint8_t* labels,
+                 const float* thresholds, const int32_t* n_splits, int32_t num_splits, const int32_t* weights,
+                 const int32_t* feature_subsets, int32_t m, int32_t n_trees, int32_t max_depth,
+                 int32_t min_instances, double min_info_gain, int32_t* out_inner, uint8_t* out_leaf, void* ws,
+                 size_t ws_bytes, int64_t min_n, hipStream_t st) {
+  if (const int rc = rf_job_setup(J, kRfJobBinary, 2, 0, x, n, d, ldx, labels, thresholds, n_splits, num_splits,
+                                  weights, feature_subsets, m, n_trees, max_depth, min_instances, min_info_gain,
+                                  out_inner, out_leaf, ws, ws_bytes, min_n))
+    return rc;
+  if (job) std::memcpy(job, J, sizeof *J);
+  return rf_launch_bin_and_reset(x, ldx, J->A, st);
+}
+
+// Zero the level's totals and histogram, then add the job's rows to them.
+int binary_level_stats(const RfJob& J, int level, hipStream_t st) {
+  int64_t ints = 0;
+  const RfArgs A = rf_at_level(J, level, &ints);
+  if (hipMemsetAsync(A.cls, 0, static_cast<size_t>(ints) * 4, st) != hipSuccess) return DAL_ERR_HIP;
+  if (A.n == 0) return DAL_OK;
+  const int64_t nodes = int64_t{1} << level;
+  const int64_t hist_ints = level < A.max_depth ? nodes * A.m * A.hb * 2 : 0;
   const int rows_per_block = 1024;
-  const dim3 hgrid(static_cast<unsigned>(ceil_div(n, rows_per_block)), static_cast<unsigned>(n_trees));
+  const dim3 hgrid(static_cast<unsigned>(ceil_div(A.n, rows_per_block)), static_cast<unsigned>(A.T));
+  const bool lds_hist = (2 * nodes + hist_ints) * 4 <= 64 * 1024;
+  const size_t hsmem = static_cast<size_t>(2 * nodes + (lds_hist ? hist_ints : 0)) * 4;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_hist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(hsmem)) != hipSuccess)
+    return DAL_ERR_HIP;
+  hipLaunchKernelGGL(rf_hist_kernel, hgrid, dim3(256), hsmem, st, A, level, rows_per_block, lds_hist);
+  DAL_RETURN_IF_LAUNCH_FAILED();
+  return DAL_OK;
+}
+
+// Leaf or best split of every node of the level from the workspace's sums.
+int binary_level_split(const RfJob& J, int level, hipStream_t st) {
+  int64_t ints = 0;
+  const RfArgs A = rf_at_level(J, level, &ints);
+  const size_t ssmem = level < A.max_depth ? static_cast<size_t>(A.m) * A.hb * 2 * 4 : 16;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(ssmem)) != hipSuccess)
+    return DAL_ERR_HIP;
+  hipLaunchKernelGGL(rf_split_kernel, dim3(1u << level, static_cast<unsigned>(A.T)), dim3(64), ssmem, st, A, level);
+  DAL_RETURN_IF_LAUNCH_FAILED();
+  return DAL_OK;
+}
+
+}  // namespace
+}  // namespace dal
+
+extern "C" int dal_rf_train_begin(void* job, const float* x, int64_t n_local, int64_t d, int64_t ldx,
+                                  const uint8_t* labels, const float* thresholds, const int32_t* n_splits,
+                                  int32_t num_splits, const int32_t* weights, const int32_t* feature_subsets,
+                                  int32_t m, int32_t n_trees, int32_t max_depth, int32_t min_instances,
+                                  double min_info_gain, int32_t* out_inner, uint8_t* out_leaf, void* ws,
+                                  size_t ws_bytes, dal_stream_t stream) {
+  RfJob J;
+  if (!job) return DAL_ERR_ARG;
+  return binary_begin(&J, job, x, n_local, d, ldx, labels, thresholds, n_splits, num_splits, weights, feature_subsets, m,
+                      n_trees, max_depth, min_instances, min_info_gain, out_inner, out_leaf, ws, ws_bytes, 0,
+                      as_stream(stream));
+}
+
+extern "C" int dal_rf_train_level_stats(const void* job, int32_t level, dal_stream_t stream) {
+  RfJob J;
+  if (const int rc = rf_job_load(job, kRfJobBinary, level, &J)) return rc;
+  return binary_level_stats(J, level, as_stream(stream));
+}
+
+extern "C" int dal_rf_train_level_split(const void* job, int32_t level, dal_stream_t stream) {
+  RfJob J;
+  if (const int rc = rf_job_load(job, kRfJobBinary, level, &J)) return rc;
+  return binary_level_split(J, level, as_stream(stream));
+}
+
+extern "C" int dal_rf_train_finish(const void* job, dal_stream_t stream) {
+  RfJob J;
+  if (const int rc = rf_job_load(job, kRfJobBinary, 0, &J)) return rc;
+  return rf_launch_finalize(J.A, as_stream(stream));
+}
+
+extern "C" int dal_rf_train_level_span(const void* job, int32_t level, void** ptr, int32_t* elem_type,
+                                       int64_t* count) {
+  return rf_level_span(job, kRfJobBinary, level, ptr, elem_type, count);
+}
+
+extern "C" int dal_rf_train(const float* x, int64_t n, int64_t d, int64_t ldx, const uint8_t* labels,
+                            const float* thresholds, const int32_t* n_splits, int32_t num_splits,
+                            const int32_t* weights, const int32_t* feature_subsets, int32_t m, int32_t n_trees,
+                            int32_t max_depth, int32_t min_instances, double min_info_gain, int32_t* out_inner,
+                            uint8_t* out_leaf, void* ws, size_t ws_bytes, dal_stream_t stream) {
+  RfJob J;
+  hipStream_t st = as_stream(stream);
+  if (const int rc = binary_begin(&J, nullptr, x, n, d, ldx, labels, thresholds, n_splits, num_splits, weights,
+                                  feature_subsets, m, n_trees, max_depth, min_instances, min_info_gain, out_inner,
+                                  out_leaf, ws, ws_bytes, 1, st))
+    return rc;
   for (int level = 0; level <= max_depth; ++level) {
-    const int64_t nodes = int64_t{1} << level;
-    const bool open_level = level < max_depth;
-    const int64_t hist_ints = open_level ? nodes * m * hb * 2 : 0;
-    if (hipMemsetAsync(A.cls, 0, static_cast<size_t>(n_trees * nodes * 2 * 4), st) != hipSuccess) return DAL_ERR_HIP;
-    if (open_level &&
-        hipMemsetAsync(A.hist, 0, static_cast<size_t>(n_trees * hist_ints * 4), st) != hipSuccess)
-      return DAL_ERR_HIP;
-    const bool lds_hist = (2 * nodes + hist_ints) * 4 <= 64 * 1024;
-    const size_t hsmem = static_cast<size_t>(2 * nodes + (lds_hist ? hist_ints : 0)) * 4;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_hist_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(hsmem)) != hipSuccess)
-      return DAL_ERR_HIP;
-    hipLaunchKernelGGL(rf_hist_kernel, hgrid, dim3(256), hsmem, st, A, level, rows_per_block, lds_hist);
-    DAL_RETURN_IF_LAUNCH_FAILED();
-    const size_t ssmem = open_level ? static_cast<size_t>(m) * hb * 2 * 4 : 16;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_split_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ssmem)) != hipSuccess)
-      return DAL_ERR_HIP;
-    hipLaunchKernelGGL(rf_split_kernel, dim3(static_cast<unsigned>(nodes), static_cast<unsigned>(n_trees)),
-                       dim3(64), ssmem, st, A, level);
-    DAL_RETURN_IF_LAUNCH_FAILED();
+    if (const int rc = binary_level_stats(J, level, st)) return rc;
+    if (const int rc = binary_level_split(J, level, st)) return rc;
   }
-  return rf_launch_finalize(A, st);
+  return rf_launch_finalize(J.A, st);
 }

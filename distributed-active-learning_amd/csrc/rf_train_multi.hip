@@ -258,79 +258,115 @@ extern "C" size_t dal_rf_train_multiclass_workspace_bytes(int64_t n, int64_t d, 
   return rf_layout(n, d, n_trees, max_depth, m, num_splits + 2, n_classes, kRedBytes).total;
 }
 
+namespace dal {
+namespace {
+
+// *J is the job; it is also copied to the caller's descriptor `job` (nullable)
+// before the first device call.
+int multi_begin(RfJob* J, void* job, const float* x, int64_t n, int64_t d, int64_t ldx, const uint8_t* labels,
+                const float* thresholds, const int32_t* n_splits, int32_t num_splits, const int32_t* weights,
+                const int32_t* feature_subsets, int32_t m, int32_t n_trees, int32_t max_depth, int32_t min_instances,
+                double min_info_gain, int32_t n_classes, int32_t* out_inner, uint8_t* out_leaf, void* ws,
+                size_t ws_bytes, int64_t min_n, hipStream_t st) {
+  if (const int rc = rf_job_setup(J, kRfJobMulti, n_classes, kRedBytes, x, n, d, ldx, labels, thresholds, n_splits,
+                                  num_splits, weights, feature_subsets, m, n_trees, max_depth, min_instances,
+                                  min_info_gain, out_inner, out_leaf, ws, ws_bytes, min_n))
+    return rc;
+  if (job) std::memcpy(job, J, sizeof *J);
+  return rf_launch_bin_and_reset(x, ldx, J->A, st);
+}
+
+// Zero the level's totals and histogram, then add the job's rows to them.
+int multi_level_stats(const RfJob& J, int level, hipStream_t st) {
+  int64_t ints = 0;
+  const RfArgs A = rf_at_level(J, level, &ints);
+  const int C = J.C;
+  if (hipMemsetAsync(A.cls, 0, static_cast<size_t>(ints) * 4, st) != hipSuccess) return DAL_ERR_HIP;
+  if (A.n == 0) return DAL_OK;
+  const int64_t nodes = int64_t{1} << level;
+  const int64_t hist_ints = level < A.max_depth ? nodes * A.m * A.hb * C : 0;
+  const int rows_per_block = 1024;
+  const dim3 hgrid(static_cast<unsigned>(ceil_div(A.n, rows_per_block)), static_cast<unsigned>(A.T));
+  // the budget of the binary kernel: class counts + level histogram within 64 KiB, else global atomics
+  const bool lds_hist = (C * nodes + hist_ints) * 4 <= 64 * 1024;
+  const size_t hsmem = static_cast<size_t>(C * nodes + (lds_hist ? hist_ints : 0)) * 4;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_hist_multi_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(hsmem)) != hipSuccess)
+    return DAL_ERR_HIP;
+  hipLaunchKernelGGL(rf_hist_multi_kernel, hgrid, dim3(256), hsmem, st, A, C, level, rows_per_block, lds_hist);
+  DAL_RETURN_IF_LAUNCH_FAILED();
+  return DAL_OK;
+}
+
+// Leaf or best split of every node of the level from the workspace's sums.
+int multi_level_split(const RfJob& J, int level, hipStream_t st) {
+  int64_t ints = 0;
+  const RfArgs A = rf_at_level(J, level, &ints);
+  const size_t ssmem = level < A.max_depth ? static_cast<size_t>(A.m) * A.hb * J.C * 4 : 16;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_split_multi_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ssmem)) != hipSuccess)
+    return DAL_ERR_HIP;
+  hipLaunchKernelGGL(rf_split_multi_kernel, dim3(1u << level, static_cast<unsigned>(A.T)), dim3(kSplitThreads),
+                     ssmem, st, A, J.C, J.red, level);
+  DAL_RETURN_IF_LAUNCH_FAILED();
+  return DAL_OK;
+}
+
+}  // namespace
+}  // namespace dal
+
+extern "C" int dal_rf_train_multiclass_begin(void* job, const float* x, int64_t n_local, int64_t d, int64_t ldx,
+                                             const uint8_t* labels, const float* thresholds,
+                                             const int32_t* n_splits, int32_t num_splits, const int32_t* weights,
+                                             const int32_t* feature_subsets, int32_t m, int32_t n_trees,
+                                             int32_t max_depth, int32_t min_instances, double min_info_gain,
+                                             int32_t n_classes, int32_t* out_inner, uint8_t* out_leaf, void* ws,
+                                             size_t ws_bytes, dal_stream_t stream) {
+  RfJob J;
+  if (!job) return DAL_ERR_ARG;
+  return multi_begin(&J, job, x, n_local, d, ldx, labels, thresholds, n_splits, num_splits, weights, feature_subsets, m,
+                     n_trees, max_depth, min_instances, min_info_gain, n_classes, out_inner, out_leaf, ws, ws_bytes,
+                     0, as_stream(stream));
+}
+
+extern "C" int dal_rf_train_multiclass_level_stats(const void* job, int32_t level, dal_stream_t stream) {
+  RfJob J;
+  if (const int rc = rf_job_load(job, kRfJobMulti, level, &J)) return rc;
+  return multi_level_stats(J, level, as_stream(stream));
+}
+
+extern "C" int dal_rf_train_multiclass_level_split(const void* job, int32_t level, dal_stream_t stream) {
+  RfJob J;
+  if (const int rc = rf_job_load(job, kRfJobMulti, level, &J)) return rc;
+  return multi_level_split(J, level, as_stream(stream));
+}
+
+extern "C" int dal_rf_train_multiclass_finish(const void* job, dal_stream_t stream) {
+  RfJob J;
+  if (const int rc = rf_job_load(job, kRfJobMulti, 0, &J)) return rc;
+  return rf_launch_finalize(J.A, as_stream(stream));
+}
+
+extern "C" int dal_rf_train_multiclass_level_span(const void* job, int32_t level, void** ptr, int32_t* elem_type,
+                                                  int64_t* count) {
+  return rf_level_span(job, kRfJobMulti, level, ptr, elem_type, count);
+}
+
 extern "C" int dal_rf_train_multiclass(const float* x, int64_t n, int64_t d, int64_t ldx, const uint8_t* labels,
                                        const float* thresholds, const int32_t* n_splits, int32_t num_splits,
                                        const int32_t* weights, const int32_t* feature_subsets, int32_t m,
                                        int32_t n_trees, int32_t max_depth, int32_t min_instances,
                                        double min_info_gain, int32_t n_classes, int32_t* out_inner,
                                        uint8_t* out_leaf, void* ws, size_t ws_bytes, dal_stream_t stream) {
-  if (!x || !labels || !thresholds || !n_splits || !weights || !feature_subsets || !out_inner || !out_leaf || !ws)
-    return DAL_ERR_ARG;
-  if (n < 1 || d < 1 || ldx < d || n_trees < 1 || m < 1 || m > d) return DAL_ERR_SHAPE;
-  if (max_depth < 1 || max_depth > DAL_RF_MAX_DEPTH) return DAL_ERR_UNSUPPORTED;
-  if (n_classes < 2 || n_classes > DAL_MC_MAX_CLASSES) return DAL_ERR_UNSUPPORTED;  // as dal_forest_score_multiclass
-  if (num_splits < 0 || num_splits >= DAL_RF_MAX_SPLITS) return DAL_ERR_SHAPE;
-  const int hb = num_splits + 2;  // find_splits emits at most num_splits + 1 thresholds
-  const int C = n_classes;
-  // the split kernel keeps one node's whole (slot, class, bin) histogram in LDS
-  const int64_t node_bytes = static_cast<int64_t>(m) * hb * C * 4;
-  if (node_bytes > DAL_RF_SPLIT_LDS_BYTES) return DAL_ERR_UNSUPPORTED;
-  const RfLayout L = rf_layout(n, d, n_trees, max_depth, m, hb, C, kRedBytes);
-  if (ws_bytes < L.total || reinterpret_cast<uintptr_t>(ws) % 256) return DAL_ERR_SHAPE;
+  RfJob J;
   hipStream_t st = as_stream(stream);
-  unsigned char* w = static_cast<unsigned char*>(ws);
-  RfArgs A{};
-  A.bins = w + L.bins;
-  A.labels = labels;
-  A.weights = weights;
-  A.subsets = feature_subsets;
-  A.thresholds = thresholds;
-  A.n_splits = n_splits;
-  A.n = n;
-  A.d = static_cast<int>(d);
-  A.m = m;
-  A.T = n_trees;
-  A.max_depth = max_depth;
-  A.hb = hb;
-  A.kmax = num_splits + 1;
-  A.min_instances = min_instances;
-  A.min_gain = min_info_gain;
-  A.node = reinterpret_cast<int32_t*>(w + L.node);
-  A.status = w + L.status;
-  A.split_f = reinterpret_cast<int32_t*>(w + L.split_f);
-  A.split_b = reinterpret_cast<int32_t*>(w + L.split_b);
-  A.hist = reinterpret_cast<int32_t*>(w + L.hist);
-  A.cls = reinterpret_cast<int32_t*>(w + L.cls);
-  A.out_inner = out_inner;
-  A.out_leaf = out_leaf;
-  unsigned char* red = w + L.red;
-
-  if (const int rc = rf_launch_bin_and_reset(x, ldx, A, st)) return rc;
-  const int rows_per_block = 1024;
-  const dim3 hgrid(static_cast<unsigned>(ceil_div(n, rows_per_block)), static_cast<unsigned>(n_trees));
+  if (const int rc = multi_begin(&J, nullptr, x, n, d, ldx, labels, thresholds, n_splits, num_splits, weights,
+                                 feature_subsets, m, n_trees, max_depth, min_instances, min_info_gain, n_classes,
+                                 out_inner, out_leaf, ws, ws_bytes, 1, st))
+    return rc;
   for (int level = 0; level <= max_depth; ++level) {
-    const int64_t nodes = int64_t{1} << level;
-    const bool open_level = level < max_depth;
-    const int64_t hist_ints = open_level ? nodes * (node_bytes / 4) : 0;
-    if (hipMemsetAsync(A.cls, 0, static_cast<size_t>(n_trees * nodes * C * 4), st) != hipSuccess) return DAL_ERR_HIP;
-    if (open_level &&
-        hipMemsetAsync(A.hist, 0, static_cast<size_t>(n_trees * hist_ints * 4), st) != hipSuccess)
-      return DAL_ERR_HIP;
-    // the budget of the binary kernel: class counts + level histogram within 64 KiB, else global atomics
-    const bool lds_hist = (C * nodes + hist_ints) * 4 <= 64 * 1024;
-    const size_t hsmem = static_cast<size_t>(C * nodes + (lds_hist ? hist_ints : 0)) * 4;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_hist_multi_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(hsmem)) != hipSuccess)
-      return DAL_ERR_HIP;
-    hipLaunchKernelGGL(rf_hist_multi_kernel, hgrid, dim3(256), hsmem, st, A, C, level, rows_per_block, lds_hist);
-    DAL_RETURN_IF_LAUNCH_FAILED();
-    const size_t ssmem = open_level ? static_cast<size_t>(node_bytes) : 16;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_split_multi_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ssmem)) != hipSuccess)
-      return DAL_ERR_HIP;
-    hipLaunchKernelGGL(rf_split_multi_kernel, dim3(static_cast<unsigned>(nodes), static_cast<unsigned>(n_trees)),
-                       dim3(kSplitThreads), ssmem, st, A, C, red, level);
-    DAL_RETURN_IF_LAUNCH_FAILED();
+    if (const int rc = multi_level_stats(J, level, st)) return rc;
+    if (const int rc = multi_level_split(J, level, st)) return rc;
   }
-  return rf_launch_finalize(A, st);
+  return rf_launch_finalize(J.A, st);
 }

@@ -61,14 +61,17 @@ struct RegArgs {
   int32_t* split_f;   // [T][n_inner]
   int32_t* split_b;   // [T][n_inner]
   int64_t* hist;      // [T][2^l][m][W][hb], the current level
-  int64_t* tot;       // [T][2^l][W]
+  int64_t* tot;       // [T][2^l][W], ending where hist begins (reg_at_level)
   int32_t* out_feature;   // [T][n_inner]
   double* out_threshold;  // [T][n_inner]
   double* out_leaf;       // [T][n_leaf]
 };
 
+// The totals come right before the histogram and a level's totals are kept at
+// the END of their piece: totals + histogram of a level are one span of int64
+// (what a sharded fit sums over ranks: dal_rf_train_regressor_level_span).
 struct RegLayout {
-  size_t node, status, split_f, split_b, hist, tot, red, total;
+  size_t node, status, split_f, split_b, tot, hist, red, total;
 };
 
 RegLayout reg_layout(int64_t n, int64_t T, int max_depth, int64_t m, int64_t hb, int64_t W) {
@@ -85,11 +88,32 @@ RegLayout reg_layout(int64_t n, int64_t T, int max_depth, int64_t m, int64_t hb,
   L.status = take(T * (2 * n_inner + 1));
   L.split_f = take(T * n_inner * 4);
   L.split_b = take(T * n_inner * 4);
-  L.hist = take(T * split_nodes * m * hb * W * 8);
   L.tot = take(T * (n_inner + 1) * W * 8);
+  L.hist = take(T * split_nodes * m * hb * W * 8);
   L.red = take(T * split_nodes * kRedBytes);
   L.total = o;
   return L;
+}
+
+// The job descriptor of the level steps (rf_train_shared.hpp has the
+// classifiers'); A.tot holds the END of the totals piece (== A.hist).
+struct RegJob {
+  uint32_t magic;
+  int32_t kind;
+  unsigned char* red;
+  RegArgs A;
+};
+static_assert(sizeof(RegJob) <= DAL_RF_JOB_BYTES, "DAL_RF_JOB_BYTES holds a regressor job");
+
+// The level's view of the job's arguments; words = elements of the level's span from A.tot on.
+RegArgs reg_at_level(const RegJob& J, int level, int64_t* words) {
+  RegArgs A = J.A;
+  const int64_t nodes = int64_t{1} << level;
+  const int64_t tot_words = A.T * nodes * A.W;
+  const int64_t hist_words = level < A.max_depth ? A.T * nodes * A.m * A.hb * A.W : 0;
+  A.tot = A.hist - tot_words;
+  *words = tot_words + hist_words;
+  return A;
 }
 
 __device__ __forceinline__ int block_min_int(int v, int* red) {
@@ -546,30 +570,40 @@ extern "C" size_t dal_rf_train_regressor_workspace_bytes(int64_t n, int32_t n_tr
   return reg_layout(n, n_trees, max_depth, m, num_splits + 2, 1 + k_y + k_sq).total;
 }
 
-extern "C" int dal_rf_train_regressor(const uint8_t* bins, int64_t n, int64_t d, const double* y,
-                                      const double* thresholds, const int32_t* n_splits, int32_t num_splits,
-                                      const int32_t* weights, const int32_t* feature_subsets, int32_t m,
-                                      int32_t n_trees, int32_t max_depth, int32_t min_instances,
-                                      double min_info_gain, int32_t q_y, int32_t k_y, int32_t q_sq, int32_t k_sq,
-                                      int32_t* out_feature, double* out_threshold, double* out_leaf, void* ws,
-                                      size_t ws_bytes, dal_stream_t stream) {
-  if (!bins || !y || !thresholds || !n_splits || !weights || !feature_subsets || !out_feature || !out_threshold ||
-      !out_leaf || !ws)
+namespace dal {
+namespace {
+
+// The argument checks of dal_rf_train_regressor over n >= min_n rows, the
+// workspace layout, the job, then every tree's root open and every other
+// node absent.  bins, y and weights may be null for a job of no rows.  *Jp
+// is the job; it is also copied to the caller's descriptor `job` (nullable)
+// before the first device call.
+int regress_begin(RegJob* Jp, void* job, const uint8_t* bins, int64_t n, int64_t d, const double* y, const double* thresholds,
+                  const int32_t* n_splits, int32_t num_splits, const int32_t* weights,
+                  const int32_t* feature_subsets, int32_t m, int32_t n_trees, int32_t max_depth,
+                  int32_t min_instances, double min_info_gain, int32_t q_y, int32_t k_y, int32_t q_sq, int32_t k_sq,
+                  int32_t* out_feature, double* out_threshold, double* out_leaf, void* ws, size_t ws_bytes,
+                  int64_t min_n, hipStream_t st) {
+  if (!thresholds || !n_splits || !feature_subsets || !out_feature || !out_threshold || !out_leaf || !ws)
     return DAL_ERR_ARG;
-  if (n < 1 || d < 1 || n_trees < 1 || m < 1 || m > d) return DAL_ERR_SHAPE;
+  if ((n > 0 || min_n > 0) && (!bins || !y || !weights)) return DAL_ERR_ARG;
+  if (n < min_n || d < 1 || n_trees < 1 || m < 1 || m > d) return DAL_ERR_SHAPE;
   if (max_depth < 1 || max_depth > DAL_RF_MAX_DEPTH) return DAL_ERR_UNSUPPORTED;
   if (!limbs_ok(q_y, k_y) || !limbs_ok(q_sq, k_sq)) return DAL_ERR_UNSUPPORTED;
   if (num_splits < 0 || num_splits >= DAL_RF_MAX_SPLITS) return DAL_ERR_SHAPE;
   const int hb = num_splits + 2;  // find_splits emits at most num_splits + 1 thresholds
   const int W = 1 + k_y + k_sq;
   // the split kernel keeps one node's whole (slot, word, bin) histogram in LDS
-  const int64_t node_bytes = static_cast<int64_t>(m) * hb * W * 8;
-  if (node_bytes > DAL_RF_SPLIT_LDS_BYTES) return DAL_ERR_UNSUPPORTED;
+  if (static_cast<int64_t>(m) * hb * W * 8 > DAL_RF_SPLIT_LDS_BYTES) return DAL_ERR_UNSUPPORTED;
   const RegLayout L = reg_layout(n, n_trees, max_depth, m, hb, W);
   if (ws_bytes < L.total || reinterpret_cast<uintptr_t>(ws) % 256) return DAL_ERR_SHAPE;
-  hipStream_t st = as_stream(stream);
   unsigned char* w = static_cast<unsigned char*>(ws);
-  RegArgs A{};
+  RegJob& J = *Jp;
+  J = RegJob{};
+  J.magic = kRfJobMagic;
+  J.kind = kRfJobRegress;
+  J.red = w + L.red;
+  RegArgs& A = J.A;
   A.bins = bins;
   A.y = y;
   A.weights = weights;
@@ -595,11 +629,11 @@ extern "C" int dal_rf_train_regressor(const uint8_t* bins, int64_t n, int64_t d,
   A.split_f = reinterpret_cast<int32_t*>(w + L.split_f);
   A.split_b = reinterpret_cast<int32_t*>(w + L.split_b);
   A.hist = reinterpret_cast<int64_t*>(w + L.hist);
-  A.tot = reinterpret_cast<int64_t*>(w + L.tot);
+  A.tot = A.hist;
   A.out_feature = out_feature;
   A.out_threshold = out_threshold;
   A.out_leaf = out_leaf;
-  unsigned char* red = w + L.red;
+  if (job) std::memcpy(job, &J, sizeof J);
 
   const int64_t n_inner = (int64_t{1} << max_depth) - 1;
   // root open, everything else absent
@@ -608,37 +642,120 @@ extern "C" int dal_rf_train_regressor(const uint8_t* bins, int64_t n, int64_t d,
   hipLaunchKernelGGL(rf_open_roots_kernel, dim3(static_cast<unsigned>(ceil_div(n_trees, 256))), dim3(256), 0, st,
                      A.status, n_trees, 2 * n_inner + 1);
   DAL_RETURN_IF_LAUNCH_FAILED();
+  return DAL_OK;
+}
+
+// Zero the level's totals and histogram, then add the job's rows to them.
+int regress_level_stats(const RegJob& J, int level, hipStream_t st) {
+  int64_t words = 0;
+  const RegArgs A = reg_at_level(J, level, &words);
+  if (hipMemsetAsync(A.tot, 0, static_cast<size_t>(words) * 8, st) != hipSuccess) return DAL_ERR_HIP;
+  if (A.n == 0) return DAL_OK;
+  const int64_t nodes = int64_t{1} << level;
+  const bool open_level = level < A.max_depth;
+  const int64_t tot_bytes = nodes * A.W * 8;
+  const int64_t hist_bytes = open_level ? nodes * A.m * A.hb * A.W * 8 : 0;
   const int rows_per_block = 1024;
-  const dim3 hgrid(static_cast<unsigned>(ceil_div(n, rows_per_block)), static_cast<unsigned>(n_trees));
-  for (int level = 0; level <= max_depth; ++level) {
-    const int64_t nodes = int64_t{1} << level;
-    const bool open_level = level < max_depth;
-    const int64_t tot_bytes = nodes * W * 8;
-    const int64_t hist_bytes = open_level ? nodes * node_bytes : 0;
-    if (hipMemsetAsync(A.tot, 0, static_cast<size_t>(n_trees * tot_bytes), st) != hipSuccess) return DAL_ERR_HIP;
-    if (open_level && hipMemsetAsync(A.hist, 0, static_cast<size_t>(n_trees * hist_bytes), st) != hipSuccess)
-      return DAL_ERR_HIP;
-    // the classifiers' budget: totals + level histogram within 64 KiB, else global atomics
-    const bool lds_tot = tot_bytes <= kHistLdsBytes;
-    const bool lds_hist = open_level && tot_bytes + hist_bytes <= kHistLdsBytes;
-    const size_t hsmem = static_cast<size_t>((lds_tot ? tot_bytes : 0) + (lds_hist ? hist_bytes : 0)) + 16;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_hist_regress_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(hsmem)) != hipSuccess)
-      return DAL_ERR_HIP;
-    hipLaunchKernelGGL(rf_hist_regress_kernel, hgrid, dim3(256), hsmem, st, A, level, rows_per_block, lds_tot,
-                       lds_hist);
-    DAL_RETURN_IF_LAUNCH_FAILED();
-    const size_t ssmem = open_level ? static_cast<size_t>(node_bytes) : 16;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_split_regress_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ssmem)) != hipSuccess)
-      return DAL_ERR_HIP;
-    hipLaunchKernelGGL(rf_split_regress_kernel, dim3(static_cast<unsigned>(nodes), static_cast<unsigned>(n_trees)),
-                       dim3(kSplitThreads), ssmem, st, A, red, level);
-    DAL_RETURN_IF_LAUNCH_FAILED();
-  }
-  hipLaunchKernelGGL(rf_finalize_regress_kernel,
-                     dim3(static_cast<unsigned>(std::min<int64_t>(ceil_div(n_trees * n_inner, 256), 4096))),
-                     dim3(256), 0, st, A);
+  const dim3 hgrid(static_cast<unsigned>(ceil_div(A.n, rows_per_block)), static_cast<unsigned>(A.T));
+  // the classifiers' budget: totals + level histogram within 64 KiB, else global atomics
+  const bool lds_tot = tot_bytes <= kHistLdsBytes;
+  const bool lds_hist = open_level && tot_bytes + hist_bytes <= kHistLdsBytes;
+  const size_t hsmem = static_cast<size_t>((lds_tot ? tot_bytes : 0) + (lds_hist ? hist_bytes : 0)) + 16;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_hist_regress_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(hsmem)) != hipSuccess)
+    return DAL_ERR_HIP;
+  hipLaunchKernelGGL(rf_hist_regress_kernel, hgrid, dim3(256), hsmem, st, A, level, rows_per_block, lds_tot,
+                     lds_hist);
   DAL_RETURN_IF_LAUNCH_FAILED();
   return DAL_OK;
+}
+
+// Leaf or best split of every node of the level from the workspace's sums.
+int regress_level_split(const RegJob& J, int level, hipStream_t st) {
+  int64_t words = 0;
+  const RegArgs A = reg_at_level(J, level, &words);
+  const size_t ssmem = level < A.max_depth ? static_cast<size_t>(A.m) * A.hb * A.W * 8 : 16;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_split_regress_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ssmem)) != hipSuccess)
+    return DAL_ERR_HIP;
+  hipLaunchKernelGGL(rf_split_regress_kernel, dim3(1u << level, static_cast<unsigned>(A.T)), dim3(kSplitThreads),
+                     ssmem, st, A, J.red, level);
+  DAL_RETURN_IF_LAUNCH_FAILED();
+  return DAL_OK;
+}
+
+int regress_finish(const RegJob& J, hipStream_t st) {
+  const int64_t n_inner = (int64_t{1} << J.A.max_depth) - 1;
+  hipLaunchKernelGGL(rf_finalize_regress_kernel,
+                     dim3(static_cast<unsigned>(std::min<int64_t>(ceil_div(J.A.T * n_inner, 256), 4096))), dim3(256),
+                     0, st, J.A);
+  DAL_RETURN_IF_LAUNCH_FAILED();
+  return DAL_OK;
+}
+
+}  // namespace
+}  // namespace dal
+
+extern "C" int dal_rf_train_regressor_begin(void* job, const uint8_t* bins, int64_t n_local, int64_t d,
+                                            const double* y, const double* thresholds, const int32_t* n_splits,
+                                            int32_t num_splits, const int32_t* weights,
+                                            const int32_t* feature_subsets, int32_t m, int32_t n_trees,
+                                            int32_t max_depth, int32_t min_instances, double min_info_gain,
+                                            int32_t q_y, int32_t k_y, int32_t q_sq, int32_t k_sq,
+                                            int32_t* out_feature, double* out_threshold, double* out_leaf, void* ws,
+                                            size_t ws_bytes, dal_stream_t stream) {
+  RegJob J;
+  if (!job) return DAL_ERR_ARG;
+  return regress_begin(&J, job, bins, n_local, d, y, thresholds, n_splits, num_splits, weights, feature_subsets, m,
+                       n_trees, max_depth, min_instances, min_info_gain, q_y, k_y, q_sq, k_sq, out_feature,
+                       out_threshold, out_leaf, ws, ws_bytes, 0, as_stream(stream));
+}
+
+extern "C" int dal_rf_train_regressor_level_stats(const void* job, int32_t level, dal_stream_t stream) {
+  RegJob J;
+  if (const int rc = rf_job_load(job, kRfJobRegress, level, &J)) return rc;
+  return regress_level_stats(J, level, as_stream(stream));
+}
+
+extern "C" int dal_rf_train_regressor_level_split(const void* job, int32_t level, dal_stream_t stream) {
+  RegJob J;
+  if (const int rc = rf_job_load(job, kRfJobRegress, level, &J)) return rc;
+  return regress_level_split(J, level, as_stream(stream));
+}
+
+extern "C" int dal_rf_train_regressor_finish(const void* job, dal_stream_t stream) {
+  RegJob J;
+  if (const int rc = rf_job_load(job, kRfJobRegress, 0, &J)) return rc;
+  return regress_finish(J, as_stream(stream));
+}
+
+extern "C" int dal_rf_train_regressor_level_span(const void* job, int32_t level, void** ptr, int32_t* elem_type,
+                                                 int64_t* count) {
+  RegJob J;
+  if (!ptr || !elem_type || !count) return DAL_ERR_ARG;
+  if (const int rc = rf_job_load(job, kRfJobRegress, level, &J)) return rc;
+  const RegArgs A = reg_at_level(J, level, count);
+  *ptr = A.tot;
+  *elem_type = DAL_RF_SPAN_I64;
+  return DAL_OK;
+}
+
+extern "C" int dal_rf_train_regressor(const uint8_t* bins, int64_t n, int64_t d, const double* y,
+                                      const double* thresholds, const int32_t* n_splits, int32_t num_splits,
+                                      const int32_t* weights, const int32_t* feature_subsets, int32_t m,
+                                      int32_t n_trees, int32_t max_depth, int32_t min_instances,
+                                      double min_info_gain, int32_t q_y, int32_t k_y, int32_t q_sq, int32_t k_sq,
+                                      int32_t* out_feature, double* out_threshold, double* out_leaf, void* ws,
+                                      size_t ws_bytes, dal_stream_t stream) {
+  RegJob J;
+  hipStream_t st = as_stream(stream);
+  if (const int rc = regress_begin(&J, nullptr, bins, n, d, y, thresholds, n_splits, num_splits, weights, feature_subsets, m,
+                                   n_trees, max_depth, min_instances, min_info_gain, q_y, k_y, q_sq, k_sq,
+                                   out_feature, out_threshold, out_leaf, ws, ws_bytes, 1, st))
+    return rc;
+  for (int level = 0; level <= max_depth; ++level) {
+    if (const int rc = regress_level_stats(J, level, st)) return rc;
+    if (const int rc = regress_level_split(J, level, st)) return rc;
+  }
+  return regress_finish(J, st);
 }

@@ -54,6 +54,9 @@ DAL_X_F64 = 1
 DAL_LAL_MAX_TREES = 4095
 DAL_RF_REG_MAX_LIMBS = 8
 DAL_RF_MAX_SPLIT_SAMPLE_F64 = 8192
+DAL_RF_JOB_BYTES = 512
+DAL_RF_SPAN_I32 = 0
+DAL_RF_SPAN_I64 = 1
 
 # name -> (restype, argtypes); every symbol of include/dal.h
 SIGNATURES = {
@@ -215,6 +218,29 @@ SIGNATURES = {
                                        c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_int32, c_int32,
                                        c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                        c_void_p]),
+    "dal_rf_train_begin": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                   c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_double,
+                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dal_rf_train_level_stats": (c_int, [c_void_p, c_int32, c_void_p]),
+    "dal_rf_train_level_split": (c_int, [c_void_p, c_int32, c_void_p]),
+    "dal_rf_train_finish": (c_int, [c_void_p, c_void_p]),
+    "dal_rf_train_level_span": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "dal_rf_train_multiclass_begin": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                              c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                              c_int32, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
+                                              c_void_p]),
+    "dal_rf_train_multiclass_level_stats": (c_int, [c_void_p, c_int32, c_void_p]),
+    "dal_rf_train_multiclass_level_split": (c_int, [c_void_p, c_int32, c_void_p]),
+    "dal_rf_train_multiclass_finish": (c_int, [c_void_p, c_void_p]),
+    "dal_rf_train_multiclass_level_span": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "dal_rf_train_regressor_begin": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                             c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                             c_double, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dal_rf_train_regressor_level_stats": (c_int, [c_void_p, c_int32, c_void_p]),
+    "dal_rf_train_regressor_level_split": (c_int, [c_void_p, c_int32, c_void_p]),
+    "dal_rf_train_regressor_finish": (c_int, [c_void_p, c_void_p]),
+    "dal_rf_train_regressor_level_span": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "dal_vote_histogram": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "dal_lal_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_double, c_double, c_void_p, c_void_p]),
     "dal_votes_rescore": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int, c_void_p, c_void_p,

@@ -913,3 +913,247 @@ def emulate_evaluate(shards, forest, hist_fn=None, measures=("accuracy",)):
         t = _shard_table(fn, x, y, forest)
         buf = t.clone() if buf is None else buf + t.to(buf.device)
     return metrics.finish(buf.cpu().numpy(), forest.n_trees, forest.n_classes, names)
+
+
+# --------------------------------------------------------- forest training --
+class _GroupOps:
+    """The collectives of a sharded fit over a real group (one local job)."""
+
+    def __init__(self, comm):
+        self.comm = comm
+
+    def reduce(self, tensors, op: str):
+        dist = self.comm.dist
+        ops = {"sum": dist.ReduceOp.SUM, "min": dist.ReduceOp.MIN, "max": dist.ReduceOp.MAX}
+        dist.all_reduce(tensors[0], op=ops[op], group=self.comm.group)  # in place, stream-ordered
+        return tensors
+
+    def gather_rows(self, tensors):
+        """Every rank's rows [c_r, w] as one [sum c_r, w]: the counts first,
+        then the rows padded to the largest count."""
+        torch = __import__("torch")
+        t = tensors[0]
+        counts = self.comm.all_gather(torch.tensor([t.shape[0]], dtype=torch.int64, device=t.device)).cpu().tolist()
+        top = max(counts)
+        pad = torch.zeros((top,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+        pad[:t.shape[0]] = t
+        got = self.comm.all_gather(pad).reshape((len(counts), top) + tuple(t.shape[1:]))
+        return [torch.cat([got[r, :c] for r, c in enumerate(counts)])]
+
+
+class _LocalOps:
+    """The same collectives over P jobs in one process (emulate_*)."""
+
+    def reduce(self, tensors, op: str):
+        torch = __import__("torch")
+        stack = torch.stack([t.to(tensors[0].device) for t in tensors])
+        red = {"sum": stack.sum(dim=0), "min": stack.amin(dim=0), "max": stack.amax(dim=0)}[op]
+        return [red.to(dtype=t.dtype, device=t.device) for t in tensors]
+
+    def gather_rows(self, tensors):
+        torch = __import__("torch")
+        return [torch.cat([t.to(u.device) for t in tensors]) for u in tensors]
+
+
+def _sharded_fit(regress: bool, shards, n_total: int, ops, steps, num_trees, max_depth, max_bins, seed,
+                 feature_subset_strategy, weights, feature_subsets, min_instances_per_node, min_info_gain,
+                 num_classes=2, tree_chunk=None):
+    """train_classifier / train_regressor over the jobs of ``shards`` =
+    [(x_local, y_local, positions)] with the local halves ``steps`` (one per
+    job) and the collectives ``ops``.  Every decision below is taken from
+    values that are the same on every rank, so the ranks raise or proceed
+    alike."""
+    from types import SimpleNamespace
+
+    from . import random_forest as rf
+
+    torch = __import__("torch")
+    n_total, P = int(n_total), len(shards)
+    if n_total < 1:
+        raise ValueError("training set must be non-empty")
+    # -- local checks: a failure is kept and raised after the first collective, on every rank
+    xs, ys, poss, bounds, cover, meta, errors = [], [], [], [], [], [], []
+    for (x_local, y_local, positions), st in zip(shards, steps):
+        x = pos = y = bound = None
+        seen = np.zeros(n_total, dtype=np.int64)
+        d = f64 = 0
+        try:
+            x = st.rows(x_local, regress)
+            yv = y_local.cpu().numpy() if isinstance(y_local, torch.Tensor) else np.asarray(y_local)
+            pos = (positions.cpu().numpy() if isinstance(positions, torch.Tensor) else np.asarray(positions))
+            pos = pos.astype(np.int64).reshape(-1)
+            if x.dim() != 2 or x.shape[1] < 1:
+                raise ValueError("a shard must be a 2-D [rows, features] array (an empty one [0, d])")
+            n_local, d, f64 = int(x.shape[0]), int(x.shape[1]), int(x.dtype == torch.float64)
+            if pos.shape[0] != n_local or (n_local and (pos.min() < 0 or pos.max() >= n_total)):
+                raise ValueError(f"positions must be {n_local} indices in [0, {n_total}), one per local row")
+            seen[:] = np.bincount(pos, minlength=n_total)
+            if regress:
+                y, b_y, b_sq = rf.regression_label_bounds(yv, n_local)
+                bound = (b_y[0], b_sq[0], -b_y[1], -b_sq[1])
+            else:
+                y = rf.check_labels(yv, n_local, num_classes)
+        except ValueError as e:
+            errors.append(e)
+        xs.append(x), ys.append(y), poss.append(pos), bounds.append(bound), cover.append(seen)
+        meta.append([d, -d, f64, -f64, int(len(errors) > len(meta))])
+    devs = [x.device if x is not None else getattr(st, "dev", torch.device("cpu")) for x, st in zip(xs, steps)]
+    # one all-reduce MAX: any rank's refusal, and the feature count and row dtype every rank must share
+    d, nd, f64, nf64, refused = ops.reduce([torch.tensor(m, dtype=torch.int64, device=dv)
+                                            for m, dv in zip(meta, devs)], "max")[0].cpu().tolist()
+    if errors:
+        raise errors[0]
+    if refused:
+        raise ValueError("another rank's rows, labels or positions were refused")
+    if d != -nd:
+        raise ValueError(f"the ranks' shards must have one feature count: they range from {-nd} to {d}")
+    if f64 != -nf64:
+        raise ValueError("the ranks' rows must have one dtype (fp32, or fp64), empty shards included")
+    seen = ops.reduce([torch.from_numpy(c).to(dv) for c, dv in zip(cover, devs)], "sum")[0].cpu().numpy()
+    if (seen != 1).any():
+        bad = int(np.nonzero(seen != 1)[0][0])
+        raise ValueError(f"positions must cover [0, {n_total}) exactly once over the ranks: position {bad} "
+                         f"appears {int(seen[bad])} times")
+    # -- the global host inputs (the single-device fit's, over n_total rows), the same on every rank
+    rf.check_growth(max_depth, max_bins)
+    if regress:
+        lim = [torch.tensor(b, dtype=torch.int64, device=dv) for b, dv in zip(bounds, devs)]
+        low_y, low_sq, ntop_y, ntop_sq = (int(v) for v in ops.reduce(lim, "min")[0].cpu().tolist())
+        (q_y, k_y), (q_sq, k_sq) = rf.regression_formats((low_y, -ntop_y), (low_sq, -ntop_sq))
+        g = rf.regressor_inputs(n_total, d, num_trees, max_depth, max_bins, seed, feature_subset_strategy, weights,
+                                feature_subsets, k_y, k_sq)
+        rows = rf.regression_split_sample_rows(n_total, max_bins, seed, bool(f64))
+        chunk = rf.regressor_tree_chunk(tree_chunk, n_total, g.T, max_depth, g.m, g.ns, k_y, k_sq)
+        fmt = (q_y, k_y, q_sq, k_sq)
+    else:
+        g = rf.classifier_inputs(n_total, d, None, 0, num_trees, max_depth, max_bins, seed, feature_subset_strategy,
+                                 weights, feature_subsets, num_classes, check_weights=True)
+        rows, chunk, fmt = g.rows, g.T, None
+    # -- thresholds: the sample's rows from wherever they live, the same search on every rank
+    picks = [x if rows is None else x[torch.from_numpy(np.nonzero(np.isin(pos, rows))[0]).to(x.device)]
+             for x, pos in zip(xs, poss)]
+    found = [st.find_splits(s, g.ns, regress) for st, s in zip(steps, ops.gather_rows(picks))]
+    # -- levels: statistics, ONE all-reduce SUM, split; no host read
+    caches = [{} for _ in range(P)]
+    outs = [[] for _ in range(P)]
+    for t0 in range(0, g.T, chunk):
+        t1 = min(g.T, t0 + chunk)
+        for i, st in enumerate(steps):
+            st.begin(SimpleNamespace(
+                regress=regress, x=xs[i], y=ys[i], weights=np.ascontiguousarray(g.weights[t0:t1][:, poss[i]]),
+                subsets=g.subsets[t0:t1], thresholds=found[i][0], n_splits=found[i][1], ns=g.ns, m=g.m,
+                max_depth=max_depth, min_instances=int(min_instances_per_node), min_gain=float(min_info_gain),
+                num_classes=int(num_classes), fmt=fmt, cache=caches[i]))
+        for level in range(max_depth + 1):
+            reduced = ops.reduce([st.level_stats(level) for st in steps], "sum")
+            for st, r in zip(steps, reduced):
+                st.split(level, r)
+        for i, st in enumerate(steps):
+            outs[i].append(st.finish())
+    flags = ops.reduce([torch.as_tensor(f[2]).reshape(1).to(torch.int32) for f in found], "max")
+    rf.check_split_overflow(flags[0].item())
+    models = []
+    for i in range(P):
+        arrays = [torch.cat(a) if isinstance(a[0], torch.Tensor) else np.concatenate(a) for a in zip(*outs[i])]
+        models.append(rf.regression_forest(*arrays, max_depth, found[i][0], found[i][1]) if regress else
+                      rf.classifier_forest(*arrays, max_depth, num_classes, found[i][0], found[i][1]))
+    return models
+
+
+def _same_model(models, regress: bool):
+    """emulate_*: every job must have grown the same forest."""
+    names = ("inner_feature", "inner_threshold", "leaf") if regress else ("inner", "leaf")
+    for m in models[1:]:
+        for a in names:
+            if getattr(m, a).tobytes() != getattr(models[0], a).tobytes():
+                raise RuntimeError(f"the shards' fits differ in {a}")
+    return models[0]
+
+
+def train_classifier(x_local, y_local, positions, n_total: int, comm, num_trees: int = 10, max_depth: int = 4,
+                     max_bins: int = 32, seed: int = 0, feature_subset_strategy: str = "auto", weights=None,
+                     feature_subsets=None, min_instances_per_node: int = 1, min_info_gain: float = 0.0,
+                     num_classes: int = 2, steps=None):
+    """dal.random_forest.train_classifier over row shards: on every rank the
+    same Forest bytes as the single-device fit of the n_total rows in
+    canonical order, for every number of ranks and every assignment of rows
+    to ranks (MLlib's own distribution: per-partition level aggregates,
+    summed, one split decision).
+
+    x_local [n_local, d] and y_local [n_local] are the rank's rows (an empty
+    shard [0, d] is legal); positions int64 [n_local] are their indices in the
+    canonical training set [0, n_total) -- contiguous shards and scattered
+    labeled rows alike.  Over the ranks the positions must cover [0, n_total)
+    exactly once: checked with one all-reduce SUM of the per-position counts,
+    after one all-reduce MAX that carries any rank's local refusal and the
+    feature count and row dtype the ranks must share; ValueError on every
+    rank alike otherwise.  ``weights`` [T, n_total] /
+    ``feature_subsets`` are the global draws (default: bagging_inputs over
+    n_total on every rank -- the host draw of the single-device fit); a rank
+    uses the columns ``positions``.  Every tree's global weight sum must stay
+    below 2^31 (check_tree_weights).  The thresholds are searched on every
+    rank over the all-gathered split sample (counts, then rows padded to the
+    largest count); numSplits is that of n_total.  Per level: the local
+    statistics, ONE all-reduce SUM of the level's int32 span, the split -- all
+    stream-ordered, no host read; then the threshold-overflow flag is
+    MAX-reduced and read once.
+
+    steps: the local half (dal.random_forest.HipSteps documents the methods;
+    None: the HIP entries on the current device; tests inject a restatement)."""
+    from .random_forest import HipSteps
+
+    return _sharded_fit(False, [(x_local, y_local, positions)], n_total, _GroupOps(comm), [steps or HipSteps()],
+                        num_trees, max_depth, max_bins, seed, feature_subset_strategy, weights, feature_subsets,
+                        min_instances_per_node, min_info_gain, num_classes=num_classes)[0]
+
+
+def train_regressor(x_local, y_local, positions, n_total: int, comm, num_trees: int = 10, max_depth: int = 4,
+                    max_bins: int = 32, seed: int = 0, feature_subset_strategy: str = "auto", weights=None,
+                    feature_subsets=None, min_instances_per_node: int = 1, min_info_gain: float = 0.0,
+                    tree_chunk=None, steps=None):
+    """dal.random_forest.train_regressor over row shards, as train_classifier
+    above: the same RegressionForest bytes on every rank, for every sharding
+    and every ``tree_chunk`` (the chunk loop stays outside the level loop; the
+    default chunk is sized from n_total, so the ranks agree on it).  The exact
+    sums' formats (q, k) of y and fl(y * y) come from an all-reduce MIN of the
+    shards' lowest set bits and negated tops; an empty or all-zero shard
+    contributes no value.  A non-finite label anywhere raises ValueError on
+    every rank.  Every rank's rows have one dtype (fp32, or fp64 for unrounded
+    rows), empty shards included.  ONE all-reduce SUM of int64 words per level."""
+    from .random_forest import HipSteps
+
+    return _sharded_fit(True, [(x_local, y_local, positions)], n_total, _GroupOps(comm), [steps or HipSteps()],
+                        num_trees, max_depth, max_bins, seed, feature_subset_strategy, weights, feature_subsets,
+                        min_instances_per_node, min_info_gain, tree_chunk=tree_chunk)[0]
+
+
+def _emulate_steps(steps, P: int):
+    from .random_forest import HipSteps
+
+    return [(steps or HipSteps)() for _ in range(P)]
+
+
+def emulate_train_classifier(shards, n_total: int, num_trees: int = 10, max_depth: int = 4, max_bins: int = 32,
+                             seed: int = 0, feature_subset_strategy: str = "auto", weights=None,
+                             feature_subsets=None, min_instances_per_node: int = 1, min_info_gain: float = 0.0,
+                             num_classes: int = 2, steps=None):
+    """train_classifier with P shards [(x, y, positions), ...] in one process
+    (tests): each all-reduce becomes an elementwise sum / min / max over the
+    shards, the all-gather a concatenation.  steps: a zero-argument factory of
+    the local half, called once per shard (None: HipSteps).  The P jobs must
+    agree; their one Forest is returned."""
+    models = _sharded_fit(False, list(shards), n_total, _LocalOps(), _emulate_steps(steps, len(shards)), num_trees,
+                          max_depth, max_bins, seed, feature_subset_strategy, weights, feature_subsets,
+                          min_instances_per_node, min_info_gain, num_classes=num_classes)
+    return _same_model(models, False)
+
+
+def emulate_train_regressor(shards, n_total: int, num_trees: int = 10, max_depth: int = 4, max_bins: int = 32,
+                            seed: int = 0, feature_subset_strategy: str = "auto", weights=None,
+                            feature_subsets=None, min_instances_per_node: int = 1, min_info_gain: float = 0.0,
+                            tree_chunk=None, steps=None):
+    """train_regressor with P shards in one process, as emulate_train_classifier."""
+    models = _sharded_fit(True, list(shards), n_total, _LocalOps(), _emulate_steps(steps, len(shards)), num_trees,
+                          max_depth, max_bins, seed, feature_subset_strategy, weights, feature_subsets,
+                          min_instances_per_node, min_info_gain, tree_chunk=tree_chunk)
+    return _same_model(models, True)

@@ -30,6 +30,7 @@ thresholds, into a ``dal.forest.RegressionForest``.
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -133,6 +134,116 @@ def check_split_histogram(m: int, n_splits: int, n_classes: int = 2) -> None:
                          "(lower max_bins or use a smaller feature subset)")
 
 
+# ------------------------------------------- host preparation, shared with
+# the row-sharded fits of dal.parallel (n is then the size of the whole
+# training set and the labels are the rank's own)
+def check_growth(max_depth: int, max_bins: int) -> None:
+    if not 1 <= max_depth <= DAL_RF_MAX_DEPTH:
+        raise ValueError(f"max_depth must lie in [1, {DAL_RF_MAX_DEPTH}]")
+    if not 2 <= max_bins <= DAL_RF_MAX_SPLITS:
+        raise ValueError(f"max_bins must lie in [2, {DAL_RF_MAX_SPLITS}]")
+
+
+def classifier_inputs(n: int, d: int, y, n_labels: int, num_trees: int, max_depth: int, max_bins: int, seed: int,
+                      feature_subset_strategy: str, weights, feature_subsets, num_classes: int,
+                      check_weights: bool = False):
+    """What train_classifier settles on the host before any device call, in
+    its order and with its messages: the growth limits, the ``n_labels``
+    labels as class-id bytes, the seeded draws (or the caller's) as int32
+    arrays over the n rows, their shapes, numSplits, the split kernel's LDS
+    limit and the rows the thresholds are fitted on.  ``y`` None: no labels
+    here (their count limits alone are checked)."""
+    check_growth(max_depth, max_bins)
+    if y is None:  # a sharded fit: every rank has checked its own labels
+        y, n_labels = np.zeros(0, dtype=np.uint8), 0
+    labels = check_labels(y, n_labels, num_classes)
+    if weights is None or feature_subsets is None:
+        w_draw, s_draw = bagging_inputs(n, d, num_trees, max_depth, seed, feature_subset_strategy)
+        weights = w_draw if weights is None else weights
+        feature_subsets = s_draw if feature_subsets is None else feature_subsets
+    w = check_tree_weights(weights) if check_weights else np.ascontiguousarray(weights, dtype=np.int32)
+    sub = np.ascontiguousarray(feature_subsets, dtype=np.int32)
+    T = int(w.shape[0])
+    n_inner = (1 << max_depth) - 1
+    if w.ndim != 2 or tuple(w.shape) != (T, n) or sub.ndim != 3 or tuple(sub.shape[:2]) != (T, n_inner):
+        raise ValueError(f"weights must be [T, {n}] and feature_subsets [T, {n_inner}, m]")
+    m = int(sub.shape[2])
+    if not 1 <= m <= d:
+        raise ValueError("feature subsets must hold 1..d features")
+    ns = num_splits(n, max_bins)
+    check_split_histogram(m, ns, num_classes)
+    check_labels(y, n_labels, num_classes, num_trees=T)
+    return SimpleNamespace(labels=labels, weights=w, subsets=sub, T=T, m=m, ns=ns, n_inner=n_inner,
+                           num_classes=int(num_classes), rows=split_sample_rows(n, max_bins, seed))
+
+
+def device_rows(X, dev, keep_f64: bool = False):
+    """The training rows as a contiguous device tensor: fp32, or fp64 where
+    the regressor is given fp64 rows (they train unrounded)."""
+    import torch
+
+    if isinstance(X, torch.Tensor):
+        x = X.to(dev) if keep_f64 and X.dtype == torch.float64 else X.to(device=dev, dtype=torch.float32)
+    else:
+        xs = np.asarray(X)
+        host_dtype = np.float64 if keep_f64 and xs.dtype == np.float64 else np.float32
+        x = torch.from_numpy(np.ascontiguousarray(xs, dtype=host_dtype)).to(dev)
+    return x.contiguous()
+
+
+def device_find_splits(x, rows, ns: int, f64_thresholds: bool):
+    """dal_rf_find_splits (fp32 thresholds, the classifiers) or
+    dal_rf_find_splits_f64 (fp64 thresholds, the regressor) over the sample
+    ``rows`` of x (None: every row): (thresholds [d, 255], n_splits [d],
+    status [1]) on x's device, stream-ordered."""
+    import torch
+
+    dev = x.device
+    n, d = int(x.shape[0]), int(x.shape[1])
+    n_sample = n if rows is None else int(rows.shape[0])
+    rows_t = None if rows is None else torch.from_numpy(rows).to(dev)
+    thresholds = torch.empty((d, DAL_RF_MAX_SPLITS), dtype=torch.float64 if f64_thresholds else torch.float32,
+                             device=dev)
+    n_splits = torch.empty(d, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    rows_p = 0 if rows_t is None else rows_t.data_ptr()
+    if f64_thresholds:
+        x_dtype = _lib.DAL_X_F64 if x.dtype == torch.float64 else _lib.DAL_X_F32
+        call("dal_rf_find_splits_f64", x.data_ptr(), x_dtype, n, d, d, rows_p, n_sample, ns, thresholds.data_ptr(),
+             n_splits.data_ptr(), status.data_ptr(), _stream(dev))
+    else:
+        call("dal_rf_find_splits", x.data_ptr(), n, d, d, rows_p, n_sample, ns, thresholds.data_ptr(),
+             n_splits.data_ptr(), status.data_ptr(), _stream(dev))
+    return thresholds, n_splits, status
+
+
+def _workspace(nbytes: int, dev):
+    """(tensor, 256-B aligned address) of nbytes of device scratch."""
+    import torch
+
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    return ws, (ws.data_ptr() + 255) // 256 * 256
+
+
+def check_split_overflow(status) -> None:
+    if int(status) & DAL_FLAG_RF_SPLITS:
+        raise _lib.DalError("threshold search emitted more than num_splits + 1 thresholds")
+
+
+def classifier_forest(inner, leaf, max_depth: int, num_classes: int, thresholds, n_splits) -> Forest:
+    """The Forest of the trained heap arrays; device tensors stay resident."""
+    on_dev = hasattr(inner, "is_cuda") and inner.is_cuda
+    forest = Forest(inner=_host(inner), leaf=_host(leaf), depth=max_depth, n_classes=int(num_classes))
+    if on_dev:
+        forest._dev[str(inner.device)] = (inner, leaf)
+    forest.split_thresholds = (thresholds, n_splits)
+    return forest
+
+
+def _host(t) -> np.ndarray:
+    return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+
+
 def train_classifier(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: int = 32, seed: int = 0,
                      feature_subset_strategy: str = "auto", weights=None, feature_subsets=None,
                      min_instances_per_node: int = 1, min_info_gain: float = 0.0, device=None,
@@ -151,48 +262,23 @@ def train_classifier(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: in
 
     dev = _require_cuda(device)
     lib = _lib.load()
-    x = X.to(device=dev, dtype=torch.float32) if isinstance(X, torch.Tensor) else \
-        torch.from_numpy(np.ascontiguousarray(np.asarray(X, dtype=np.float32))).to(dev)
-    x = x.contiguous()
+    x = device_rows(X, dev)
     if x.dim() != 2 or x.shape[0] < 1:
         raise ValueError("training set must be a non-empty 2-D [rows, features] array")
     n, d = int(x.shape[0]), int(x.shape[1])
-    if not 1 <= max_depth <= DAL_RF_MAX_DEPTH:
-        raise ValueError(f"max_depth must lie in [1, {DAL_RF_MAX_DEPTH}]")
-    if not 2 <= max_bins <= DAL_RF_MAX_SPLITS:
-        raise ValueError(f"max_bins must lie in [2, {DAL_RF_MAX_SPLITS}]")
     yv = y.cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
-    labels = torch.from_numpy(check_labels(yv, n, num_classes)).to(dev)
-    if weights is None or feature_subsets is None:
-        w_draw, s_draw = bagging_inputs(n, d, num_trees, max_depth, seed, feature_subset_strategy)
-        weights = w_draw if weights is None else weights
-        feature_subsets = s_draw if feature_subsets is None else feature_subsets
-    w = torch.as_tensor(np.ascontiguousarray(weights, dtype=np.int32)).to(dev)
-    sub = torch.as_tensor(np.ascontiguousarray(feature_subsets, dtype=np.int32)).to(dev)
-    T = int(w.shape[0])
-    n_inner = (1 << max_depth) - 1
-    if tuple(w.shape) != (T, n) or sub.dim() != 3 or tuple(sub.shape[:2]) != (T, n_inner):
-        raise ValueError(f"weights must be [T, {n}] and feature_subsets [T, {n_inner}, m]")
-    m = int(sub.shape[2])
-    if not 1 <= m <= d:
-        raise ValueError("feature subsets must hold 1..d features")
-    ns = num_splits(n, max_bins)
-    check_split_histogram(m, ns, num_classes)
-    check_labels(yv, n, num_classes, num_trees=T)
-    rows = split_sample_rows(n, max_bins, seed)
-    n_sample = n if rows is None else int(rows.shape[0])
-    rows_t = None if rows is None else torch.from_numpy(rows).to(dev)
-    thresholds = torch.empty((d, DAL_RF_MAX_SPLITS), dtype=torch.float32, device=dev)
-    n_splits = torch.empty(d, dtype=torch.int32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    p = classifier_inputs(n, d, yv, n, num_trees, max_depth, max_bins, seed, feature_subset_strategy, weights,
+                          feature_subsets, num_classes)
+    labels = torch.from_numpy(p.labels).to(dev)
+    w = torch.from_numpy(p.weights).to(dev)
+    sub = torch.from_numpy(p.subsets).to(dev)
+    T, m, ns, n_inner = p.T, p.m, p.ns, p.n_inner
+    thresholds, n_splits, status = device_find_splits(x, p.rows, ns, f64_thresholds=False)
     s = _stream(dev)
-    call("dal_rf_find_splits", x.data_ptr(), n, d, d, 0 if rows_t is None else rows_t.data_ptr(), n_sample, ns,
-         thresholds.data_ptr(), n_splits.data_ptr(), status.data_ptr(), s)
     multi = int(num_classes) > 2
     wsb = int(lib.dal_rf_train_multiclass_workspace_bytes(n, d, T, max_depth, m, ns, int(num_classes))) if multi \
         else int(lib.dal_rf_train_workspace_bytes(n, d, T, max_depth, m, ns))
-    ws = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
-    wsp = (ws.data_ptr() + 255) // 256 * 256
+    ws, wsp = _workspace(wsb, dev)
     inner = torch.empty((T, n_inner, 2), dtype=torch.int32, device=dev)
     leaf = torch.empty((T, n_inner + 1), dtype=torch.uint8, device=dev)
     head = (x.data_ptr(), n, d, d, labels.data_ptr(), thresholds.data_ptr(), n_splits.data_ptr(), ns,
@@ -202,13 +288,8 @@ def train_classifier(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: in
         call("dal_rf_train_multiclass", *head, int(num_classes), *tail)
     else:
         call("dal_rf_train", *head, *tail)
-    if int(status.item()) & DAL_FLAG_RF_SPLITS:
-        raise _lib.DalError("threshold search emitted more than num_splits + 1 thresholds")
-    forest = Forest(inner=inner.cpu().numpy(), leaf=leaf.cpu().numpy(), depth=max_depth,
-                    n_classes=int(num_classes))
-    forest._dev[str(dev)] = (inner, leaf)
-    forest.split_thresholds = (thresholds, n_splits)
-    return forest
+    check_split_overflow(status.item())
+    return classifier_forest(inner, leaf, max_depth, num_classes, thresholds, n_splits)
 
 
 # ---------------------------------------------------------------- regression
@@ -229,27 +310,44 @@ def regression_subset_size(n_features: int, n_trees: int, strategy: str = "auto"
     return feature_subset_size(n_features, n_trees, regression_subset_strategy(n_trees, strategy))
 
 
+NO_BITS = (2 ** 31 - 1, -(2 ** 31))  # (low, top) of values without a set bit: neutral under MIN / MAX
+
+
+def exact_sum_bounds(values):
+    """(low, top) of a vector of finite doubles: the exponent of the lowest
+    set bit over the nonzero values and the exponent above the highest set
+    bit; NO_BITS when there is no nonzero value (an empty or all-zero shard
+    of a sharded fit then leaves the other shards' format alone)."""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    v = v[v != 0.0]
+    if v.size == 0:
+        return NO_BITS
+    mant, exp = np.frexp(v)  # |mant| in [0.5, 1): the highest set bit has exponent exp - 1
+    m = np.abs(mant * 9007199254740992.0).astype(np.int64)  # 53-bit integers, exact
+    low_bit = m & -m
+    tz = np.log2(low_bit.astype(np.float64)).astype(np.int64)  # powers of two: exact
+    return int((exp.astype(np.int64) - 53 + tz).min()), int(exp.max())
+
+
+def format_from_bounds(low: int, top: int):
+    """(Q, K, span) of the exact accumulator from (low, top): (0, 1, 0) for NO_BITS."""
+    if (int(low), int(top)) == NO_BITS:
+        return 0, 1, 0
+    span = int(top) - int(low)
+    return int(low), max(1, -(-span // LIMB_BITS)), span
+
+
 def exact_sum_format(values):
     """(Q, K, span) of a vector of finite doubles for the exact accumulator
     (csrc/rf_exact_sum.hpp): Q the exponent of the lowest set bit over the
     nonzero values, span = (the exponent above the highest set bit) - Q, K =
     max(1, ceil(span / 31)) limbs.  (0, 1, 0) when every value is zero."""
-    v = np.asarray(values, dtype=np.float64).reshape(-1)
-    v = v[v != 0.0]
-    if v.size == 0:
-        return 0, 1, 0
-    mant, exp = np.frexp(v)  # |mant| in [0.5, 1): the highest set bit has exponent exp - 1
-    m = np.abs(mant * 9007199254740992.0).astype(np.int64)  # 53-bit integers, exact
-    low_bit = m & -m
-    tz = np.log2(low_bit.astype(np.float64)).astype(np.int64)  # powers of two: exact
-    q = int((exp.astype(np.int64) - 53 + tz).min())
-    span = int(exp.max()) - q
-    return q, max(1, -(-span // LIMB_BITS)), span
+    return format_from_bounds(*exact_sum_bounds(values))
 
 
-def check_regression_labels(y, n: int):
-    """The labels as n finite doubles and the two accumulator formats
-    ((Q, K) of y, (Q, K) of fl(y * y)), or ValueError.  Pure host code."""
+def regression_label_bounds(y, n: int):
+    """The labels as n finite doubles with exact_sum_bounds of y and of
+    fl(y * y), or ValueError.  Pure host code."""
     yv = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
     if yv.shape[0] != n:
         raise ValueError(f"labels must be {n} values, one per row")
@@ -259,16 +357,30 @@ def check_regression_labels(y, n: int):
         sq = yv * yv
     if not np.isfinite(sq).all():
         raise ValueError("a label's square overflows fp64")
+    return yv, exact_sum_bounds(yv), exact_sum_bounds(sq)
+
+
+def regression_formats(bounds_y, bounds_sq):
+    """((Q, K) of y, (Q, K) of fl(y * y)) from their (low, top), within the
+    exact variance sums' limits, or ValueError."""
     fmt = []
-    for what, v in (("labels", yv), ("squared labels", sq)):
-        q, k, span = exact_sum_format(v)
+    for what, b in (("labels", bounds_y), ("squared labels", bounds_sq)):
+        q, k, span = format_from_bounds(*b)
         if k > DAL_RF_REG_MAX_LIMBS:
             raise ValueError(f"the {what} span {span} bits between their highest and lowest set bit, more than the "
                              f"{DAL_RF_REG_MAX_LIMBS * LIMB_BITS} the exact variance sums hold")
         if q + span + LIMB_BITS > 1023:
             raise ValueError(f"a weighted sum of the {what} could overflow fp64")
         fmt.append((q, k))
-    return yv, fmt[0], fmt[1]
+    return fmt[0], fmt[1]
+
+
+def check_regression_labels(y, n: int):
+    """The labels as n finite doubles and the two accumulator formats
+    ((Q, K) of y, (Q, K) of fl(y * y)), or ValueError.  Pure host code."""
+    yv, b_y, b_sq = regression_label_bounds(y, n)
+    f_y, f_sq = regression_formats(b_y, b_sq)
+    return yv, f_y, f_sq
 
 
 def check_tree_weights(weights) -> np.ndarray:
@@ -294,32 +406,12 @@ def regression_split_sample_rows(n: int, max_bins: int, seed: int, f64: bool):
     return rows[:cap].astype(np.int64)
 
 
-def train_regressor(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: int = 32, seed: int = 0,
-                    feature_subset_strategy: str = "auto", weights=None, feature_subsets=None,
-                    min_instances_per_node: int = 1, min_info_gain: float = 0.0, device=None,
-                    tree_chunk=None) -> RegressionForest:
-    """RandomForest.trainRegressor(categoricalFeaturesInfo={},
-    impurity="variance") on the GPU (csrc/rf_train_regress.hip): X [n, d] fp32
-    or fp64 (numpy or torch; fp64 rows train unrounded), y [n] real labels.
-    ``weights`` [T, n] / ``feature_subsets`` [T, 2^max_depth - 1, m] override
-    the seeded draws (bagging_inputs with regression's "auto" = onethird).
-    The variance sums are exact (include/dal.h), so the result is the same
-    bytes on every run and for every ``tree_chunk`` (trees per launch; None
-    bounds the workspace at about 256 MiB).  The RegressionForest is resident
-    on the device; ``split_thresholds`` holds (thresholds fp64 [d, 255],
-    n_splits int32 [d]) there."""
-    import torch
-
-    is_t = isinstance(X, torch.Tensor)
-    xs = X if is_t else np.asarray(X)
-    if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] < 1:
-        raise ValueError("training set must be a non-empty 2-D [rows, features] array")
-    n, d = int(xs.shape[0]), int(xs.shape[1])
-    if not 1 <= max_depth <= DAL_RF_MAX_DEPTH:
-        raise ValueError(f"max_depth must lie in [1, {DAL_RF_MAX_DEPTH}]")
-    if not 2 <= max_bins <= DAL_RF_MAX_SPLITS:
-        raise ValueError(f"max_bins must lie in [2, {DAL_RF_MAX_SPLITS}]")
-    yv, (q_y, k_y), (q_sq, k_sq) = check_regression_labels(y.cpu().numpy() if isinstance(y, torch.Tensor) else y, n)
+def regressor_inputs(n: int, d: int, num_trees: int, max_depth: int, max_bins: int, seed: int,
+                     feature_subset_strategy: str, weights, feature_subsets, k_y: int, k_sq: int):
+    """What train_regressor settles on the host after the labels, in its
+    order and with its messages: the seeded draws (or the caller's) over the n
+    rows, check_tree_weights, the shapes, numSplits and the split kernel's LDS
+    limit.  Shared with dal.parallel (n = the whole training set)."""
     if weights is None or feature_subsets is None:
         w_draw, s_draw = bagging_inputs(n, d, num_trees, max_depth, seed,
                                         regression_subset_strategy(num_trees, feature_subset_strategy))
@@ -341,39 +433,71 @@ def train_regressor(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: int
         raise ValueError(f"{m} candidate features per node x {ns + 1} thresholds x {W} words need {need} bytes of "
                          f"split histogram, more than the GPU trainer's {DAL_RF_SPLIT_LDS_BYTES} "
                          "(lower max_bins or use a smaller feature subset)")
+    return SimpleNamespace(weights=w_np, subsets=sub_np, T=T, m=m, ns=ns, n_inner=n_inner)
+
+
+def regressor_tree_chunk(tree_chunk, n: int, T: int, max_depth: int, m: int, ns: int, k_y: int, k_sq: int) -> int:
+    """Trees per launch: the caller's, or what keeps the workspace at about 256 MiB."""
+    if tree_chunk is None:
+        per_tree = int(_lib.load().dal_rf_train_regressor_workspace_bytes(n, 1, max_depth, m, ns, k_y, k_sq)) + 4 * n
+        tree_chunk = max(1, (256 << 20) // per_tree)
+    return max(1, min(int(tree_chunk), T))
+
+
+def regression_forest(feat, thr, leaf, max_depth: int, thresholds, n_splits) -> RegressionForest:
+    """The RegressionForest of the trained heap arrays; device tensors stay resident."""
+    on_dev = hasattr(feat, "is_cuda") and feat.is_cuda
+    model = RegressionForest(inner_feature=_host(feat), inner_threshold=_host(thr), leaf=_host(leaf),
+                             depth=max_depth)
+    if on_dev:
+        model._dev[str(feat.device)] = (feat, thr, leaf)
+    model.split_thresholds = (thresholds, n_splits)
+    return model
+
+
+def train_regressor(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: int = 32, seed: int = 0,
+                    feature_subset_strategy: str = "auto", weights=None, feature_subsets=None,
+                    min_instances_per_node: int = 1, min_info_gain: float = 0.0, device=None,
+                    tree_chunk=None) -> RegressionForest:
+    """RandomForest.trainRegressor(categoricalFeaturesInfo={},
+    impurity="variance") on the GPU (csrc/rf_train_regress.hip): X [n, d] fp32
+    or fp64 (numpy or torch; fp64 rows train unrounded), y [n] real labels.
+    ``weights`` [T, n] / ``feature_subsets`` [T, 2^max_depth - 1, m] override
+    the seeded draws (bagging_inputs with regression's "auto" = onethird).
+    The variance sums are exact (include/dal.h), so the result is the same
+    bytes on every run and for every ``tree_chunk`` (trees per launch; None
+    bounds the workspace at about 256 MiB).  The RegressionForest is resident
+    on the device; ``split_thresholds`` holds (thresholds fp64 [d, 255],
+    n_splits int32 [d]) there."""
+    import torch
+
+    xs = X if isinstance(X, torch.Tensor) else np.asarray(X)
+    if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] < 1:
+        raise ValueError("training set must be a non-empty 2-D [rows, features] array")
+    n, d = int(xs.shape[0]), int(xs.shape[1])
+    check_growth(max_depth, max_bins)
+    yv, (q_y, k_y), (q_sq, k_sq) = check_regression_labels(y.cpu().numpy() if isinstance(y, torch.Tensor) else y, n)
+    p = regressor_inputs(n, d, num_trees, max_depth, max_bins, seed, feature_subset_strategy, weights,
+                         feature_subsets, k_y, k_sq)
+    w_np, sub_np, T, m, ns, n_inner = p.weights, p.subsets, p.T, p.m, p.ns, p.n_inner
 
     from .engine import _require_cuda
 
     dev = _require_cuda(device)
     lib = _lib.load()
-    if is_t:
-        x = X.to(dev) if X.dtype == torch.float64 else X.to(device=dev, dtype=torch.float32)
-    else:
-        host_dtype = np.float64 if xs.dtype == np.float64 else np.float32
-        x = torch.from_numpy(np.ascontiguousarray(xs, dtype=host_dtype)).to(dev)
-    x = x.contiguous()
+    x = device_rows(xs, dev, keep_f64=True)
     f64 = x.dtype == torch.float64
     x_dtype = _lib.DAL_X_F64 if f64 else _lib.DAL_X_F32
     rows = regression_split_sample_rows(n, max_bins, seed, f64)
-    n_sample = n if rows is None else int(rows.shape[0])
-    rows_t = None if rows is None else torch.from_numpy(rows).to(dev)
-    thresholds = torch.empty((d, DAL_RF_MAX_SPLITS), dtype=torch.float64, device=dev)
-    n_splits = torch.empty(d, dtype=torch.int32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    thresholds, n_splits, status = device_find_splits(x, rows, ns, f64_thresholds=True)
     bins = torch.empty((n, d), dtype=torch.uint8, device=dev)
     s = _stream(dev)
-    call("dal_rf_find_splits_f64", x.data_ptr(), x_dtype, n, d, d, 0 if rows_t is None else rows_t.data_ptr(),
-         n_sample, ns, thresholds.data_ptr(), n_splits.data_ptr(), status.data_ptr(), s)
     call("dal_rf_bin_rows", x.data_ptr(), x_dtype, n, d, d, thresholds.data_ptr(), n_splits.data_ptr(),
          bins.data_ptr(), s)
     y_t = torch.from_numpy(yv).to(dev)
-    if tree_chunk is None:
-        per_tree = int(lib.dal_rf_train_regressor_workspace_bytes(n, 1, max_depth, m, ns, k_y, k_sq)) + 4 * n
-        tree_chunk = max(1, (256 << 20) // per_tree)
-    tree_chunk = max(1, min(int(tree_chunk), T))
+    tree_chunk = regressor_tree_chunk(tree_chunk, n, T, max_depth, m, ns, k_y, k_sq)
     wsb = int(lib.dal_rf_train_regressor_workspace_bytes(n, tree_chunk, max_depth, m, ns, k_y, k_sq))
-    ws = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
-    wsp = (ws.data_ptr() + 255) // 256 * 256
+    ws, wsp = _workspace(wsb, dev)
     feat = torch.empty((T, n_inner), dtype=torch.int32, device=dev)
     thr = torch.empty((T, n_inner), dtype=torch.float64, device=dev)
     leaf = torch.empty((T, n_inner + 1), dtype=torch.float64, device=dev)
@@ -385,13 +509,8 @@ def train_regressor(X, y, num_trees: int = 10, max_depth: int = 4, max_bins: int
              n_splits.data_ptr(), ns, w_t.data_ptr(), sub_t.data_ptr(), m, t1 - t0, max_depth,
              int(min_instances_per_node), float(min_info_gain), q_y, k_y, q_sq, k_sq, feat[t0:t1].data_ptr(),
              thr[t0:t1].data_ptr(), leaf[t0:t1].data_ptr(), wsp, wsb, s)
-    if int(status.item()) & DAL_FLAG_RF_SPLITS:
-        raise _lib.DalError("threshold search emitted more than num_splits + 1 thresholds")
-    model = RegressionForest(inner_feature=feat.cpu().numpy(), inner_threshold=thr.cpu().numpy(),
-                             leaf=leaf.cpu().numpy(), depth=max_depth)
-    model._dev[str(dev)] = (feat, thr, leaf)
-    model.split_thresholds = (thresholds, n_splits)
-    return model
+    check_split_overflow(status.item())
+    return regression_forest(feat, thr, leaf, max_depth, thresholds, n_splits)
 
 
 def predict(forest: Forest, X, device=None):
@@ -437,3 +556,111 @@ def predict_regression(model, X, device=None):
     x = x.to(dev).contiguous()
     return engine.forest_regress(model, x, int(x.shape[0]), int(x.shape[1]), int(x.shape[1]), dev,
                                  f64=x.dtype == torch.float64)
+
+
+# ------------------------------------------------ level steps (sharded fits)
+class HipSteps:
+    """The local half of a row-sharded fit (dal.parallel.train_classifier /
+    train_regressor) on the GPU: the level-step entries of include/dal.h over
+    one rank's rows.  Everything is enqueued on the current stream; no method
+    reads the device.  Tests replace it with a restatement of the same
+    methods (the ``steps`` argument):
+
+      rows(x_local, regress)             the rank's rows as a [n_local, d] tensor
+      find_splits(sample, ns, regress)   (thresholds, n_splits, status [1]) of the gathered sample
+      begin(job)                         bin the local rows, open the roots
+      level_stats(level) -> tensor       the level's totals + histogram of the local rows (integers, 1-D)
+      split(level, reduced)              leaf or best split per node from the sums over all ranks
+      finish() -> arrays                 (inner, leaf) or (feature, threshold, leaf) of the job's trees
+
+    ``job`` (a SimpleNamespace): regress, x (from rows), y (class-id bytes or
+    fp64 labels, numpy), weights int32 [T, n_local], subsets int32 [T, 2^D - 1,
+    m], thresholds / n_splits (from find_splits), ns, m, max_depth,
+    min_instances, min_gain, num_classes, fmt = (q_y, k_y, q_sq, k_sq), and
+    cache, a dict that lives as long as the fit (a regressor's tree chunks
+    share their binned rows through it)."""
+
+    def __init__(self, device=None):
+        from .engine import _require_cuda
+
+        self.dev = _require_cuda(device)
+
+    def rows(self, x_local, regress: bool):
+        return device_rows(x_local, self.dev, keep_f64=regress)
+
+    def find_splits(self, sample, ns: int, regress: bool):
+        return device_find_splits(sample, None, ns, f64_thresholds=regress)
+
+    def begin(self, job) -> None:
+        import ctypes
+
+        import torch
+
+        lib = _lib.load()
+        dev, x, c = self.dev, job.x, job.cache
+        n, d = int(x.shape[0]), int(x.shape[1])
+        s = _stream(dev)
+        if "y" not in c:
+            c["y"] = torch.from_numpy(np.ascontiguousarray(job.y)).to(dev)
+            if job.regress:
+                c["bins"] = torch.empty((n, d), dtype=torch.uint8, device=dev)
+                if n:
+                    call("dal_rf_bin_rows", x.data_ptr(), _lib.DAL_X_F64 if x.dtype == torch.float64 else
+                         _lib.DAL_X_F32, n, d, d, job.thresholds.data_ptr(), job.n_splits.data_ptr(),
+                         c["bins"].data_ptr(), s)
+        w = torch.from_numpy(np.ascontiguousarray(job.weights, dtype=np.int32)).to(dev)
+        sub = torch.from_numpy(np.ascontiguousarray(job.subsets, dtype=np.int32)).to(dev)
+        T, n_inner = int(w.shape[0]), (1 << job.max_depth) - 1
+        self.blob = ctypes.create_string_buffer(_lib.DAL_RF_JOB_BYTES)
+        grow = (job.ns, w.data_ptr(), sub.data_ptr(), job.m, T, job.max_depth, int(job.min_instances),
+                float(job.min_gain))
+        if job.regress:
+            q_y, k_y, q_sq, k_sq = job.fmt
+            self.name = "dal_rf_train_regressor"
+            wsb = int(lib.dal_rf_train_regressor_workspace_bytes(max(n, 1), T, job.max_depth, job.m, job.ns, k_y,
+                                                                 k_sq))
+            self.out = (torch.empty((T, n_inner), dtype=torch.int32, device=dev),
+                        torch.empty((T, n_inner), dtype=torch.float64, device=dev),
+                        torch.empty((T, n_inner + 1), dtype=torch.float64, device=dev))
+            self.ws, wsp = _workspace(wsb, dev)
+            call(self.name + "_begin", self.blob, c["bins"].data_ptr(), n, d, c["y"].data_ptr(),
+                 job.thresholds.data_ptr(), job.n_splits.data_ptr(), *grow, q_y, k_y, q_sq, k_sq,
+                 *(o.data_ptr() for o in self.out), wsp, wsb, s)
+        else:
+            multi = int(job.num_classes) > 2
+            self.name = "dal_rf_train_multiclass" if multi else "dal_rf_train"
+            wsb = int(lib.dal_rf_train_multiclass_workspace_bytes(max(n, 1), d, T, job.max_depth, job.m, job.ns,
+                                                                  int(job.num_classes))) if multi else \
+                int(lib.dal_rf_train_workspace_bytes(max(n, 1), d, T, job.max_depth, job.m, job.ns))
+            self.out = (torch.empty((T, n_inner, 2), dtype=torch.int32, device=dev),
+                        torch.empty((T, n_inner + 1), dtype=torch.uint8, device=dev))
+            self.ws, wsp = _workspace(wsb, dev)
+            classes = (int(job.num_classes),) if multi else ()
+            call(self.name + "_begin", self.blob, x.data_ptr(), n, d, d, c["y"].data_ptr(),
+                 job.thresholds.data_ptr(), job.n_splits.data_ptr(), *grow, *classes,
+                 *(o.data_ptr() for o in self.out), wsp, wsb, s)
+        self.keep = (x, w, sub, job.thresholds, job.n_splits, c)  # what the job points at, for its lifetime
+
+    def level_stats(self, level: int):
+        """The span dal_rf_train*_level_span names, as a view of the workspace."""
+        import ctypes
+
+        import torch
+
+        call(self.name + "_level_stats", self.blob, int(level), _stream(self.dev))
+        ptr, kind, count = ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int64()
+        call(self.name + "_level_span", self.blob, int(level), ctypes.byref(ptr), ctypes.byref(kind),
+             ctypes.byref(count))
+        dtype, size = (torch.int64, 8) if kind.value == _lib.DAL_RF_SPAN_I64 else (torch.int32, 4)
+        off = ptr.value - self.ws.data_ptr()
+        self.span = self.ws[off:off + count.value * size].view(dtype)
+        return self.span
+
+    def split(self, level: int, reduced) -> None:
+        if reduced.data_ptr() != self.span.data_ptr():
+            self.span.copy_(reduced)
+        call(self.name + "_level_split", self.blob, int(level), _stream(self.dev))
+
+    def finish(self):
+        call(self.name + "_finish", self.blob, _stream(self.dev))
+        return self.out

@@ -906,6 +906,97 @@ int dal_rf_train_regressor(const uint8_t* bins, int64_t n, int64_t d, const doub
                            int32_t k_sq, int32_t* out_feature, double* out_threshold, double* out_leaf, void* ws,
                            size_t ws_bytes, dal_stream_t stream);
 
+/* ---- forest training in level steps: the seam of a row-sharded fit ---------
+ * MLlib's RandomForest is distributed at this place: every partition fills
+ * the (node, feature, bin) aggregates of the current level, they are summed,
+ * and the driver picks the splits.  New symbols only: dal_abi_version() stays
+ * 10 (absent from older libraries; probe with dal_rf_train_begin).
+ *
+ * Each trainer is four steps over a caller-owned job descriptor, an opaque
+ * blob of DAL_RF_JOB_BYTES bytes (any alignment) that *_begin fills; together
+ * with the workspace it is the whole state between calls -- the library keeps
+ * none, so jobs are independent and a descriptor may be copied.
+ *   *_begin            the argument checks and limits of dal_rf_train /
+ *                      dal_rf_train_multiclass / dal_rf_train_regressor over
+ *                      the rank's n_local rows, the workspace layout, the
+ *                      binning of the local rows (the regressor takes bins, as
+ *                      dal_rf_train_regressor does), every tree's root open.
+ *                      The descriptor is written once the arguments pass,
+ *                      before the first device call.
+ *   *_level_stats(l)   zero the level's totals and histogram, then add the
+ *                      local rows to them; a row's node of the previous level
+ *                      stays in the rank's node [T][n_local].
+ *   *_level_split(l)   leaf or best split of every node of the level from the
+ *                      totals and the histogram as they then stand in the
+ *                      workspace (the same work on every rank); writes the
+ *                      split features, split bins and node states.
+ *   *_finish           the heap arrays of the outputs given to *_begin.
+ * dal_rf_train* are begin, then stats and split for l = 0..max_depth, then
+ * finish: the same launches, the same bytes.
+ *
+ * A sharded fit (the canonical semantics): rank r holds n_local rows of a
+ * training set of n_total rows, the weights columns of ITS rows [T][n_local],
+ * and the same thresholds, n_splits, num_splits = min(maxBins, n_total) - 1,
+ * feature subsets and (regressor) label formats as every other rank.  Between
+ * *_level_stats and *_level_split the ranks sum *_level_span element-wise
+ * (integers: any order gives the same bytes).  Every rank then holds the
+ * forest of the single-device fit of all rows -- for every number of ranks and
+ * every assignment of rows to ranks.  n_local == 0 is legal for the steps (x,
+ * labels / bins, y and weights may then be null): no row kernel is launched,
+ * the span is zeroed, the split runs.  dal_rf_train* keep refusing n < 1.
+ * Every tree's weights must sum to less than 2^31 over ALL ranks (int32 class
+ * counts and the regressor's 64-bit words alike): the caller's check.
+ *
+ * *_level_span: ONE contiguous span per level -- ONE collective per level --
+ * the totals directly followed by the histogram:
+ *   classifiers  DAL_RF_SPAN_I32, T 2^l (C + m hb C) elements,
+ *   regressor    DAL_RF_SPAN_I64, T 2^l (W + m hb W) elements,
+ * hb = num_splits + 2, W = 1 + k_y + k_sq, C = 2 for dal_rf_train_*; at
+ * l == max_depth the totals alone (T 2^l C, T 2^l W).  The address lies in the
+ * workspace and is aligned to its element.
+ *
+ * Before any HIP call: a null pointer, or a descriptor that no *_begin of the
+ * same trainer filled, is DAL_ERR_ARG; a level outside [0, max_depth]
+ * DAL_ERR_SHAPE; n_local < 0 DAL_ERR_SHAPE; the trainers' limits
+ * (DAL_RF_MAX_DEPTH, DAL_MC_MAX_CLASSES, DAL_RF_REG_MAX_LIMBS,
+ * DAL_RF_SPLIT_LDS_BYTES) DAL_ERR_UNSUPPORTED, as in dal_rf_train*.  The
+ * workspace is dal_rf_train*_workspace_bytes(max(n_local, 1), ...) bytes. */
+#define DAL_RF_JOB_BYTES 512
+#define DAL_RF_SPAN_I32 0
+#define DAL_RF_SPAN_I64 1
+int dal_rf_train_begin(void* job, const float* x, int64_t n_local, int64_t d, int64_t ldx, const uint8_t* labels,
+                       const float* thresholds, const int32_t* n_splits, int32_t num_splits,
+                       const int32_t* weights, const int32_t* feature_subsets, int32_t m, int32_t n_trees,
+                       int32_t max_depth, int32_t min_instances, double min_info_gain, int32_t* out_inner,
+                       uint8_t* out_leaf, void* ws, size_t ws_bytes, dal_stream_t stream);
+int dal_rf_train_level_stats(const void* job, int32_t level, dal_stream_t stream);
+int dal_rf_train_level_split(const void* job, int32_t level, dal_stream_t stream);
+int dal_rf_train_finish(const void* job, dal_stream_t stream);
+int dal_rf_train_level_span(const void* job, int32_t level, void** ptr, int32_t* elem_type, int64_t* count);
+int dal_rf_train_multiclass_begin(void* job, const float* x, int64_t n_local, int64_t d, int64_t ldx,
+                                  const uint8_t* labels, const float* thresholds, const int32_t* n_splits,
+                                  int32_t num_splits, const int32_t* weights, const int32_t* feature_subsets,
+                                  int32_t m, int32_t n_trees, int32_t max_depth, int32_t min_instances,
+                                  double min_info_gain, int32_t n_classes, int32_t* out_inner, uint8_t* out_leaf,
+                                  void* ws, size_t ws_bytes, dal_stream_t stream);
+int dal_rf_train_multiclass_level_stats(const void* job, int32_t level, dal_stream_t stream);
+int dal_rf_train_multiclass_level_split(const void* job, int32_t level, dal_stream_t stream);
+int dal_rf_train_multiclass_finish(const void* job, dal_stream_t stream);
+int dal_rf_train_multiclass_level_span(const void* job, int32_t level, void** ptr, int32_t* elem_type,
+                                       int64_t* count);
+int dal_rf_train_regressor_begin(void* job, const uint8_t* bins, int64_t n_local, int64_t d, const double* y,
+                                 const double* thresholds, const int32_t* n_splits, int32_t num_splits,
+                                 const int32_t* weights, const int32_t* feature_subsets, int32_t m,
+                                 int32_t n_trees, int32_t max_depth, int32_t min_instances, double min_info_gain,
+                                 int32_t q_y, int32_t k_y, int32_t q_sq, int32_t k_sq, int32_t* out_feature,
+                                 double* out_threshold, double* out_leaf, void* ws, size_t ws_bytes,
+                                 dal_stream_t stream);
+int dal_rf_train_regressor_level_stats(const void* job, int32_t level, dal_stream_t stream);
+int dal_rf_train_regressor_level_split(const void* job, int32_t level, dal_stream_t stream);
+int dal_rf_train_regressor_finish(const void* job, dal_stream_t stream);
+int dal_rf_train_regressor_level_span(const void* job, int32_t level, void** ptr, int32_t* elem_type,
+                                      int64_t* count);
+
 /* ---- LAL query scores from the forest votes --------------------------------
  * active_learner.py:240-343 (ActiveLearnerLAL.selectNext).  The regressor's
  * five features depend on an unlabeled row through its vote count v alone, so
