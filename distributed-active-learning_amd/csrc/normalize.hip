@@ -135,16 +135,16 @@ __global__ __launch_bounds__(256) void canon_colsum_wave_kernel(const float* __r
 }
 
 constexpr int kColFeat = 8;  // features per block of the few-chunks kernel
-__global__ __launch_bounds__(256) void canon_colsum_block_kernel(const float* __restrict__ x, int64_t n, int d,
-                                                                 int64_t ldx, const double* __restrict__ norm64,
-                                                                 const uint8_t* __restrict__ flags,
-                                                                 double* __restrict__ partials) {
+// (the body of both block kernels: chunk c, the features of blockIdx.y)
+__device__ __forceinline__ void canon_colsum_block_body(const float* __restrict__ x, int64_t n, int d, int64_t ldx,
+                                                        const double* __restrict__ norm64,
+                                                        const uint8_t* __restrict__ flags,
+                                                        double* __restrict__ partials, const int64_t c) {
   __shared__ double u[DAL_CANON_CHUNK][kColFeat];
   __shared__ double sn[DAL_CANON_CHUNK];
   __shared__ uint8_t sl[DAL_CANON_CHUNK];
   const int tid = threadIdx.x;
   const int fl = tid % kColFeat, rs = tid / kColFeat;
-  const int64_t c = blockIdx.x;
   const int f = blockIdx.y * kColFeat + fl;
   constexpr int kRowsPerPass = 256 / kColFeat;
   constexpr int kPer = DAL_CANON_CHUNK / kRowsPerPass;
@@ -177,6 +177,25 @@ __global__ __launch_bounds__(256) void canon_colsum_block_kernel(const float* __
 #pragma unroll 32
   for (int rl = 0; rl < DAL_CANON_CHUNK; ++rl) acc = acc + u[rl][tid];
   partials[c * d + f] = acc;
+}
+
+__global__ __launch_bounds__(256) void canon_colsum_block_kernel(const float* __restrict__ x, int64_t n, int d,
+                                                                 int64_t ldx, const double* __restrict__ norm64,
+                                                                 const uint8_t* __restrict__ flags,
+                                                                 double* __restrict__ partials) {
+  canon_colsum_block_body(x, n, d, ldx, norm64, flags, partials, blockIdx.x);
+}
+
+// The same arithmetic for the listed chunks only (dal_canon_colsum_partials_chunks):
+// block b rewrites row chunk_ids[b] of partials; an id outside the pool is skipped.
+__global__ __launch_bounds__(256) void canon_colsum_chunks_kernel(const float* __restrict__ x, int64_t n, int d,
+                                                                  int64_t ldx, const double* __restrict__ norm64,
+                                                                  const uint8_t* __restrict__ flags,
+                                                                  const int64_t* __restrict__ chunk_ids,
+                                                                  double* __restrict__ partials) {
+  const int64_t c = chunk_ids[blockIdx.x];
+  if (c < 0 || c >= (n + DAL_CANON_CHUNK - 1) / DAL_CANON_CHUNK) return;  // (the whole block)
+  canon_colsum_block_body(x, n, d, ldx, norm64, flags, partials, c);
 }
 
 // Separable canonical density for every row: d_i = sum_f (x_if / norm64[i]) *
@@ -370,6 +389,20 @@ extern "C" int dal_canon_colsum_partials(const float* x, int64_t n, int64_t d, i
                        dim3(static_cast<unsigned>(chunks), static_cast<unsigned>(ceil_div(d, kColFeat))), dim3(256), 0,
                        as_stream(stream), x, n, static_cast<int>(d), ldx, norm64, row_flags, partials);
   }
+  DAL_RETURN_IF_LAUNCH_FAILED();
+  return DAL_OK;
+}
+
+extern "C" int dal_canon_colsum_partials_chunks(const float* x, int64_t n, int64_t d, int64_t ldx,
+                                                const double* norm64, const uint8_t* row_flags,
+                                                const int64_t* chunk_ids, int64_t n_chunks, double* partials,
+                                                dal_stream_t stream) {
+  if (!x || !norm64 || !partials || (!chunk_ids && n_chunks)) return DAL_ERR_ARG;
+  if (n < 1 || d < 1 || ldx < d || n_chunks < 0 || n_chunks > ceil_div(n, DAL_CANON_CHUNK)) return DAL_ERR_SHAPE;
+  if (n_chunks == 0) return DAL_OK;
+  hipLaunchKernelGGL(canon_colsum_chunks_kernel,
+                     dim3(static_cast<unsigned>(n_chunks), static_cast<unsigned>(ceil_div(d, kColFeat))), dim3(256), 0,
+                     as_stream(stream), x, n, static_cast<int>(d), ldx, norm64, row_flags, chunk_ids, partials);
   DAL_RETURN_IF_LAUNCH_FAILED();
   return DAL_OK;
 }

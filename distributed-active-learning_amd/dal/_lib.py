@@ -32,6 +32,8 @@ DAL_KEY_NONE = 0xFFFFFFFFFFFFFFFF
 DAL_FIXED_SCALE = 4294967296.0
 DAL_ROW_GRANULE = 512
 DAL_CANON_CHUNK = 256
+DAL_DOWNDATE_MAX_ROWS = 1024
+DAL_DOWNDATE_TILE = 64
 DAL_MAX_TREE_DEPTH = 16
 DAL_SORT_CAP = 8192
 DAL_SORT_CAP_PAYLOAD = 4096
@@ -72,6 +74,10 @@ SIGNATURES = {
     "dal_canon_colsum_partials": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
     "dal_canon_colsum_reduce": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "dal_canon_colsum_partials_chunks": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                                 c_void_p, c_int64, c_void_p, c_void_p]),
+    "dal_density_downdate_error_bound": (c_double, [c_int64, c_int64]),
+    "dal_density_downdate": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
     "dal_gram_rowsum": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                 c_int, c_void_p]),
     "dal_split_f16_halves": (c_int64, [c_int64, c_int64]),

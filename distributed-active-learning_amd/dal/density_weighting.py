@@ -18,6 +18,8 @@ re-ranked in canonical fp64 so the selected set is bit-exact.
 """
 from __future__ import annotations
 
+import numpy as np
+
 from ._lib import DAL_MC_MAX_TREES
 from .engine import PoolState, Selection, as_pool_state, density_step, multiclass_density_step
 from .forest import Forest
@@ -39,6 +41,11 @@ def information_density(pool, excluded_idx=None, device=None, mode: str = "gram"
 
 
 L0 = "L0"  # excluded_idx default: the reference's initial labeled window
+# excluded_idx sentinel: E = every row outside ``unlabeled_idx`` -- the density
+# over the CURRENT unlabeled pool (rows leave it as they are labeled; the
+# reference freezes E at L0).  A PoolState whose E only has to grow takes the
+# incremental path (PoolState.exclude), anything else a cold step.
+LABELED = "labeled"
 
 
 def select(pool, unlabeled_idx, forest: Forest, k: int, beta: float = 1.0, excluded_idx=L0,
@@ -49,7 +56,12 @@ def select(pool, unlabeled_idx, forest: Forest, k: int, beta: float = 1.0, exclu
                   the reference's initial labeled window range(window_size)
                   (density_weighting.py:89,95-100); for a PoolState the default
                   keeps the state's own excluded set.  None or [] excludes
-                  nothing.
+                  nothing.  LABELED: every row outside ``unlabeled_idx`` (the
+                  density over the current unlabeled pool, which the reference
+                  does not compute: its E stays L0); a PoolState whose E is a
+                  subset of that set grows it with PoolState.exclude -- the
+                  cached density is lowered by the new rows' cosine sums
+                  instead of being recomputed.
     window_size   the reference's window (L0 = range(window_size)).  Omitted,
                   it is k -- the script takes window_size rows per iteration
                   (:172) -- unless k may be a batch clamped to a short
@@ -73,9 +85,26 @@ def select(pool, unlabeled_idx, forest: Forest, k: int, beta: float = 1.0, exclu
 def _pool_state(pool, unlabeled_idx, k, excluded_idx, window_size, device) -> PoolState:
     """The pool with the excluded set of select / select_multiclass applied
     (their ``excluded_idx`` and ``window_size`` arguments)."""
+    if isinstance(excluded_idx, str) and excluded_idx == LABELED:
+        n_total = pool.n_total if isinstance(pool, PoolState) else \
+            int(pool.shape[0]) if hasattr(pool, "shape") else len(pool)
+        unl = unlabeled_idx.cpu().numpy() if hasattr(unlabeled_idx, "cpu") else np.asarray(unlabeled_idx)
+        unl = unl.astype(np.int64).reshape(-1)
+        if unl.size and (unl.min() < 0 or unl.max() >= n_total):
+            raise ValueError(f"unlabeled indices must lie in [0, {n_total})")
+        keep = np.ones(n_total, dtype=bool)
+        keep[unl] = False
+        labeled = np.nonzero(keep)[0]
+        if isinstance(pool, PoolState):
+            if np.isin(pool.excluded, labeled, assume_unique=True).all():
+                pool.exclude(labeled)  # E only grows: the incremental path
+            else:
+                pool.set_excluded(labeled)
+            return pool
+        return as_pool_state(pool, excluded=labeled, device=device)
     if isinstance(excluded_idx, str):
         if excluded_idx != L0:
-            raise ValueError(f"excluded_idx must be index-like, None or {L0!r}")
+            raise ValueError(f"excluded_idx must be index-like, None, {L0!r} or {LABELED!r}")
         if isinstance(pool, PoolState):
             excluded_idx = None
         else:
@@ -113,4 +142,4 @@ def select_multiclass(pool, unlabeled_idx, forest: Forest, k: int, beta: float =
     return multiclass_density_step(state, unlabeled_idx, forest, k, beta=beta, density_fixed=density, mode=mode)
 
 
-__all__ = ["information_density", "select", "select_multiclass", "PoolState", "Selection"]
+__all__ = ["information_density", "select", "select_multiclass", "PoolState", "Selection", "L0", "LABELED"]

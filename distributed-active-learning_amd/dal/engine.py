@@ -18,7 +18,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (DAL_ASCENDING, DAL_CANON_CHUNK, DAL_DENSITY_EXACT, DAL_DENSITY_FIXED,
-                   DAL_DENSITY_NONE, DAL_DESCENDING, DAL_FIXED_SCALE, DAL_FLAG_CAND_OVERFLOW,
+                   DAL_DENSITY_NONE, DAL_DESCENDING, DAL_DOWNDATE_MAX_ROWS, DAL_DOWNDATE_TILE, DAL_FIXED_SCALE,
+                   DAL_FLAG_CAND_OVERFLOW,
                    DAL_FLAG_SAMPLE_MISS, DAL_FLAG_ZERO_NORM, DAL_MC_ENTROPY, DAL_MC_LEAST_CONFIDENCE,
                    DAL_MC_MARGIN, DAL_MC_MAX_TREES, DAL_ROW_CANDIDATE, DAL_ROW_EXCLUDED,
                    DAL_SORT_CAP_PAYLOAD, DAL_STEP_RESET_STATUS,
@@ -184,6 +185,14 @@ class PoolState:
         self.gram_fp4 = bool(gram_fp4)
         self.gram_i8 = bool(gram_i8) and not self.gram_fp4  # (one form runs)
         self._split_i8 = self._split_fp4 = None
+        # after exclude(): the column count the cached Gram density summed and the
+        # downdates' share of its error bound (density_error); None / 0: a cold density
+        self._density_cols = None
+        self._downdate_err = 0.0
+        # exclude() drops the warm plans (they capture E's flags and bound by
+        # value): the first step after it runs eagerly, so a loop that grows E
+        # every iteration captures no hipGraph per iteration
+        self._excluded_since_step = False
         self.flags = torch.zeros(self.n, dtype=torch.uint8, device=dev)
         self.excluded = np.zeros(0, dtype=np.int64)
         self.set_excluded(excluded)
@@ -230,6 +239,7 @@ class PoolState:
         self._u = self._norm64 = self._density = self._colsum = self._colsum_partials = None
         self._split = self._density_exact = self._xb = self._split_i8 = self._split_fp4 = None
         self._graphs = {}
+        self._density_cols, self._downdate_err = None, 0.0
 
     def blocked_pool(self, forest, build: bool = True, multiclass: bool = None):
         """The pool's blocked feature-major copy (dal_pool_blocked) when the
@@ -287,6 +297,98 @@ class PoolState:
         self._u = self._norm64 = self._density = self._colsum = self._colsum_partials = None
         self._split = self._density_exact = self._split_i8 = self._split_fp4 = None
         self._graphs = {}
+        self._density_cols, self._downdate_err = None, 0.0
+
+    def new_excluded(self, rows):
+        """The rows of ``rows`` (global indices) not yet in E: sorted, distinct."""
+        new = np.unique(np.asarray(list(rows) if isinstance(rows, range) else rows, dtype=np.int64).reshape(-1))
+        if new.size and (new[0] < 0 or new[-1] >= self.n_total):
+            raise ValueError(f"excluded indices must lie in [0, {self.n_total})")
+        return np.setdiff1d(new, self.excluded, assume_unique=True)
+
+    def exclude(self, rows) -> int:
+        """Grow E by ``rows`` (global indices; duplicates and members of E are
+        ignored) and return how many rows were new.  With a cached "sym" Gram
+        density the caches are repaired, not dropped: the density is lowered in
+        place by the rows' cosine sums (dal_density_downdate, an N x k product
+        instead of a new N^2 Gram; its bound is added to density_error), and
+        the row flags, the operands and the column sums become those of a
+        fresh pool with E u rows, byte for byte.  Without a cached density, or
+        on a gram "f32" pool, this is set_excluded(E u rows).  Removing rows
+        from E is not incremental: use set_excluded."""
+        new = self.new_excluded(rows)
+        if new.size == 0:
+            return 0
+        if self._density is None or self.gram == "f32":
+            self.set_excluded(np.union1d(self.excluded, new))
+            return int(new.size)
+        if self.row_base or self.n != self.n_total:
+            raise ValueError("exclude on a shard: use dal.parallel.exclude")
+        for c0 in range(0, int(new.size), DAL_DOWNDATE_MAX_ROWS):
+            chunk = new[c0:c0 + DAL_DOWNDATE_MAX_ROWS]
+            self.apply_exclude(chunk, self.delta_operand(chunk))
+        return int(new.size)
+
+    def _local_of(self, chunk):
+        """(positions in ``chunk``, local rows) of the chunk's rows this pool or shard owns."""
+        pos = np.nonzero((chunk >= self.row_base) & (chunk < self.row_base + self.n))[0]
+        return pos, chunk[pos] - self.row_base
+
+    def delta_operand(self, chunk):
+        """The split operand rows of ``chunk`` (sorted new rows of E, at most
+        DAL_DOWNDATE_MAX_ROWS) as dal_density_downdate takes them: int16
+        [m_pad, 2 * d_pad], row p = the operand row of chunk[p] where this pool
+        or shard owns it, zeros elsewhere (another shard's rows, the padding).
+        Gathered BEFORE apply_exclude zeroes those rows."""
+        torch = _torch()
+        m_pad = (int(chunk.size) + DAL_DOWNDATE_TILE - 1) // DAL_DOWNDATE_TILE * DAL_DOWNDATE_TILE
+        out = torch.zeros((m_pad, 2 * self.d_pad), dtype=torch.int16, device=self.device)
+        pos, loc = self._local_of(chunk)
+        if pos.size:
+            out[torch.from_numpy(pos).to(self.device)] = self.gram_operand()[torch.from_numpy(loc).to(self.device)]
+        return out
+
+    def apply_exclude(self, chunk, delta_ops):
+        """One step of exclude(): ``chunk`` (sorted new rows of E) leaves the
+        cached density of this pool's or shard's rows; ``delta_ops``: the
+        chunk's operand rows (delta_operand; on several GPUs the integer sum
+        of every shard's).  Stream-ordered, in this order: the downdate of
+        the density in place, EXCLUDED into the flags and zeros into the
+        chunk's operand rows, the touched 256-row chunks of the column-sum
+        partials rewritten and reduced."""
+        torch = _torch()
+        lib = _lib.load()
+        m = int(chunk.size)
+        if self._density_cols is None:
+            self._density_cols = max(self.n_total - self.n_excluded_global(), 1)
+        ops = self.gram_operand()
+        if self.n:
+            if int(self._density.shape[0]) < self.n_pad or not self._density.is_contiguous():
+                raise ValueError("the cached density must hold one contiguous word per padded row")
+            call("dal_density_downdate", _ptr(ops), self.n_pad, self.d_pad, _ptr(delta_ops), m,
+                 _ptr(self._density), 0, _stream(self.device))
+        _, loc = self._local_of(chunk)
+        if loc.size:
+            idx = torch.from_numpy(chunk).to(self.device)
+            call("dal_mark_rows", _ptr(idx), m, self.row_base, self.n, DAL_ROW_EXCLUDED, _ptr(self.flags),
+                 _stream(self.device))
+            loc_t = torch.from_numpy(loc).to(self.device)
+            for t in (ops, self._split_i8, self._split_fp4, self._u):
+                if t is not None:
+                    t.index_fill_(0, loc_t, 0)
+            if self._colsum_partials is not None:
+                touched = torch.from_numpy(np.unique(loc // DAL_CANON_CHUNK)).to(self.device)
+                call("dal_canon_colsum_partials_chunks", _ptr(self.x), self.n, self.d, self.d, _ptr(self.norms()),
+                     _ptr(self.flags), _ptr(touched), int(touched.shape[0]), _ptr(self._colsum_partials),
+                     _stream(self.device))
+                self._colsum = None if self._colsum is None else self.colsum(self._colsum_partials)
+            else:
+                self._colsum = None
+        self._density_exact = None
+        self._graphs = {}
+        self._excluded_since_step = True
+        self.excluded = np.union1d(self.excluded, chunk)
+        self._downdate_err += float(lib.dal_density_downdate_error_bound(m, self.d_pad))
 
     def n_excluded_global(self) -> int:
         return int(self.excluded.size)
@@ -434,7 +536,7 @@ class PoolState:
                 self.gram_residual(acc, op)
             if u_cols is not None:
                 return acc
-            self._density = acc
+            self.set_density_fixed(acc)
         return self._density
 
     def nb_active(self) -> int:
@@ -520,7 +622,9 @@ class PoolState:
         return self.forest_events is None and self.select_events is None and self.gram_events is None
 
     def set_density_fixed(self, acc):
+        """A cold Gram density of the current E (this pool's, or a shard's slice)."""
         self._density = acc
+        self._density_cols, self._downdate_err = None, 0.0
 
     def density_exact(self, colsum=None):
         """Separable canonical fp64 density of this shard's rows (NaN for E):
@@ -796,11 +900,16 @@ def topk_keys(keys, k: int, idx_base: int = 0):
 
 def density_error(state: PoolState) -> float:
     """Bound on |d_gemm - d_canonical| (rigorous; dal_density_error_bound or
-    _sym, by the pool's Gram kernel)."""
+    _sym, by the pool's Gram kernel; after PoolState.exclude the cached
+    density's cold bound plus dal_density_downdate_error_bound per downdate)."""
     n_cols = max(state.n_total - state.n_excluded_global(), 1)
     lib = _lib.load()
     if state.gram == "f32":
         return float(lib.dal_density_error_bound(n_cols))
+    if state._density_cols is not None:
+        # after PoolState.exclude: the cold Gram's bound at the columns it
+        # summed, plus the bounds of the downdates applied since
+        return float(lib.dal_density_error_bound_sym_d(state._density_cols, state.d_pad)) + state._downdate_err
     return float(lib.dal_density_error_bound_sym_d(n_cols, state.d_pad))
 
 
@@ -1070,7 +1179,9 @@ def multiclass_density_step(state: PoolState, unlabeled_idx, forest: Forest, k: 
         state.check_status()
         return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, counts=(counts, loc))
     C = int(forest.n_classes)
-    if (state.use_graphs and density_fixed is None and state._density is not None and state._colsum is not None
+    after_exclude, state._excluded_since_step = state._excluded_since_step, False
+    if (state.use_graphs and not after_exclude and density_fixed is None and state._density is not None
+            and state._colsum is not None
             and state.row_base == 0 and state.n == state.n_total and state.events_off()):
         return _density_step_graph(state, unl, forest, min(int(k), int(unl.shape[0])), beta, n_classes=C)
     # warm (density cached): the score kernel reads the pool's blocked copy
@@ -1144,7 +1255,9 @@ def density_step(state: PoolState, unlabeled_idx, forest: Forest, k: int, beta: 
     unl = _as_index(unlabeled_idx, state.device)
     if int(unl.shape[0]) == 0:
         raise ValueError("unlabeled set is empty (the reference loop breaks here)")
-    if (state.use_graphs and density_fixed is None and state._density is not None and state._colsum is not None
+    after_exclude, state._excluded_since_step = state._excluded_since_step, False
+    if (state.use_graphs and not after_exclude and density_fixed is None and state._density is not None
+            and state._colsum is not None
             and state.row_base == 0 and state.n == state.n_total and state.events_off()):
         return _density_step_graph(state, unl, forest, min(int(k), int(unl.shape[0])), beta)
     # warm (density cached): the score kernel reads the pool's blocked copy

@@ -96,7 +96,7 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
              window_size: int = 10, n_estimators: int = 10, max_iterations=None,
              seed: int = 0, select_fn=None, device=None, beta: float = 1.0,
              verbose: bool = False, trainer="gpu", num_classes=None, lal_model=None,
-             initial_labeled=None, measures=None, hist_fn=None) -> LoopResult:
+             initial_labeled=None, measures=None, hist_fn=None, density_over: str = "initial") -> LoopResult:
     """Run the AL loop.  strategy: "uncertainty" (uncertainty_sampling.py),
     "density" (density_weighting.py, E = L0 = range(window_size)),
     "information_density" (class entropy x density, E = L0;
@@ -135,7 +135,27 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     labels; a scikit-learn model goes through Forest.from_sklearn.  hist_fn:
     dal.metrics.evaluate's (tests inject the restatement; None: the HIP
     kernel).  measures=None changes nothing: same calls, log and ``accuracy``.
+
+    density_over ("density" and "information_density" only): which rows the
+    density d_i = sum_{j not in E} cos(x_i, x_j) sums over.  "initial" (the
+    default) is the reference: E is frozen at the rows the loop starts from,
+    so every row labeled later keeps contributing to every density
+    (density_weighting.py:95-100 drops L0 once, before the loop).
+    "unlabeled" DEPARTS from the reference: E is the current labeled set, the
+    usual definition of information density (an average similarity to the
+    pool still to be queried).  After each selection the loop calls
+    ``state.exclude(chosen)``, which lowers the cached density by the chosen
+    rows' cosine sums (an N x k product) instead of recomputing the N^2 Gram
+    -- the cost that made the reference keep E fixed.  With ``select_fn`` the
+    value is only validated: the callback sees ``unlabeled`` and can derive E.
+    Any other value, or "unlabeled" with a strategy that has no density,
+    raises ValueError.
     """
+    if density_over not in ("initial", "unlabeled"):
+        raise ValueError(f"density_over must be 'initial' or 'unlabeled', not {density_over!r}")
+    if density_over == "unlabeled" and strategy not in ("density", "information_density"):
+        raise ValueError(f"density_over='unlabeled' needs strategy 'density' or 'information_density': "
+                         f"{strategy!r} has no density")
     from .forest import Forest
 
     # more than two label values: multiclass uncertainty sampling (per-class
@@ -249,6 +269,8 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
             else:
                 raise ValueError(f"unknown strategy {strategy!r}")
             chosen = sel.indices.cpu().numpy()
+            if density_over == "unlabeled":
+                state.exclude(chosen)  # the next step's E is the current labeled set
         res.labeled_history.append(chosen)
         res.accuracy.append(acc)
         labeled.extend(int(i) for i in chosen)

@@ -667,6 +667,85 @@ def emulate(selectors, unlabeled_idx, forest, k: int, mode: str = "dw",
     return out
 
 
+def _exclude_chunks(st, rows):
+    """The rows of ``rows`` new to E (identical on every rank: E is global),
+    in chunks one downdate takes."""
+    new = st.new_excluded(rows)
+    m = _lib.DAL_DOWNDATE_MAX_ROWS
+    return new, [new[c0:c0 + m] for c0 in range(0, int(new.size), m)]
+
+
+def _sum_delta(blocks, world: int):
+    """Rank-major [P * m_pad, 2 * d_pad] int16 blocks -> their integer sum:
+    exactly one rank owns each row of Delta and the others hold zeros, so the
+    sum of the bit patterns (two halves per int32 lane: no carry can cross)
+    reconstructs Delta exactly."""
+    torch = __import__("torch")
+    w = int(blocks.shape[1])
+    return blocks.contiguous().view(torch.int32).reshape(world, -1, w // 2).sum(0, dtype=torch.int32) \
+        .contiguous().view(torch.int16)
+
+
+def _exclude_cold(sel: ShardedSelector, new):
+    """No cached density (or gram "f32"): E u rows the invalidating way."""
+    sel.state.set_excluded(np.union1d(sel.state.excluded, new))
+    sel._density = None
+    sel._parts_full = None
+    sel._colsum = None
+    sel._plans = {}
+
+
+def exclude(sel: ShardedSelector, comm, rows) -> int:
+    """PoolState.exclude across all ranks (every rank calls it with the same
+    ``rows``, global indices): one small all-gather per chunk carries the
+    operand rows of Delta -- each rank contributes the rows it owns, zeros
+    elsewhere --, every rank lowers its own density slice by their cosine sums
+    and repairs its own flags, operand and partials; the partials are
+    all-gathered again and the global column sum and the warm plans are
+    rebuilt on the next step.  Ranks that own none of Delta, and empty
+    shards, take part in the collectives and leave their rows as they are.
+    Returns the count of newly excluded rows."""
+    st = sel.state
+    new, chunks = _exclude_chunks(st, rows)
+    if new.size == 0:
+        return 0
+    if sel._density is None or st.gram == "f32":
+        _exclude_cold(sel, new)
+        return int(new.size)
+    for chunk in chunks:
+        delta = _sum_delta(comm.all_gather(st.delta_operand(chunk)), sel.world)
+        st.apply_exclude(chunk, delta)
+    sel._parts_full = comm.all_gather(sel.prep()[1])
+    sel._colsum = None
+    sel._plans = {}
+    return int(new.size)
+
+
+def emulate_exclude(selectors, rows) -> int:
+    """``exclude`` for P shards in one process (tests): the all-gathers become
+    concatenations."""
+    torch = __import__("torch")
+    if not selectors:
+        return 0
+    new, chunks = _exclude_chunks(selectors[0].state, rows)
+    if new.size == 0:
+        return 0
+    if any(s._density is None for s in selectors) or selectors[0].state.gram == "f32":
+        for s in selectors:
+            _exclude_cold(s, new)
+        return int(new.size)
+    for chunk in chunks:
+        delta = _sum_delta(torch.cat([s.state.delta_operand(chunk) for s in selectors]), len(selectors))
+        for s in selectors:
+            s.state.apply_exclude(chunk, delta)
+    parts_full = torch.cat([s.prep()[1] for s in selectors])
+    for s in selectors:
+        s._parts_full = parts_full
+        s._colsum = None
+        s._plans = {}
+    return int(new.size)
+
+
 def diversity_select_sharded(x_local, row_base: int, labeled_rows, k: int, comm, candidates=None,
                              device=None, sort_fn=hip_sort_positions):
     """Batch-mode diversity selection (BASELINE config 5) over a row-sharded

@@ -122,6 +122,15 @@ int dal_canon_colsum_partials(const float* x, int64_t n, int64_t d, int64_t ldx,
                               double* partials, dal_stream_t stream);
 int dal_canon_colsum_reduce(const double* partials, int64_t n_chunks, int64_t d,
                             double* colsum, dal_stream_t stream);
+/* dal_canon_colsum_partials for the listed chunks only (a new symbol; the ABI
+ * number stays): row chunk_ids[b] of the full [ceil(n / 256)][d] partials
+ * array is rewritten with the same sequential arithmetic, so it has the bytes
+ * a fresh pool with these row_flags produces; every other row is left alone.
+ * chunk_ids: device int64 [n_chunks], distinct (an id outside the pool is
+ * skipped); n_chunks == 0 launches nothing. */
+int dal_canon_colsum_partials_chunks(const float* x, int64_t n, int64_t d, int64_t ldx, const double* norm64,
+                                     const uint8_t* row_flags, const int64_t* chunk_ids, int64_t n_chunks,
+                                     double* partials, dal_stream_t stream);
 /* Separable canonical density (the exact identity sum_j <u_i,u_j> = <u_i, s>):
  * density[i] = sum_f (x_if / norm64[i]) * colsum[f], sequential, no FMA --
  * bit-identical to the re-rank and the oracle; NaN for EXCLUDED rows.
@@ -255,6 +264,39 @@ double dal_density_error_bound_sym(int64_t n_cols);
  * dal_density_error_bound_sym_d(n, 0) is the longest chain's, valid for any
  * d_pad. */
 double dal_density_error_bound_sym_d(int64_t n_cols, int64_t d_pad);
+
+/* ---- density downdate: E grows by a batch Delta --------------------------
+ * New symbols only: dal_abi_version() stays 10; a caller probes for
+ * dal_density_downdate (absent from older libraries).
+ * The usual information density sums over the CURRENT unlabeled pool, so a
+ * row leaves every density when it is labeled (the reference freezes E at L0,
+ * density_weighting.py:95-100).  Growing E by Delta (m rows) lowers each
+ * density by sum_{j in Delta} <u_i, u_j>: an N x m product, not a new Gram.
+ *   acc[i] -= fixed(sum_{j < m} <u_i, u_j>)   for every row i of ops
+ * ops: the split operand (dal_split_f16's layout) of the rows acc belongs to,
+ * [n_pad][2 * d_pad], n_pad % 256 == 0; delta_ops: the operand rows of Delta
+ * in the same layout, [m_pad][2 * d_pad] with m_pad = m rounded up to
+ * DAL_DOWNDATE_TILE and rows m .. m_pad - 1 zero, gathered BEFORE those rows
+ * are zeroed in ops; both 16-byte aligned.  acc: int64 [n_pad] fixed point
+ * (x 2^32), updated in place, one owner per row, chains folded to multiples
+ * of 2^-32 and subtracted as integers: its bytes do not depend on grid_blocks
+ * (<= 0: two blocks per CU) or on the run.  fp16 MFMA on H.H + H.L + L.H of
+ * the split (L.L is charged to the bound); every form of the "sym" Gram
+ * (fp16, int8, fp4) keeps this operand, so there is one downdate.
+ * Contract: if acc held the density of E within a bound B, it holds the
+ * density of E u Delta within B + dal_density_downdate_error_bound(m, d_pad)
+ * on every row outside E u Delta (rigorous, non-decreasing in m; DESIGN.md,
+ * "Density downdate").  The caller then repairs what else is keyed by E: the
+ * row flags, the operand rows of Delta (zeros) and the column-sum partials
+ * (dal_canon_colsum_partials_chunks).
+ * Null pointer or misaligned operand DAL_ERR_ARG; n_pad % 256, a d_pad not
+ * from dal_pad_features or m < 1 DAL_ERR_SHAPE; m > DAL_DOWNDATE_MAX_ROWS
+ * DAL_ERR_CAPACITY (the caller chunks a longer Delta). */
+#define DAL_DOWNDATE_MAX_ROWS 1024
+#define DAL_DOWNDATE_TILE 64
+double dal_density_downdate_error_bound(int64_t m, int64_t d_pad);
+int dal_density_downdate(const uint16_t* ops, int64_t n_pad, int64_t d_pad, const uint16_t* delta_ops, int64_t m,
+                         int64_t* acc, int grid_blocks, dal_stream_t stream);
 
 /* ---- (a5-a10) forest votes + uncertainty / density-weighted score ------
  * Replaces uncertainty_sampling.py:88-98 / density_weighting.py:136-167:
