@@ -59,6 +59,14 @@ DAL_RF_MAX_SPLIT_SAMPLE_F64 = 8192
 DAL_RF_JOB_BYTES = 512
 DAL_RF_SPAN_I32 = 0
 DAL_RF_SPAN_I64 = 1
+DAL_ROW_PICKED = 4
+DAL_KCENTER_JOB_BYTES = 512
+
+
+def kcenter_record_bytes(d: int) -> int:
+    """DAL_KCENTER_RECORD_BYTES(d): key, index, value, one reserved word, d bf16 values."""
+    return 32 + 2 * int(d)
+
 
 # name -> (restype, argtypes); every symbol of include/dal.h
 SIGNATURES = {
@@ -264,6 +272,14 @@ SIGNATURES = {
                                     c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dal_sq_error_format": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dal_sq_error_accumulate": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "dal_kcenter_error_bound": (c_double, [c_int64]),
+    "dal_kcenter_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
+    "dal_kcenter_begin": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dal_kcenter_propose": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "dal_kcenter_commit": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "dal_kcenter_select": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1019,6 +1019,10 @@ class _GroupOps:
         got = self.comm.all_gather(pad).reshape((len(counts), top) + tuple(t.shape[1:]))
         return [torch.cat([got[r, :c] for r, c in enumerate(counts)])]
 
+    def gather_row(self, rows):
+        """One int64 row per rank as [P, w] (TorchComm.all_gather_rows: stream-ordered, no host read)."""
+        return [self.comm.all_gather_rows(rows[0])]
+
 
 class _LocalOps:
     """The same collectives over P jobs in one process (emulate_*)."""
@@ -1032,6 +1036,10 @@ class _LocalOps:
     def gather_rows(self, tensors):
         torch = __import__("torch")
         return [torch.cat([t.to(u.device) for t in tensors]) for u in tensors]
+
+    def gather_row(self, rows):
+        torch = __import__("torch")
+        return [torch.stack([t.to(u.device) for t in rows]) for u in rows]
 
 
 def _sharded_fit(regress: bool, shards, n_total: int, ops, steps, num_trees, max_depth, max_bins, seed,
@@ -1236,3 +1244,71 @@ def emulate_train_regressor(shards, n_total: int, num_trees: int = 10, max_depth
                           max_depth, max_bins, seed, feature_subset_strategy, weights, feature_subsets,
                           min_instances_per_node, min_info_gain, tree_chunk=tree_chunk)
     return _same_model(models, True)
+
+
+# ------------------------------------------------------- greedy k-center --
+def _kcenter(shards, ops, steps, labeled_rows, k: int, candidates):
+    """kcenter_select_sharded over the jobs of ``shards`` = [(x_local,
+    row_base)] with the local halves ``steps`` (one per job) and the
+    collectives ``ops``: one all-reduce SUM of the in-range candidate counts
+    fixes the number of steps on every rank alike; then per step propose, one
+    all-gather of one record per rank, commit -- no host read in the loop."""
+    from .engine import Selection
+
+    if int(k) < 1:
+        raise ValueError("k must be >= 1")
+    counts = [st.prepare(x_local, row_base, labeled_rows, candidates) for (x_local, row_base), st in zip(shards, steps)]
+    kk = min(int(k), int(ops.reduce(counts, "sum")[0].item()))
+    for st in steps:
+        st.begin(kk)
+    for t in range(kk):
+        for st, records in zip(steps, ops.gather_row([st.propose(t) for st in steps])):
+            st.commit(t, records)
+    return [Selection(scores=scores, indices=idx, selected_scores=sc)
+            for idx, sc, scores in (st.finish() for st in steps)]
+
+
+def kcenter_select_sharded(x_local, row_base: int, labeled_rows, k: int, comm, candidates=None, device=None,
+                           steps=None):
+    """dal.similarity.kcenter_select over a row-sharded bf16 pool: on every
+    rank the indices and fp64 pick-time values of the single-device selection
+    of the whole pool, for every shard count, uneven and empty shards included.
+
+    x_local [n_local, d] are the rank's rows (global index of row 0:
+    ``row_base``), ``labeled_rows`` [m, d] the labeled set replicated on every
+    rank, ``candidates`` global indices (None: every row of every shard).  One
+    all-reduce SUM of the in-range candidate counts up front fixes the number
+    of steps; per step: the rank's best row (dal_kcenter_propose), ONE
+    all-gather of one record per rank (TorchComm.all_gather_rows), the pick and
+    the update pass (dal_kcenter_commit) -- stream-ordered, no host read inside
+    the loop.  ``scores`` are the fp32 max-cosines of the rank's own
+    candidates after the last pick.
+
+    steps: the local half (dal.similarity.HipKCenterSteps documents the
+    methods; None: the HIP entries on ``device``; tests inject a restatement)."""
+    from .similarity import HipKCenterSteps
+
+    return _kcenter([(x_local, row_base)], _GroupOps(comm), [steps or HipKCenterSteps(device)], labeled_rows, k,
+                    candidates)[0]
+
+
+def emulate_kcenter(shards, labeled_rows, k: int, candidates=None, steps=None):
+    """kcenter_select_sharded with P shards [(x_local, row_base), ...] in one
+    process (tests): the all-reduce becomes a sum over the shards, the
+    all-gather a stack.  steps: a zero-argument factory of the local half,
+    called once per shard (None: HipKCenterSteps).  The P jobs must agree on
+    the picks; the Selection carries them and the shards' scores concatenated
+    in shard order."""
+    from .engine import Selection
+    from .similarity import HipKCenterSteps
+
+    torch = __import__("torch")
+    shards = list(shards)
+    sels = _kcenter(shards, _LocalOps(), [(steps or HipKCenterSteps)() for _ in shards], labeled_rows, k, candidates)
+    first = sels[0]
+    for s in sels[1:]:
+        if not (torch.equal(s.indices.cpu(), first.indices.cpu())
+                and torch.equal(s.selected_scores.cpu().view(torch.int64), first.selected_scores.cpu().view(torch.int64))):
+            raise RuntimeError("the shards' k-center selections differ")
+    return Selection(scores=torch.cat([s.scores.to(first.scores.device) for s in sels]), indices=first.indices,
+                     selected_scores=first.selected_scores)

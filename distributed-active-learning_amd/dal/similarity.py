@@ -379,5 +379,154 @@ def diversity_select(pool, labeled_idx, k: int, candidates=None, device=None, ro
     return Selection(scores=mx[cand], indices=out_idx, selected_scores=out_sc)
 
 
+# ---------------------------------------------------------------------------
+# Greedy k-center (farthest-first) batch selection
+# ---------------------------------------------------------------------------
+class HipKCenterSteps:
+    """The local half of a greedy k-center selection on one device: the
+    dal_kcenter_* step entries over one row shard.  The single-device
+    ``kcenter_select`` and ``dal.parallel.kcenter_select_sharded`` drive the
+    same object; tests inject a numpy restatement with these methods:
+
+    prepare(x_local, row_base, labeled_rows, candidates) -> int64 [1] tensor,
+        the number of candidates inside this shard (``candidates`` None: every
+        row); computes m(0) and the row flags, nothing is read back;
+    begin(kk)       the job for kk steps (dal_kcenter_begin);
+    propose(t)      -> the shard's record of step t, an int64 [w] tensor,
+        w = DAL_KCENTER_RECORD_BYTES(d) / 8;
+    commit(t, records)  records int64 [P, w], the same on every rank;
+    finish()        -> (indices int64 [kk'], selected_scores fp64 [kk'], scores
+        fp32 of this shard's candidates after the last pick), kk' = the steps
+        that found a candidate; the status words' one host read.
+    Nothing between begin and finish reads the device."""
+
+    def __init__(self, device=None):
+        self.device = device
+
+    def prepare(self, x_local, row_base, labeled_rows, candidates):
+        import torch
+
+        from . import _lib
+        from ._lib import DAL_ROW_CANDIDATE
+        from .engine import _as_index, _ptr, _stream
+
+        x, dev = _bf16_pool(x_local, self.device)
+        lab_rows, _ = _bf16_pool(labeled_rows, dev)
+        if lab_rows.shape[0] < 1 or lab_rows.shape[1] != x.shape[1]:
+            raise ValueError("k-center needs at least one labeled row of the pool's width")
+        self.x, self.dev, self.row_base = x, dev, int(row_base)
+        self.n, self.d = int(x.shape[0]), int(x.shape[1])
+        n, d = self.n, self.d
+        self.lab = lab = LabeledSet(lab_rows, dev)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.inv = torch.empty(n, dtype=torch.float32, device=dev)
+        self.m32 = torch.empty(n, dtype=torch.float32, device=dev)
+        if n:
+            _lib.call("dal_inv_norms_bf16", _ptr(x), n, n, d, d, _ptr(self.inv), _ptr(self.status), _stream(dev))
+            # m(0) from the tight bf16 kernel (values only): within dal_maxcos_error_bound(d)
+            _lib.call("dal_max_cosine", _ptr(x), n, d, _ptr(lab.rows), lab.m_pad, _ptr(lab.inv), 0, _ptr(self.m32), 0,
+                      _ptr(self.status), _stream(dev))
+        if candidates is None:
+            self.flags = torch.full((n,), DAL_ROW_CANDIDATE, dtype=torch.uint8, device=dev)
+            self.cand = None
+            self.n_cand = n
+            return torch.tensor([n], dtype=torch.int64, device=dev)
+        self.flags = torch.zeros(n, dtype=torch.uint8, device=dev)
+        gidx = _as_index(candidates, dev)
+        in_range = torch.zeros(1, dtype=torch.int32, device=dev)
+        if n and gidx.shape[0]:
+            _lib.call("dal_mark_rows_count", _ptr(gidx), int(gidx.shape[0]), self.row_base, n, DAL_ROW_CANDIDATE,
+                      _ptr(self.flags), _ptr(in_range), _stream(dev))
+        self.cand = gidx - self.row_base if self.row_base else gidx
+        self.n_cand = int(gidx.shape[0])  # an upper bound: foreign indices are dropped by the marking
+        return in_range.to(torch.int64)
+
+    def begin(self, kk: int, select: bool = False):
+        """select: the whole selection from this one host call (dal_kcenter_select)."""
+        import ctypes
+
+        import torch
+
+        from . import _lib
+        from .engine import _ptr, _stream, workspace
+
+        lib = _lib.load()
+        dev, n, d, m = self.dev, self.n, self.d, self.lab.m
+        self.kk = kk = int(kk)
+        self.out_idx = torch.empty(kk, dtype=torch.int64, device=dev)
+        self.out_sc = torch.empty(kk, dtype=torch.float64, device=dev)
+        if kk < 1:
+            return
+        # the centers table [d][m + kk]: the labeled rows' canonical unit rows, then one column per pick
+        self.centers = torch.empty((d, m + kk), dtype=torch.float64, device=dev)
+        self.centers[:, :m] = self.lab.unit64_t
+        wsb = int(lib.dal_kcenter_workspace_bytes(n, d, m, kk))
+        self.ws, wsp = workspace(wsb, dev)
+        self.job = ctypes.create_string_buffer(_lib.DAL_KCENTER_JOB_BYTES)
+        self.record = torch.empty(_lib.kcenter_record_bytes(d) // 8, dtype=torch.int64, device=dev)
+        _lib.call("dal_kcenter_select" if select else "dal_kcenter_begin", self.job, _ptr(self.x), n, d, d,
+                  self.row_base, _ptr(self.flags), _ptr(self.m32), _ptr(self.inv), _ptr(self.centers), m, kk, wsp, wsb,
+                  _ptr(self.out_idx), _ptr(self.out_sc), _ptr(self.status), _stream(dev))
+
+    def propose(self, t: int):
+        from . import _lib
+        from .engine import _ptr, _stream
+
+        _lib.call("dal_kcenter_propose", self.job, int(t), _ptr(self.record), _stream(self.dev))
+        return self.record
+
+    def commit(self, t: int, records):
+        from . import _lib
+        from .engine import _ptr, _stream
+
+        records = records.to(self.dev).contiguous()
+        _lib.call("dal_kcenter_commit", self.job, int(t), _ptr(records), int(records.shape[0]), _stream(self.dev))
+
+    def finish(self):
+        import torch
+
+        found = (self.out_idx >= 0).sum().to(torch.int32).reshape(1)
+        st, st_lab, kk = torch.cat([self.status, self.lab.status, found]).tolist()  # the one host read
+        if (st | st_lab) & 1:
+            raise ValueError("zero-norm row: cosine undefined")
+        if self.cand is None:
+            scores = self.m32
+        else:
+            cand = self.cand
+            if self.n_cand:  # candidates of other shards are not ours
+                cand = cand[(cand >= 0) & (cand < self.n)]
+            scores = self.m32[cand]
+        return self.out_idx[:kk], self.out_sc[:kk], scores
+
+
+def kcenter_select(pool, labeled_idx, k: int, candidates=None, device=None, row_base: int = 0, labeled_rows=None):
+    """Greedy k-center (farthest-first, the core-set rule) batch selection:
+    k times, pick the candidate with the smallest max-cosine to the labeled
+    rows AND the picks so far (ties -> lower index), exact against the
+    canonical fp64 definition (include/dal.h, dal_kcenter_*).  Equal to k
+    successive ``diversity_select(pool, labeled + picks, 1, candidates minus
+    picks)`` calls, at one streaming pass over the pool per pick and without
+    their bound on the labeled set's growth.
+
+    Same pool contract as ``diversity_select`` (bf16, d in {64, 128, 256}, at
+    least one labeled row).  Returns Selection(scores = the fp32 max-cosine of
+    the candidates after the last pick, within dal_kcenter_error_bound(d) of
+    the canonical values; indices = the min(k, candidates) picks in pick order;
+    selected_scores = their canonical fp64 values at pick time,
+    non-decreasing).  Candidate indices outside the pool are dropped."""
+    from .engine import Selection, _as_index
+
+    if int(k) < 1:
+        raise ValueError("k must be >= 1")
+    x, dev = _bf16_pool(pool, device)
+    if labeled_rows is None:
+        labeled_rows = x[_as_index(labeled_idx, dev)]
+    st = HipKCenterSteps(dev)
+    st.prepare(x, row_base, labeled_rows, candidates)
+    st.begin(min(int(k), st.n_cand), select=True)
+    idx, sc, scores = st.finish()
+    return Selection(scores=scores, indices=idx, selected_scores=sc)
+
+
 __all__ = ["column_similarities", "cosine_pair_candidates", "cosine_pair_values", "max_cosine", "diversity_select",
-           "LabeledSet"]
+           "LabeledSet", "HipKCenterSteps", "kcenter_select"]

@@ -1213,6 +1213,93 @@ int dal_sq_error_format(const double* pred, const double* y, int64_t n, int32_t*
 int dal_sq_error_accumulate(const double* pred, const double* y, int64_t n, int32_t q, int32_t k, int64_t* cells,
                             dal_stream_t stream);
 
+/* ---- greedy k-center batch selection (farthest-first) ----------------------
+ * Batch-mode diversity (similarity.py:34-38 reduced to the nearest labeled
+ * row) where every pick joins the set the remaining rows are compared with.
+ * New symbols only: dal_abi_version() stays 10 (absent from older libraries;
+ * probe with dal_kcenter_begin).
+ *
+ * Canonical semantics.  pool: bf16 [n][ld], d in {64, 128, 256}; cos64 is the
+ * cosine of dal_cosine_pairs_resolve / the oracle's max_cosine_canonical (unit
+ * rows u = x / ||x|| with the sequential fp64 norm, sum_f u_if * u_jf in
+ * ascending f, multiply then add, no FMA).  With L the m labeled rows and C
+ * the rows flagged DAL_ROW_CANDIDATE:
+ *   m_i(0) = max_{l in L} cos64(i, l)
+ *   for t = 1 .. k:  p_t = argmin_{i in C, not picked} m_i(t-1), ties -> the
+ *                    lower global index; s_t = m_{p_t}(t-1);
+ *                    m_i(t) = max(m_i(t-1), cos64(i, p_t)) for every row.
+ * out_idx[t-1] = p_t (global: local row + idx_base), out_score[t-1] = s_t
+ * (fp64, non-decreasing in t).  When no candidate is left the step writes
+ * index -1 and a NaN score and changes nothing else.
+ *
+ * The caller's device state, which the steps update in place:
+ *   m32       fp32 [n], on entry within dal_kcenter_error_bound(d) of m_i(0)
+ *             (dal_max_cosine's out_max); after step t within the same bound
+ *             of m_i(t) -- the maximum of values that are each within B of
+ *             their canonical counterparts is within B of the canonical
+ *             maximum, so the bound does not grow;
+ *   row_flags uint8 [n]: DAL_ROW_CANDIDATE marks C; a pick gains
+ *             DAL_ROW_PICKED;
+ *   inv_norm  fp32 [n] = 1 / ||x_i|| (dal_inv_norms_bf16);
+ *   centers   fp64 [d][m + k], feature-major with row stride m + k: the
+ *             caller fills the first m columns with the labeled rows'
+ *             canonical unit rows (dal_canon_unit_rows_bf16's values); step t
+ *             appends column m + t.
+ * The job descriptor is a caller-owned blob of DAL_KCENTER_JOB_BYTES bytes
+ * (any alignment) that dal_kcenter_begin fills; with the workspace
+ * (dal_kcenter_workspace_bytes, 256-B aligned) it is the whole state between
+ * calls, as for the forest trainers' level steps.
+ *
+ *   dal_kcenter_begin    checks every argument on the host, writes the
+ *                        descriptor, folds m32 into the per-block minima over
+ *                        the live candidates.
+ *   dal_kcenter_propose  step t (0-based, 0 <= t < k): the shard's best row
+ *                        as a record of DAL_KCENTER_RECORD_BYTES(d) bytes at
+ *                        ``record`` (device, 16-B aligned): the ascending key
+ *                        of the fp64 value (uint64; DAL_KEY_NONE when the
+ *                        shard has no live candidate), the global index
+ *                        (int64), the fp64 value, one reserved word (0), the
+ *                        row's d bf16 values.  Every live candidate whose m32
+ *                        is within 2 B of the shard's fp32 minimum has its
+ *                        canonical m_i(t-1) recomputed over the first m + t
+ *                        columns of the table -- any number of them, on the
+ *                        device.
+ *   dal_kcenter_commit   step t: the pick is the minimum (key, index) over
+ *                        the n_records records at ``records`` (device, 16-B
+ *                        aligned, contiguous; every rank passes the same
+ *                        bytes, e.g. all-gathered); writes out_idx[t] and
+ *                        out_score[t], marks the row when it is local,
+ *                        appends the pick's canonical unit row, and runs the
+ *                        update pass over the shard's rows -- the one kernel
+ *                        of a step that reads the pool (each row once).
+ *   dal_kcenter_select   begin, then k x (propose, commit on the own record),
+ *                        all enqueued by one host call.
+ * n == 0 is a legal shard (pool, row_flags, m32 and inv_norm may be null): it
+ * proposes DAL_KEY_NONE and follows the commits.
+ *
+ * Before any HIP call: a null pointer, a record that is not 16-B aligned, or a
+ * descriptor that no dal_kcenter_begin filled, is DAL_ERR_ARG; d outside
+ * {64, 128, 256}, n < 0, n > INT32_MAX, ld < d, ld % 8, m < 1, k < 1,
+ * idx_base < 0, a pool, m32 or inv_norm that is not 16-B aligned, a workspace
+ * that is short or not 256-B aligned, t outside [0, k) or n_records < 1 are
+ * DAL_ERR_SHAPE; m + k > INT32_MAX DAL_ERR_CAPACITY.  A refused begin leaves no
+ * job behind.  A zero-norm row raises DAL_FLAG_ZERO_NORM in *dev_status. */
+#define DAL_ROW_PICKED 4 /* dal_kcenter_*: the row was picked by an earlier step */
+#define DAL_KCENTER_JOB_BYTES 512
+#define DAL_KCENTER_RECORD_BYTES(d) (32 + 2 * (size_t)(d))
+double dal_kcenter_error_bound(int64_t d);
+size_t dal_kcenter_workspace_bytes(int64_t n, int64_t d, int64_t m, int64_t k);
+int dal_kcenter_begin(void* job, const uint16_t* pool, int64_t n, int64_t d, int64_t ld, int64_t idx_base,
+                      uint8_t* row_flags, float* m32, const float* inv_norm, double* centers, int64_t m, int64_t k,
+                      void* ws, size_t ws_bytes, int64_t* out_idx, double* out_score, int32_t* dev_status,
+                      dal_stream_t stream);
+int dal_kcenter_propose(const void* job, int64_t t, void* record, dal_stream_t stream);
+int dal_kcenter_commit(const void* job, int64_t t, const void* records, int64_t n_records, dal_stream_t stream);
+int dal_kcenter_select(void* job, const uint16_t* pool, int64_t n, int64_t d, int64_t ld, int64_t idx_base,
+                       uint8_t* row_flags, float* m32, const float* inv_norm, double* centers, int64_t m, int64_t k,
+                       void* ws, size_t ws_bytes, int64_t* out_idx, double* out_score, int32_t* dev_status,
+                       dal_stream_t stream);
+
 /* ---- standalone similarity kernels --------------------------------------
  * cosine_similarity.py:42-45: every entry of U.U^T (fp32 MFMA), written to
  * out[n_pad][n_pad] (fp32).  similarity.py:38 (columnSimilarities, i<j) is
