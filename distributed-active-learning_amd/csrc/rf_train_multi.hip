@@ -4,10 +4,13 @@
 //                                impurity='gini', maxDepth=4, maxBins=32)
 //   final_thesis/uncertainty_sampling.py:71-76, density_weighting.py:119-124
 // The algorithm is the one of rf_train.hip (its header comment has the steps)
-// with C classes wherever two appear there; thresholds, binning, the status
-// reset and the heap finalize do not depend on the labels and are that file's
-// (rf_train_shared.hpp).  The binary kernels stay as they are: this file adds
-// the two level kernels for a class axis.
+// with C classes wherever two appear there, and the binary fit is this file's
+// at C = 2 (dal_rf_train*: its own job kind, the same kernels -- at C = 2 the
+// arithmetic below is the binary Gini's operation for operation).  This file
+// owns the two level kernels and the Gini of C counts; the begin step, binning,
+// the status reset and the heap finalize are rf_train.hip's
+// (rf_train_shared.hpp), routing, prefix sums, the first-maximum reduction,
+// the commit and the entry ladder are rf_train_device.hpp's.
 //
 //   histogram  [tree][node][slot][class][bin], bins innermost: the split
 //              kernel's lanes take consecutive split indices k and so read
@@ -24,19 +27,10 @@
 //              reduced over the wave by shuffles and over the four waves
 //              through 64 bytes of workspace per node (the LDS is the
 //              histogram's up to its last byte).
-#include <algorithm>
-#include <cfloat>
-#include <climits>
-
-#include "common.hpp"
-#include "rf_train_shared.hpp"
+#include "rf_train_device.hpp"
 
 namespace dal {
 namespace {
-
-constexpr int kSplitThreads = 256;
-constexpr int kSplitWaves = kSplitThreads / kWave;
-constexpr int kRedBytes = 64;  // per node: kSplitWaves gains (fp64) then kSplitWaves pair indices (int32)
 
 // Gini.calculate over C counts read through cnt(c); total = their sum.
 template <class Counts>
@@ -78,20 +72,9 @@ __global__ __launch_bounds__(256) void rf_hist_multi_kernel(RfArgs A, int C, int
   for (int64_t i = r0 + threadIdx.x; i < r1; i += blockDim.x) {
     const int w = A.weights[static_cast<int64_t>(t) * A.n + i];
     if (w <= 0) continue;
-    int32_t* nd = A.node + static_cast<int64_t>(t) * A.n + i;
-    int h = 0;
-    if (level > 0) {
-      const int hp = *nd;
-      if (hp < 0) continue;
-      const int f = A.split_f[static_cast<int64_t>(t) * n_inner + hp];
-      if (f < 0) {  // the row's node became a leaf
-        *nd = -1;
-        continue;
-      }
-      const int b = A.bins[i * A.d + f];
-      h = 2 * hp + 1 + (b > A.split_b[static_cast<int64_t>(t) * n_inner + hp] ? 1 : 0);
-    }
-    *nd = h;
+    const Routed R = route_row(A, t, i, level, n_inner);
+    if (!R.live) continue;
+    const int h = R.h;
     const int local = h - first;
     const int y = min(static_cast<int>(A.labels[i]), C - 1);
     atomicAdd(&cls_s[C * local + y], w);
@@ -105,7 +88,7 @@ __global__ __launch_bounds__(256) void rf_hist_multi_kernel(RfArgs A, int C, int
     }
   }
   __syncthreads();
-  int32_t* gcls = A.cls + static_cast<int64_t>(t) * nodes * C;
+  int32_t* gcls = A.tot + static_cast<int64_t>(t) * nodes * C;
   for (int e = threadIdx.x; e < C * nodes; e += blockDim.x)
     if (cls_s[e]) atomicAdd(&gcls[e], cls_s[e]);
   for (int e = threadIdx.x; e < hist_n; e += blockDim.x)
@@ -115,14 +98,12 @@ __global__ __launch_bounds__(256) void rf_hist_multi_kernel(RfArgs A, int C, int
 // The leaf's class -- the first index of the largest weighted count
 // (indexOfLargestArrayElement) -- over the leaf's heap subtree.
 __device__ __forceinline__ void fill_leaf_multi(const RfArgs& A, int C, int t, int h, int level, const int32_t* gc) {
-  const int n_inner = (1 << A.max_depth) - 1;
-  const int span = 1 << (A.max_depth - level);
-  const int first_leaf = (h + 1) * span - 1 - n_inner;
+  const LeafSpan L = leaf_span(A, t, h, level);
   int best = 0;
   for (int c = 1; c < C; ++c)
     if (gc[c] > gc[best]) best = c;
-  uint8_t* out = A.out_leaf + static_cast<int64_t>(t) * (n_inner + 1) + first_leaf;
-  for (int q = 0; q < span; ++q) out[q] = static_cast<uint8_t>(best);
+  uint8_t* out = A.out_leaf + L.first;
+  for (int q = 0; q < L.count; ++q) out[q] = static_cast<uint8_t>(best);  // (the loop is this kernel's: leaf_span)
 }
 
 // calculateImpurityStats (MLlib 2.1) for split k of slot s: left counts from
@@ -159,7 +140,7 @@ __global__ __launch_bounds__(kSplitThreads) void rf_split_multi_kernel(RfArgs A,
   const uint8_t s_h = st[h];  // (block-uniform: every return below is taken by the whole block)
   if (s_h == kAbsent) return;
   const int tid = threadIdx.x;
-  const int32_t* gc = A.cls + (static_cast<int64_t>(t) * nodes + local) * C;
+  const int32_t* gc = A.tot + (static_cast<int64_t>(t) * nodes + local) * C;
   if (s_h == kLeaf || level == A.max_depth) {
     if (tid == 0) {
       fill_leaf_multi(A, C, t, h, level, gc);
@@ -172,15 +153,7 @@ __global__ __launch_bounds__(kSplitThreads) void rf_split_multi_kernel(RfArgs A,
   const int32_t* sub = A.subsets + (static_cast<int64_t>(t) * n_inner + h) * A.m;
   for (int e = tid; e < node_ints; e += kSplitThreads) cum[e] = gh[e];
   __syncthreads();
-  for (int q = tid; q < A.m * C; q += kSplitThreads) {
-    const int nb = min(A.n_splits[sub[q / C]] + 1, A.hb);
-    int* row = cum + q * A.hb;
-    int a = 0;
-    for (int b = 0; b < nb; ++b) {
-      a += row[b];
-      row[b] = a;
-    }
-  }
+  prefix_sum_series(A, cum, C, sub, tid);
   __syncthreads();
   int64_t tc = 0;
   for (int c = 0; c < C; ++c) tc += gc[c];
@@ -199,33 +172,9 @@ __global__ __launch_bounds__(kSplitThreads) void rf_split_multi_kernel(RfArgs A,
       best_p = p;
     }
   }
-  // lexicographic first maximum over (gain desc, pair index asc): the wave, then the block
-  for (int o = 32; o > 0; o >>= 1) {
-    const double og = __shfl_xor(best, o);
-    const int op = __shfl_xor(best_p, o);
-    if (og > best || (og == best && op < best_p)) {
-      best = og;
-      best_p = op;
-    }
-  }
-  unsigned char* r = red + (static_cast<int64_t>(t) * nodes + local) * kRedBytes;
-  double* red_g = reinterpret_cast<double*>(r);
-  int* red_p = reinterpret_cast<int*>(r + kSplitWaves * 8);
-  if ((tid & (kWave - 1)) == 0) {
-    red_g[tid / kWave] = best;
-    red_p[tid / kWave] = best_p;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores have left this wave before the barrier
-  }
-  __syncthreads();
+  wave_first_max(best, best_p);
+  block_first_max(red + (static_cast<int64_t>(t) * nodes + local) * kRedBytes, best, best_p, tid);
   if (tid != 0) return;
-  for (int w = 1; w < kSplitWaves; ++w) {
-    const double og = red_g[w];
-    const int op = red_p[w];
-    if (og > best || (og == best && op < best_p)) {
-      best = og;
-      best_p = op;
-    }
-  }
   if (!(best > 0.0)) {  // gain <= 0 or no valid split: leaf
     fill_leaf_multi(A, C, t, h, level, gc);
     A.split_f[static_cast<int64_t>(t) * n_inner + h] = -1;
@@ -234,18 +183,73 @@ __global__ __launch_bounds__(kSplitThreads) void rf_split_multi_kernel(RfArgs A,
   const int s = best_p / A.kmax, k = best_p - s * A.kmax;
   double li = 0.0, ri = 0.0;
   split_gain_multi(cum + s * C * A.hb + k, A.hb, gc, C, tc, parent_imp, A.min_instances, A.min_gain, &li, &ri);
-  A.split_f[static_cast<int64_t>(t) * n_inner + h] = sub[s];
-  A.split_b[static_cast<int64_t>(t) * n_inner + h] = k;
-  const bool child_leaf = level + 1 == A.max_depth;
-  st[2 * h + 1] = (child_leaf || li == 0.0) ? kLeaf : kOpen;
-  st[2 * h + 2] = (child_leaf || ri == 0.0) ? kLeaf : kOpen;
+  commit_split(A, st, t, h, level, n_inner, sub[s], k, li, ri);
 }
 
-bool multi_shape_ok(int64_t n, int64_t d, int32_t n_trees, int32_t max_depth, int32_t m, int32_t num_splits,
-                    int32_t n_classes) {
-  return n >= 1 && d >= 1 && n_trees >= 1 && max_depth >= 1 && max_depth <= DAL_RF_MAX_DEPTH && m >= 1 &&
-         num_splits >= 0 && n_classes >= 2 && n_classes <= DAL_MC_MAX_CLASSES;
-}
+template <int32_t KIND>
+struct ClassTrainer {
+  using Job = RfJob;
+  static constexpr int32_t kKind = KIND;
+
+  // (n_classes sits before the outputs in the entries' argument lists)
+  static int begin(RfJob* J, void* job, int64_t min_n, hipStream_t st, const float* x, int64_t n, int64_t d,
+                   int64_t ldx, const uint8_t* labels, const float* thresholds, const int32_t* n_splits,
+                   int32_t num_splits, const int32_t* weights, const int32_t* feature_subsets, int32_t m,
+                   int32_t n_trees, int32_t max_depth, int32_t min_instances, double min_info_gain,
+                   int32_t n_classes, int32_t* out_inner, uint8_t* out_leaf, void* ws, size_t ws_bytes) {
+    return rf_classifier_begin(J, job, kKind, n_classes, min_n, st, x, n, d, ldx, labels, thresholds,
+                               n_splits, num_splits, weights, feature_subsets, m, n_trees, max_depth, min_instances,
+                               min_info_gain, out_inner, out_leaf, ws, ws_bytes);
+  }
+
+  // Zero the level's totals and histogram, then add the job's rows to them.
+  static int level_stats(const RfJob& J, int level, hipStream_t st) {
+    int64_t ints = 0;
+    const RfArgs A = rf_at_level(J, level, &ints);
+    const int C = J.C;
+    if (hipMemsetAsync(A.tot, 0, static_cast<size_t>(ints) * 4, st) != hipSuccess) return DAL_ERR_HIP;
+    if (A.n == 0) return DAL_OK;
+    const int64_t nodes = int64_t{1} << level;
+    const int64_t hist_ints = level < A.max_depth ? nodes * A.m * A.hb * C : 0;
+    const int rows_per_block = 1024;
+    const dim3 hgrid(static_cast<unsigned>(ceil_div(A.n, rows_per_block)), static_cast<unsigned>(A.T));
+    // class counts + level histogram within the LDS budget, else global atomics
+    const bool lds_hist = (C * nodes + hist_ints) * 4 <= kHistLdsBytes;
+    const size_t hsmem = static_cast<size_t>(C * nodes + (lds_hist ? hist_ints : 0)) * 4;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_hist_multi_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(hsmem)) != hipSuccess)
+      return DAL_ERR_HIP;
+    hipLaunchKernelGGL(rf_hist_multi_kernel, hgrid, dim3(256), hsmem, st, A, C, level, rows_per_block, lds_hist);
+    DAL_RETURN_IF_LAUNCH_FAILED();
+    return DAL_OK;
+  }
+
+  // Leaf or best split of every node of the level from the workspace's sums.
+  static int level_split(const RfJob& J, int level, hipStream_t st) {
+    int64_t ints = 0;
+    const RfArgs A = rf_at_level(J, level, &ints);
+    const size_t ssmem = level < A.max_depth ? static_cast<size_t>(A.m) * A.hb * J.C * 4 : 16;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_split_multi_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ssmem)) != hipSuccess)
+      return DAL_ERR_HIP;
+    hipLaunchKernelGGL(rf_split_multi_kernel, dim3(1u << level, static_cast<unsigned>(A.T)), dim3(kSplitThreads),
+                       ssmem, st, A, J.C, J.red, level);
+    DAL_RETURN_IF_LAUNCH_FAILED();
+    return DAL_OK;
+  }
+
+  static int finish(const RfJob& J, hipStream_t st) { return rf_launch_finalize(J.A, st); }
+};
+using Multi = RfLadder<ClassTrainer<kRfJobMulti>>;
+
+// The binary entries: two classes, and no n_classes in their argument lists.
+struct BinaryTrainer : ClassTrainer<kRfJobBinary> {
+  template <class... Args>
+  static int begin(RfJob* J, void* job, int64_t min_n, hipStream_t st, Args... args) {
+    return rf_classifier_begin(J, job, kKind, 2, min_n, st, args...);
+  }
+};
+using Binary = RfLadder<BinaryTrainer>;
 
 }  // namespace
 }  // namespace dal
@@ -254,66 +258,11 @@ using namespace dal;
 
 extern "C" size_t dal_rf_train_multiclass_workspace_bytes(int64_t n, int64_t d, int32_t n_trees, int32_t max_depth,
                                                           int32_t m, int32_t num_splits, int32_t n_classes) {
-  if (!multi_shape_ok(n, d, n_trees, max_depth, m, num_splits, n_classes)) return 0;
-  return rf_layout(n, d, n_trees, max_depth, m, num_splits + 2, n_classes, kRedBytes).total;
+  if (n < 1 || d < 1 || n_trees < 1 || max_depth < 1 || max_depth > DAL_RF_MAX_DEPTH || m < 1 || num_splits < 0 ||
+      n_classes < 2 || n_classes > DAL_MC_MAX_CLASSES)
+    return 0;
+  return rf_layout(n * d, n, n_trees, max_depth, m, num_splits + 2, n_classes, 4, kRedBytes).total;
 }
-
-namespace dal {
-namespace {
-
-// *J is the job; it is also copied to the caller's descriptor `job` (nullable)
-// before the first device call.
-int multi_begin(RfJob* J, void* job, const float* x, int64_t n, int64_t d, int64_t ldx, const uint8_t* labels,
-                const float* thresholds, const int32_t* n_splits, int32_t num_splits, const int32_t* weights,
-                const int32_t* feature_subsets, int32_t m, int32_t n_trees, int32_t max_depth, int32_t min_instances,
-                double min_info_gain, int32_t n_classes, int32_t* out_inner, uint8_t* out_leaf, void* ws,
-                size_t ws_bytes, int64_t min_n, hipStream_t st) {
-  if (const int rc = rf_job_setup(J, kRfJobMulti, n_classes, kRedBytes, x, n, d, ldx, labels, thresholds, n_splits,
-                                  num_splits, weights, feature_subsets, m, n_trees, max_depth, min_instances,
-                                  min_info_gain, out_inner, out_leaf, ws, ws_bytes, min_n))
-    return rc;
-  if (job) std::memcpy(job, J, sizeof *J);
-  return rf_launch_bin_and_reset(x, ldx, J->A, st);
-}
-
-// Zero the level's totals and histogram, then add the job's rows to them.
-int multi_level_stats(const RfJob& J, int level, hipStream_t st) {
-  int64_t ints = 0;
-  const RfArgs A = rf_at_level(J, level, &ints);
-  const int C = J.C;
-  if (hipMemsetAsync(A.cls, 0, static_cast<size_t>(ints) * 4, st) != hipSuccess) return DAL_ERR_HIP;
-  if (A.n == 0) return DAL_OK;
-  const int64_t nodes = int64_t{1} << level;
-  const int64_t hist_ints = level < A.max_depth ? nodes * A.m * A.hb * C : 0;
-  const int rows_per_block = 1024;
-  const dim3 hgrid(static_cast<unsigned>(ceil_div(A.n, rows_per_block)), static_cast<unsigned>(A.T));
-  // the budget of the binary kernel: class counts + level histogram within 64 KiB, else global atomics
-  const bool lds_hist = (C * nodes + hist_ints) * 4 <= 64 * 1024;
-  const size_t hsmem = static_cast<size_t>(C * nodes + (lds_hist ? hist_ints : 0)) * 4;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_hist_multi_kernel),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(hsmem)) != hipSuccess)
-    return DAL_ERR_HIP;
-  hipLaunchKernelGGL(rf_hist_multi_kernel, hgrid, dim3(256), hsmem, st, A, C, level, rows_per_block, lds_hist);
-  DAL_RETURN_IF_LAUNCH_FAILED();
-  return DAL_OK;
-}
-
-// Leaf or best split of every node of the level from the workspace's sums.
-int multi_level_split(const RfJob& J, int level, hipStream_t st) {
-  int64_t ints = 0;
-  const RfArgs A = rf_at_level(J, level, &ints);
-  const size_t ssmem = level < A.max_depth ? static_cast<size_t>(A.m) * A.hb * J.C * 4 : 16;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf_split_multi_kernel),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ssmem)) != hipSuccess)
-    return DAL_ERR_HIP;
-  hipLaunchKernelGGL(rf_split_multi_kernel, dim3(1u << level, static_cast<unsigned>(A.T)), dim3(kSplitThreads),
-                     ssmem, st, A, J.C, J.red, level);
-  DAL_RETURN_IF_LAUNCH_FAILED();
-  return DAL_OK;
-}
-
-}  // namespace
-}  // namespace dal
 
 extern "C" int dal_rf_train_multiclass_begin(void* job, const float* x, int64_t n_local, int64_t d, int64_t ldx,
                                              const uint8_t* labels, const float* thresholds,
@@ -322,34 +271,26 @@ extern "C" int dal_rf_train_multiclass_begin(void* job, const float* x, int64_t 
                                              int32_t max_depth, int32_t min_instances, double min_info_gain,
                                              int32_t n_classes, int32_t* out_inner, uint8_t* out_leaf, void* ws,
                                              size_t ws_bytes, dal_stream_t stream) {
-  RfJob J;
-  if (!job) return DAL_ERR_ARG;
-  return multi_begin(&J, job, x, n_local, d, ldx, labels, thresholds, n_splits, num_splits, weights, feature_subsets, m,
-                     n_trees, max_depth, min_instances, min_info_gain, n_classes, out_inner, out_leaf, ws, ws_bytes,
-                     0, as_stream(stream));
+  return Multi::begin(job, stream, x, n_local, d, ldx, labels, thresholds, n_splits, num_splits, weights,
+                      feature_subsets, m, n_trees, max_depth, min_instances, min_info_gain, n_classes, out_inner,
+                      out_leaf, ws, ws_bytes);
 }
 
 extern "C" int dal_rf_train_multiclass_level_stats(const void* job, int32_t level, dal_stream_t stream) {
-  RfJob J;
-  if (const int rc = rf_job_load(job, kRfJobMulti, level, &J)) return rc;
-  return multi_level_stats(J, level, as_stream(stream));
+  return Multi::level_stats(job, level, stream);
 }
 
 extern "C" int dal_rf_train_multiclass_level_split(const void* job, int32_t level, dal_stream_t stream) {
-  RfJob J;
-  if (const int rc = rf_job_load(job, kRfJobMulti, level, &J)) return rc;
-  return multi_level_split(J, level, as_stream(stream));
+  return Multi::level_split(job, level, stream);
 }
 
 extern "C" int dal_rf_train_multiclass_finish(const void* job, dal_stream_t stream) {
-  RfJob J;
-  if (const int rc = rf_job_load(job, kRfJobMulti, 0, &J)) return rc;
-  return rf_launch_finalize(J.A, as_stream(stream));
+  return Multi::finish(job, stream);
 }
 
 extern "C" int dal_rf_train_multiclass_level_span(const void* job, int32_t level, void** ptr, int32_t* elem_type,
                                                   int64_t* count) {
-  return rf_level_span(job, kRfJobMulti, level, ptr, elem_type, count);
+  return Multi::level_span(job, level, ptr, elem_type, count);
 }
 
 extern "C" int dal_rf_train_multiclass(const float* x, int64_t n, int64_t d, int64_t ldx, const uint8_t* labels,
@@ -358,15 +299,46 @@ extern "C" int dal_rf_train_multiclass(const float* x, int64_t n, int64_t d, int
                                        int32_t n_trees, int32_t max_depth, int32_t min_instances,
                                        double min_info_gain, int32_t n_classes, int32_t* out_inner,
                                        uint8_t* out_leaf, void* ws, size_t ws_bytes, dal_stream_t stream) {
-  RfJob J;
-  hipStream_t st = as_stream(stream);
-  if (const int rc = multi_begin(&J, nullptr, x, n, d, ldx, labels, thresholds, n_splits, num_splits, weights,
-                                 feature_subsets, m, n_trees, max_depth, min_instances, min_info_gain, n_classes,
-                                 out_inner, out_leaf, ws, ws_bytes, 1, st))
-    return rc;
-  for (int level = 0; level <= max_depth; ++level) {
-    if (const int rc = multi_level_stats(J, level, st)) return rc;
-    if (const int rc = multi_level_split(J, level, st)) return rc;
-  }
-  return rf_launch_finalize(J.A, st);
+  return Multi::fit(stream, x, n, d, ldx, labels, thresholds, n_splits, num_splits, weights, feature_subsets, m,
+                    n_trees, max_depth, min_instances, min_info_gain, n_classes, out_inner, out_leaf, ws, ws_bytes);
+}
+
+extern "C" size_t dal_rf_train_workspace_bytes(int64_t n, int64_t d, int32_t n_trees, int32_t max_depth, int32_t m,
+                                               int32_t num_splits) {
+  return dal_rf_train_multiclass_workspace_bytes(n, d, n_trees, max_depth, m, num_splits, 2);
+}
+
+extern "C" int dal_rf_train_begin(void* job, const float* x, int64_t n_local, int64_t d, int64_t ldx,
+                                  const uint8_t* labels, const float* thresholds, const int32_t* n_splits,
+                                  int32_t num_splits, const int32_t* weights, const int32_t* feature_subsets,
+                                  int32_t m, int32_t n_trees, int32_t max_depth, int32_t min_instances,
+                                  double min_info_gain, int32_t* out_inner, uint8_t* out_leaf, void* ws,
+                                  size_t ws_bytes, dal_stream_t stream) {
+  return Binary::begin(job, stream, x, n_local, d, ldx, labels, thresholds, n_splits, num_splits, weights,
+                       feature_subsets, m, n_trees, max_depth, min_instances, min_info_gain, out_inner, out_leaf, ws,
+                       ws_bytes);
+}
+
+extern "C" int dal_rf_train_level_stats(const void* job, int32_t level, dal_stream_t stream) {
+  return Binary::level_stats(job, level, stream);
+}
+
+extern "C" int dal_rf_train_level_split(const void* job, int32_t level, dal_stream_t stream) {
+  return Binary::level_split(job, level, stream);
+}
+
+extern "C" int dal_rf_train_finish(const void* job, dal_stream_t stream) { return Binary::finish(job, stream); }
+
+extern "C" int dal_rf_train_level_span(const void* job, int32_t level, void** ptr, int32_t* elem_type,
+                                       int64_t* count) {
+  return Binary::level_span(job, level, ptr, elem_type, count);
+}
+
+extern "C" int dal_rf_train(const float* x, int64_t n, int64_t d, int64_t ldx, const uint8_t* labels,
+                            const float* thresholds, const int32_t* n_splits, int32_t num_splits,
+                            const int32_t* weights, const int32_t* feature_subsets, int32_t m, int32_t n_trees,
+                            int32_t max_depth, int32_t min_instances, double min_info_gain, int32_t* out_inner,
+                            uint8_t* out_leaf, void* ws, size_t ws_bytes, dal_stream_t stream) {
+  return Binary::fit(stream, x, n, d, ldx, labels, thresholds, n_splits, num_splits, weights, feature_subsets, m,
+                     n_trees, max_depth, min_instances, min_info_gain, out_inner, out_leaf, ws, ws_bytes);
 }

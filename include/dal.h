@@ -798,7 +798,11 @@ int dal_parse_labeled_text(const char* text, size_t len, int64_t rows, int64_t c
  * out_inner [T][2^D - 1][2] = (feature, fp32 threshold bits), (0, +inf) below
  * a leaf; out_leaf [T][2^D] = class (first maximum of the weighted counts),
  * a shallow leaf's class repeated over its subtree.  ws: 256-B aligned,
- * dal_rf_train_workspace_bytes(...) bytes. */
+ * dal_rf_train_workspace_bytes(...) bytes: what
+ * dal_rf_train_multiclass_workspace_bytes returns at n_classes = 2 (the binary
+ * fit runs the C-class level kernels at C = 2, whose split step keeps 64 B of
+ * workspace per split node; a level's span, dal_rf_train_level_span, has the
+ * C-class interior [class][bin] at C = 2). */
 int dal_rf_find_splits(const float* x, int64_t n, int64_t d, int64_t ldx, const int64_t* sample_rows,
                        int64_t n_sample, int32_t num_splits, float* thresholds, int32_t* n_splits,
                        int32_t* dev_status, dal_stream_t stream);

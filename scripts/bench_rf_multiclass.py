@@ -24,8 +24,14 @@ the core count it used.
 --ab-lib PATH   time only the binary fit with the library at PATH (a build of
                 an older commit: scripts/ab_build.sh in that checkout) and with
                 this tree's, in alternating child processes, ALTERNATIONS each.
+                With --lib PATH2 the second side is the library at PATH2
+                instead of this tree's (PATH against itself: the spread of
+                the measurement).  With --ab-all the C-class fits are timed
+                on both sides as well.
+--n ROWS        labeled rows instead of 5,000 (200,000: the histogram kernel
+                is no longer launch-bound).
 
-    python scripts/bench_rf_multiclass.py [--rounds 5] [--reps 20] [--out DIR] [--ab-lib PATH]
+    python scripts/bench_rf_multiclass.py [--rounds 5] [--reps 20] [--n ROWS] [--out DIR] [--ab-lib PATH [--lib PATH2]]
 """
 import argparse
 import json
@@ -117,7 +123,7 @@ def child(rounds: int, reps: int, lib_path, variants) -> dict:
 
 def run_child(args, lib_path=None, binary_only=False) -> dict:
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--rounds", str(args.rounds), "--reps",
-           str(args.reps)]
+           str(args.reps), "--n", str(N)]
     if lib_path:
         cmd += ["--lib", lib_path]
     if binary_only:
@@ -147,28 +153,36 @@ def sklearn_fit() -> dict:
 
 
 def main():
+    global N
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--ab-lib", default=None)
+    ap.add_argument("--out-name", default=None)
+    ap.add_argument("--ab-all", action="store_true")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--lib", default=None)
     ap.add_argument("--binary-only", action="store_true")
+    ap.add_argument("--n", type=int, default=N)
     args = ap.parse_args()
+    N = args.n
     if args.child:
         print(json.dumps(child(args.rounds, args.reps, args.lib, (2,) if args.binary_only else (2,) + CLASSES)))
         return
     shape = f"{N} x {D} labeled rows, T={TREES}, depth {DEPTH}, 32 bins, sqrt features"
     if args.ab_lib:
-        runs = {"other": [], "this": []}
+        sides = (("other", args.ab_lib), ("this", args.lib))
+        runs = {}
         for _ in range(ALTERNATIONS):  # a failed child ends the run: nothing more is started
-            runs["other"].append(run_child(args, args.ab_lib, True)["fits"]["binary"]["median_ms"])
-            runs["this"].append(run_child(args, None, True)["fits"]["binary"]["median_ms"])
-        out = {"what": "binary fit (dal_rf_train), two library builds, alternating processes", "shape": shape,
-               "other_lib": args.ab_lib, "median_ms_per_process": runs,
-               "other_over_this": statistics.median(runs["other"]) / statistics.median(runs["this"])}
-        name = "binary_ab.json"
+            for side, lib in sides:
+                for fit, rec in run_child(args, lib, not args.ab_all)["fits"].items():
+                    runs.setdefault(fit, {"other": [], "this": []})[side].append(rec["median_ms"])
+        ratio = {fit: statistics.median(r["this"]) / statistics.median(r["other"]) for fit, r in runs.items()}
+        out = {"what": "fits per entry (binary: dal_rf_train), two library builds, alternating processes",
+               "shape": shape, "other_lib": args.ab_lib, "this_lib": args.lib or "this tree's",
+               "median_ms_per_process": runs, "this_over_other": ratio}
+        name = args.out_name or "binary_ab.json"
     else:
         out = {"what": "C-class fit against the binary fit, one process", "shape": shape, "gpu": run_child(args),
                "sklearn_host": sklearn_fit()}

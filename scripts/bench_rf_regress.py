@@ -22,7 +22,14 @@ RandomForestRegressor(max_depth=4, max_features=1/3, n_jobs=16).fit of the
 same rows is timed on the host in the parent.  No ratio is asserted: the
 numbers are recorded in profiles/rf_regress/bench.json.
 
-    python scripts/bench_rf_regress.py [--reps 5] [--out profiles/rf_regress]
+--ab-lib PATH   time the fits with the library at PATH (a build of another
+                commit: scripts/ab_build.sh in that checkout) and with this
+                tree's -- or, with --lib PATH2, the one at PATH2: PATH against
+                itself gives the spread of the measurement -- in alternating
+                child processes, ALTERNATIONS each; no kernel split, no
+                scikit-learn.  Written to regress_ab.json (--out-name) in --out.
+
+    python scripts/bench_rf_regress.py [--reps 5] [--out profiles/rf_regress] [--ab-lib PATH [--lib PATH2]]
 """
 import argparse
 import json
@@ -40,7 +47,7 @@ for p in (REPO, os.path.join(REPO, "distributed-active-learning_amd")):
 
 SHAPES = ((5000, 5, 2000), (20000, 5, 2000), (5000, 30, 100))  # n, d, T
 DEPTH = 4
-CHILD_TIMEOUT_S = 420
+CHILD_TIMEOUT_S, ALTERNATIONS = 420, 3
 
 
 def _rows(n, d):
@@ -81,9 +88,18 @@ def _kernel_split(fit):
     return out
 
 
-def child(reps: int) -> dict:
+def child(reps: int, lib_path=None, split=True) -> dict:
     import torch
 
+    if lib_path:  # another build: keep the symbols it has
+        import ctypes
+
+        from dal import _lib
+
+        _lib.LIB_PATH = os.path.abspath(lib_path)
+        probe = ctypes.CDLL(_lib.LIB_PATH)
+        for missing in [name for name in _lib.SIGNATURES if not hasattr(probe, name)]:
+            del _lib.SIGNATURES[missing]
     from dal.random_forest import bagging_inputs, check_regression_labels, train_regressor
 
     dev = torch.device("cuda:0")
@@ -108,10 +124,11 @@ def child(reps: int) -> dict:
         rec = _summary(ts)
         rec["label_limbs"] = {"k_y": k_y, "k_sq": k_sq, "words_per_cell": 1 + k_y + k_sq}
         rec["features_per_node"] = int(s.shape[2])
-        try:
-            rec["kernels"] = _kernel_split(fit)
-        except Exception as e:  # the timing above stands without the split
-            rec["kernels"] = {"error": repr(e)[:200]}
+        if split:
+            try:
+                rec["kernels"] = _kernel_split(fit)
+            except Exception as e:  # the timing above stands without the split
+                rec["kernels"] = {"error": repr(e)[:200]}
         out["shapes"][f"{n}x{d}_T{T}"] = rec
     return out
 
@@ -138,22 +155,43 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "rf_regress"))
     ap.add_argument("--child", action="store_true")
+    ap.add_argument("--ab-lib", default=None)
+    ap.add_argument("--lib", default=None)
+    ap.add_argument("--out-name", default=None)
     args = ap.parse_args()
     if args.child:
-        print(json.dumps(child(args.reps)))
+        print(json.dumps(child(args.reps, args.lib, split=not args.lib)))
         return
-    res = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--reps", str(args.reps)],
-                         capture_output=True, text=True, timeout=CHILD_TIMEOUT_S)
-    if res.returncode != 0:
-        sys.stderr.write(res.stdout[-2000:] + res.stderr[-4000:])
-        raise SystemExit(f"child failed with status {res.returncode}")
-    out = {"what": "train_regressor (exact variance histograms) per fit, and scikit-learn on the same host",
-           "depth": DEPTH, "max_bins": 32, "gpu": json.loads(res.stdout.strip().splitlines()[-1]),
-           "sklearn_host": sklearn_fit()}
+
+    def run_child(lib_path):
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--reps", str(args.reps)]
+        res = subprocess.run(cmd + (["--lib", lib_path] if lib_path else []), capture_output=True, text=True,
+                             timeout=CHILD_TIMEOUT_S)
+        if res.returncode != 0:
+            sys.stderr.write(res.stdout[-2000:] + res.stderr[-4000:])
+            raise SystemExit(f"child failed with status {res.returncode}")
+        return json.loads(res.stdout.strip().splitlines()[-1])
+
+    if args.ab_lib:
+        this_lib = args.lib or os.path.join(REPO, "distributed-active-learning_amd", "dal", "libdal.so")
+        runs = {}
+        for _ in range(ALTERNATIONS):  # a failed child ends the run: nothing more is started
+            for side, lib in (("other", args.ab_lib), ("this", this_lib)):
+                for shape, rec in run_child(lib)["shapes"].items():
+                    runs.setdefault(shape, {"other": [], "this": []})[side].append(rec["median_ms"])
+        out = {"what": "train_regressor per fit, two library builds, alternating processes", "reps": args.reps,
+               "other_lib": args.ab_lib, "this_lib": os.path.relpath(this_lib, REPO), "median_ms_per_process": runs,
+               "this_over_other": {shape: statistics.median(r["this"]) / statistics.median(r["other"])
+                                   for shape, r in runs.items()}}
+        name = args.out_name or "regress_ab.json"
+    else:
+        out = {"what": "train_regressor (exact variance histograms) per fit, and scikit-learn on the same host",
+               "depth": DEPTH, "max_bins": 32, "gpu": run_child(None), "sklearn_host": sklearn_fit()}
+        name = "bench.json"
     text = json.dumps(out, indent=1)
     print(text)
     os.makedirs(args.out, exist_ok=True)
-    with open(os.path.join(args.out, "bench.json"), "w") as f:
+    with open(os.path.join(args.out, name), "w") as f:
         f.write(text + "\n")
 
 

@@ -159,12 +159,34 @@ def _raw_train(cuda, X, y, w, s, depth, n_classes):
     return inner.cpu().numpy().tobytes(), leaf.cpu().numpy().tobytes()
 
 
-def test_two_classes_equal_the_binary_entry(cuda):
+@functools.lru_cache(maxsize=None)
+def _two_class_set():
     from dal.random_forest import bagging_inputs
 
     g = load_golden("checkerboard4x4.npz")
     X, y = g["X"], g["y"].astype(np.int64)
     w, s = bagging_inputs(X.shape[0], X.shape[1], 10, 4, seed=14)
+    return X, y, w, s
+
+
+def test_two_classes_equal_the_binary_oracle(cuda):
+    """The binary entry runs the C-class kernels at C = 2, so the yardstick of
+    the two-class fit is the binary CPU restatement (oracle/rf_oracle.py), byte
+    for byte, not the other entry."""
+    from oracle import rf_oracle
+
+    X, y, w, s = _two_class_set()
+    _, sf, st, lc = rf_oracle.train_classifier(X, y, w, s, max_depth=4)
+    assert ((sf >= 0).sum(axis=1) >= 9).all()  # real trees
+    inner = np.zeros(sf.shape + (2,), dtype=np.int32)
+    inner[..., 1] = np.array([np.inf], dtype=np.float32).view(np.int32)[0]
+    inner[..., 0][sf >= 0] = sf[sf >= 0]
+    inner[..., 1][sf >= 0] = st[sf >= 0].astype(np.float32).view(np.int32)
+    assert _raw_train(cuda, X, y, w, s, 4, 2) == (inner.tobytes(), lc.astype(np.uint8).tobytes())
+
+
+def test_two_classes_equal_the_binary_entry(cuda):
+    X, y, w, s = _two_class_set()
     assert _raw_train(cuda, X, y, w, s, 4, 2) == _raw_train(cuda, X, y, w, s, 4, None)
 
 

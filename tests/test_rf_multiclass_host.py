@@ -154,6 +154,36 @@ def test_abi_rejects_before_any_hip_call():
         assert ws(*bad) == 0
 
 
+# (n, d, T, depth, m, num_splits): multiclass at C = 2 and 32, regressor at k_y = k_sq = 1 and
+# DAL_RF_REG_MAX_LIMBS (8) -- bytes returned by the library of the commit before the trainers'
+# shared layout function (rf_layout), which must return the same.  Last column: what
+# dal_rf_train_workspace_bytes returned there, before the binary fit ran the C-class kernels
+# (their 64 B of scratch per split node came on top).
+WORKSPACE_BYTES = [
+    ((1, 1, 1, 1, 1, 0), 2048, 2048, 1792, 2304, 1792),                              # n = 1, depth 1
+    ((1000, 784, 10, 4, 28, 31), 1424128, 10313728, 1825280, 10122240, 1419008),
+    ((5000, 64, 10, 4, 8, 31), 697600, 3251200, 718080, 3101440, 692480),
+    ((1025, 64, 2, 6, 8, 31), 215808, 2258688, 422400, 2329088, 211712),
+    ((333, 7, 3, 10, 7, 254), 22180352, 352850432, 66267136, 374892544, 22082048),   # DAL_RF_MAX_DEPTH
+    ((200000, 64, 10, 4, 8, 31), 20977408, 23531008, 8517888, 10901248, 20972288),
+    ((1000, 784, 10, 11, 28, 31), 0, 0, 0, 0, 0),                                    # depth 11: rejected
+]
+
+
+@pytest.mark.parametrize("shape,c2,c32,k1,k8,binary_before", WORKSPACE_BYTES,
+                         ids=[str(r[0]) for r in WORKSPACE_BYTES])
+def test_workspace_bytes_are_what_they_were(shape, c2, c32, k1, k8, binary_before):
+    from dal import _lib
+
+    lib = _lib.load()
+    n, d, T, depth, m, ns = shape
+    multi, regress = lib.dal_rf_train_multiclass_workspace_bytes, lib.dal_rf_train_regressor_workspace_bytes
+    assert multi(*shape, 2) == c2 and multi(*shape, 32) == c32
+    assert regress(n, T, depth, m, ns, 1, 1) == k1 and regress(n, T, depth, m, ns, 8, 8) == k8
+    assert lib.dal_rf_train_workspace_bytes(*shape) == multi(*shape, 2)
+    assert binary_before <= c2
+
+
 # ----------------------------------------------------------------------- loop --
 def test_run_loop_num_classes_argument():
     from dal.loop import run_loop

@@ -1,4 +1,5 @@
-"""GPU random-forest training (dal.random_forest, csrc/rf_train.hip) against
+"""GPU random-forest training (dal.random_forest; csrc/rf_train.hip and the
+level kernels of csrc/rf_train_multi.hip at two classes) against
 the CPU restatement of MLlib 2.1's RandomForest.trainClassifier
 (oracle/rf_oracle.py; reference call sites final_thesis/uncertainty_sampling.py:71-76,
 density_weighting.py:119-124).
@@ -194,12 +195,14 @@ def test_gpu_trained_forest_votes_and_predict(cuda):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["min_instances", "min_gain", "bins4", "bins100", "depth1", "constant_feature",
-                                  "one_class", "sampled_thresholds", "heavy_weights"])
+                                  "one_class", "sampled_thresholds", "heavy_weights", "global_atomics"])
 def test_gpu_train_edge_cases_match_oracle(cuda, case):
     """MLlib's strategy knobs and degenerate inputs: minInstancesPerNode,
     minInfoGain, maxBins, depth 1, a constant feature, a single-class label
-    set, thresholds fitted on a row sample (n > max(maxBins^2, 10000)), and
-    large bootstrap counts."""
+    set, thresholds fitted on a row sample (n > max(maxBins^2, 10000)), large
+    bootstrap counts, and a level whose histogram is past the kernel's LDS
+    budget over a second block of rows (level 5: 32 nodes x 8 slots x 33 bins
+    x 2 classes x 4 B > 64 KiB; 1,025 rows = 1,024 + 1)."""
     from dal.random_forest import bagging_inputs, split_sample_rows, train_classifier
 
     rng = np.random.default_rng(17)
@@ -226,6 +229,10 @@ def test_gpu_train_edge_cases_match_oracle(cuda, case):
         n = 20000
         X = rng.random((n, d), dtype=np.float32)
         y = (X[:, 2] > 0.4).astype(np.int64)
+    elif case == "global_atomics":
+        n, d, T, depth = 1025, 64, 2, 6
+        X = rng.standard_normal((n, d)).astype(np.float32)
+        y = ((X[:, :8].sum(axis=1) > 0) ^ (rng.random(n) < 0.2)).astype(np.int64)  # noisy: no early pure nodes
     w, s = bagging_inputs(n, d, T, depth, seed=5)
     if case == "heavy_weights":
         w = (w * 37).astype(np.int32)
@@ -235,6 +242,9 @@ def test_gpu_train_edge_cases_match_oracle(cuda, case):
     if case == "sampled_thresholds":
         assert rows is not None and 0 < rows.size <= 16384
     _, sf, st, lc = R.train_classifier(X, y, w, s, max_depth=depth, max_bins=max_bins, split_rows=rows, **okw)
+    if case == "global_atomics":
+        assert s.shape[2] == 8 and (w[:, 1024:] > 0).any()  # 8 slots; the second block holds a drawn row
+        assert (sf[:, 31:63] >= 0).any(axis=1).all()        # every tree splits an (open) node at level 5
     inner, leaf = _oracle_heap(sf, st, lc)
     assert np.array_equal(F.inner, inner)
     assert np.array_equal(F.leaf, leaf)
