@@ -128,12 +128,15 @@ class DeviceGuard {
 // DAL_STEP_WS_CLEAN) with the plan's flag hooks and publishing slot: the
 // binary dw_step_impl or the C-class dw_step_multiclass_impl.
 template <class Step>
-static int plan_create(int64_t n, const uint8_t* base_flags, uint8_t* flags, int64_t idx_base, int64_t k, void* ws,
-                       size_t ws_bytes, int64_t* out_pair, int32_t* dev_status, dal_stream_t stream,
-                       dal_dw_plan_t** plan_out, Step&& step) {
-  if (!plan_out || !base_flags || !flags || !out_pair || !ws) return DAL_ERR_ARG;
+static int plan_create(const float* x, int64_t n, int64_t d, int64_t ldx, const uint8_t* base_flags, uint8_t* flags,
+                       int64_t idx_base, int64_t k, void* ws, size_t ws_bytes, int64_t* out_pair,
+                       int32_t* dev_status, dal_stream_t stream, dal_dw_plan_t** plan_out, Step&& step) {
+  if (!plan_out) return DAL_ERR_ARG;
   *plan_out = nullptr;
-  if (n < 1 || k < 1) return DAL_ERR_SHAPE;
+  if (!x || !base_flags || !flags || !out_pair || !ws) return DAL_ERR_ARG;
+  // the pool and its shape are refused here, before the workspace is touched
+  // and a capture begun (the captured step would report them only after both)
+  if (n < 1 || k < 1 || d < 1 || ldx < d) return DAL_ERR_SHAPE;
   hipStream_t st = as_stream(stream);
   const DeviceGuard guard(st);
   if (!guard.ok()) return DAL_ERR_HIP;
@@ -218,7 +221,7 @@ extern "C" int dal_dw_plan_create(const float* x, const float* xb, const void* f
                                   size_t ws_bytes, int32_t* votes, double* scores, uint64_t* keys_lo,
                                   uint64_t* keys_hi, int64_t* out_pair, uint64_t* out_keys, int32_t* dev_status,
                                   dal_stream_t stream, dal_dw_plan_t** plan_out) {
-  return plan_create(n, base_flags, flags, idx_base, k, ws, ws_bytes, out_pair, dev_status, stream, plan_out,
+  return plan_create(x, n, d, ldx, base_flags, flags, idx_base, k, ws, ws_bytes, out_pair, dev_status, stream, plan_out,
                      [&](hipStream_t cs, const ForestStepHooks& hooks, PlanSlot* slot) {
                        return dw_step_impl(x, xb, fprep, n, d, ldx, inner, leaf, n_trees, depth, lut, density_fixed,
                                            density_err, flags, beta, idx_base, norm64, colsum, k, cap, level1_passes,
@@ -243,7 +246,7 @@ extern "C" int dal_dw_plan_create_multiclass(const float* x, const float* xb, co
                                              dal_dw_plan_t** plan_out) {
   const McStepScore M{x, xb, fprep, n, d, ldx, inner, leaf, n_trees, depth, n_classes, lut, density_fixed,
                       density_err, beta, counts, pred, entropy, row_index};
-  return plan_create(n, base_flags, flags, idx_base, k, ws, ws_bytes, out_pair, dev_status, stream, plan_out,
+  return plan_create(x, n, d, ldx, base_flags, flags, idx_base, k, ws, ws_bytes, out_pair, dev_status, stream, plan_out,
                      [&](hipStream_t cs, const ForestStepHooks& hooks, PlanSlot* slot) {
                        return dw_step_multiclass_impl(M, flags, idx_base, norm64, colsum, k, cap, level1_passes,
                                                       DAL_STEP_RESET_STATUS | DAL_STEP_WS_CLEAN, ws, ws_bytes, scores,

@@ -18,7 +18,27 @@
  *    Data-dependent conditions found by a kernel (zero-norm row, candidate
  *    overflow) are OR-ed into the caller's device word ``dev_status``
  *    (DAL_FLAG_*), which the caller reads after synchronising.
- *  - Pool rows are fp32, row-major with leading dimension ``ldx`` (floats).
+ *  - Pool rows are fp32, row-major with leading dimension ``ldx`` (floats):
+ *    element (i, f) is x[i * ldx + f].  Every entry that takes an ``ldx``
+ *    accepts ANY ldx >= d (ldx < d is DAL_ERR_SHAPE, found on the host before
+ *    any device call) and an ``x`` that is only 4-byte aligned (8 bytes for
+ *    the fp64 rows of DAL_X_F64).  The ldx - d padding elements of a row are
+ *    never read as data and never written, nor is anything before x or after
+ *    the last row's d-th element.  The outputs are bit-identical for every
+ *    stride and every alignment of the same logical matrix: the 16-byte and
+ *    LDS-DMA staging of the forest kernels is taken when d % 4 == 0,
+ *    ldx % 4 == 0 and x is 16-byte aligned, and 4-byte loads otherwise -- a
+ *    matter of speed alone (the rows per block, and with them the row groups
+ *    of dal_dw_step's fast level 1, follow the staging; the selection does
+ *    not).  The same holds for the ``ld`` (elements) of a bf16 pool, 2-byte
+ *    aligned.  The entries that ask for more say so and refuse the rest with
+ *    DAL_ERR_SHAPE: dal_kcenter_begin / dal_kcenter_select (ld % 8 == 0 and a
+ *    16-byte aligned pool), dal_max_cosine / dal_max_cosine_unit (a
+ *    contiguous, 16-byte aligned [n][d] pool: they take no ld), and the
+ *    normalised rows ``u`` of dal_gram_rowsum / dal_split_f16 (ld % 4 == 0,
+ *    16-byte aligned) -- a library-made buffer, not the caller's pool.
+ *    tests/test_gpu_strided_pool.py and tests/test_gpu_strided_bf16.py hold
+ *    every such entry to this on poisoned, strided and misaligned pools.
  *  - Normalised pool buffer ``u``: [n_pad][d_pad] fp32, rows padded with zero
  *    rows to dal_pad_rows(n), features padded with zeros to
  *    dal_pad_features(d).  Zero rows/features contribute exactly 0.
@@ -630,7 +650,10 @@ int dal_dw_step_multiclass_form(int64_t n, int64_t d, int32_t n_trees, int32_t d
  * the plan; dal_dw_plan_destroy frees it.  xb (ABI v9) and fprep (ABI v10;
  * both nullable): as dal_dw_step's -- the plan reads fprep at its captured
  * address on every replay, so a new forest is re-prepared into the same
- * buffer before the next run. */
+ * buffer before the next run.  A null x, base_flags, flags, out_pair, ws or
+ * plan is DAL_ERR_ARG and n < 1, k < 1, d < 1 or ldx < d DAL_ERR_SHAPE, both
+ * before the workspace is touched or a capture begun (*plan is then NULL);
+ * the step's other checks are made while it is captured. */
 typedef struct dal_dw_plan dal_dw_plan_t;
 int dal_dw_plan_create(const float* x, const float* xb, const void* fprep, int64_t n, int64_t d, int64_t ldx,
                        const int32_t* inner,
