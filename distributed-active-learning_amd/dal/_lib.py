@@ -280,6 +280,10 @@ SIGNATURES = {
     "dal_kcenter_commit": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "dal_kcenter_select": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dal_kcenter_ranked_workspace_bytes": (c_size_t, [c_int64]),
+    "dal_kcenter_ranked_error_bound": (c_double, [c_int64, c_double]),
+    "dal_kcenter_ranked_attach": (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "dal_kcenter_run": (c_int, [c_void_p, c_void_p]),
 }
 
 _lib = None

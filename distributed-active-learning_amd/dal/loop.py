@@ -96,7 +96,8 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
              window_size: int = 10, n_estimators: int = 10, max_iterations=None,
              seed: int = 0, select_fn=None, device=None, beta: float = 1.0,
              verbose: bool = False, trainer="gpu", num_classes=None, lal_model=None,
-             initial_labeled=None, measures=None, hist_fn=None, density_over: str = "initial") -> LoopResult:
+             initial_labeled=None, measures=None, hist_fn=None, density_over: str = "initial",
+             alpha=None, sim_pool=None) -> LoopResult:
     """Run the AL loop.  strategy: "uncertainty" (uncertainty_sampling.py),
     "density" (density_weighting.py, E = L0 = range(window_size)),
     "information_density" (class entropy x density, E = L0;
@@ -104,8 +105,11 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     lal_direct_mllib_implementation/classes/active_learner.py:240-343:
     dal.active_learner.select_lal with ``lal_model``, a
     dal.forest.RegressionForest over the five LAL features; binary only; the
-    labeled count and its positives come from the current labeled set) or
-    "random".
+    labeled count and its positives come from the current labeled set),
+    "ranked_batch" (dal.uncertainty_sampling.select_batch: the least-confidence
+    weight x diversity greedy batch against the current labeled set; binary or
+    ``num_classes``; ``alpha`` and ``sim_pool`` are passed on and belong to
+    this strategy alone) or "random".
     trainer: see train_forest.  Labels of more than two values: "uncertainty"
     and "information_density" score the C-class forest
     (Forest.from_sklearn(rf, multiclass=True)) and need trainer="sklearn" or a
@@ -162,6 +166,8 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     # votes, dal.engine.multiclass_step) over a scikit-learn or caller-trained
     # forest, or one the GPU trainer fits when num_classes is given; density
     # weighting is binary
+    if strategy != "ranked_batch" and (alpha is not None or sim_pool is not None):
+        raise ValueError("alpha and sim_pool belong to strategy='ranked_batch'")
     classes = np.unique(np.asarray(y))
     multiclass = classes.size > 2
     if num_classes is not None and int(num_classes) < max(classes.size, 2):
@@ -199,6 +205,10 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
 
         excluded = np.asarray(labeled, dtype=np.int64) if strategy in ("density", "information_density") else None
         state = PoolState(X, excluded=excluded, device=device)
+        if sim_pool is not None:
+            from .similarity import _bf16_pool
+
+            sim_pool, _ = _bf16_pool(sim_pool, state.device)  # uploaded and rounded once
     it = 1
     while True:
         line = f"labeled =  {len(labeled)}  unlabeled =  {unlabeled.size}"
@@ -256,6 +266,9 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
             if strategy == "uncertainty":
                 from .uncertainty_sampling import select
                 sel = select(state, unlabeled, forest, k)
+            elif strategy == "ranked_batch":
+                from .uncertainty_sampling import select_batch
+                sel = select_batch(state, unlabeled, lab, forest, k, alpha=alpha, sim_pool=sim_pool)
             elif strategy == "density":
                 from .density_weighting import select
                 sel = select(state, unlabeled, forest, k, beta=beta)

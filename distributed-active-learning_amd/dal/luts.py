@@ -70,3 +70,46 @@ def multiclass_lut(strategy: str, n_trees: int) -> np.ndarray:
     else:
         raise ValueError(f"unknown strategy {strategy!r}; expected one of {STRATEGIES}")
     return np.array(vals, dtype=np.float64)
+
+
+# Ranked batch-mode selection (dal.similarity.ranked_batch_select) wants a
+# weight in [0, 1], higher = more uncertain.  Binary forests: one table of
+# T + 1 entries per strategy, Python floats from the tables above,
+#   least_confidence  1.0 - 2.0 * lc[v]      lc = lut("least_confidence", T)
+#   margin            1.0 - mg[v]            mg = lut("margin", T)
+#   entropy           (0.0 + h[T - v]) + h[v], h = multiclass_lut("entropy", T):
+#                     the two-term Shannon entropy in class order (class 0 has
+#                     T - v votes), 0 at v in {0, T}, 1 at v = T / 2.
+# The reference's one-sided entropy score (lut("entropy", T)) is NaN at v = T
+# and is not a weight.
+def batch_weight_lut(strategy: str, n_trees: int) -> np.ndarray:
+    T = int(n_trees)
+    if strategy == "least_confidence":
+        vals = [1.0 - 2.0 * float(s) for s in lut("least_confidence", T)]
+    elif strategy == "margin":
+        vals = [1.0 - float(s) for s in lut("margin", T)]
+    elif strategy == "entropy":
+        h = [float(s) for s in multiclass_lut("entropy", T)]
+        vals = [(0.0 + h[T - v]) + h[v] for v in range(T + 1)]
+    else:
+        raise ValueError(f"unknown strategy {strategy!r}; expected one of {STRATEGIES}")
+    return np.array(vals, dtype=np.float64)
+
+
+def batch_weights_multiclass(strategy: str, scores, n_classes: int):
+    """The ranked batch-mode weights of a C-class step from its fp64 scores
+    (numpy array or torch tensor; dal.engine.multiclass_step's ``scores``),
+    one fp64 operation per row: least_confidence 1 - maxp, margin 1 - margin,
+    entropy H / log2(C) with the module's log(x)/log(2), then capped at 1 (the
+    uniform vote's quotient can round one ulp above)."""
+    C = int(n_classes)
+    if C < 2:
+        raise ValueError("n_classes must be >= 2")
+    if strategy in ("least_confidence", "margin"):
+        return 1.0 - scores
+    if strategy != "entropy":
+        raise ValueError(f"unknown strategy {strategy!r}; expected one of {STRATEGIES}")
+    if isinstance(scores, np.ndarray):
+        return (scores / _log2(C)).clip(max=1.0)
+    # a tensor divisor: dividing a device tensor by a Python float multiplies by its reciprocal
+    return (scores / scores.new_full((1,), _log2(C))).clamp(max=1.0)

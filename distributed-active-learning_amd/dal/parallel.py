@@ -1247,25 +1247,48 @@ def emulate_train_regressor(shards, n_total: int, num_trees: int = 10, max_depth
 
 
 # ------------------------------------------------------- greedy k-center --
-def _kcenter(shards, ops, steps, labeled_rows, k: int, candidates):
+def _kcenter(shards, ops, steps, labeled_rows, k: int, candidates, weights=None, alpha=None):
     """kcenter_select_sharded over the jobs of ``shards`` = [(x_local,
     row_base)] with the local halves ``steps`` (one per job) and the
     collectives ``ops``: one all-reduce SUM of the in-range candidate counts
     fixes the number of steps on every rank alike; then per step propose, one
-    all-gather of one record per rank, commit -- no host read in the loop."""
+    all-gather of one record per rank, commit -- no host read in the loop.
+
+    weights: one fp64 array per job (the shard's rows) makes it the ranked
+    batch-mode selection; its default alpha is formed from the all-reduced
+    count, the same float on every rank."""
     from .engine import Selection
 
     if int(k) < 1:
         raise ValueError("k must be >= 1")
-    counts = [st.prepare(x_local, row_base, labeled_rows, candidates) for (x_local, row_base), st in zip(shards, steps)]
-    kk = min(int(k), int(ops.reduce(counts, "sum")[0].item()))
+    if weights is None:
+        counts = [st.prepare(x_local, row_base, labeled_rows, candidates)
+                  for (x_local, row_base), st in zip(shards, steps)]
+    else:
+        from .similarity import check_alpha, default_alpha
+
+        if alpha is not None:
+            alpha = check_alpha(alpha)
+        counts = [st.prepare(x_local, row_base, labeled_rows, candidates, weights=w, alpha=alpha)
+                  for (x_local, row_base), st, w in zip(shards, steps, weights)]
+    total = int(ops.reduce(counts, "sum")[0].item())
+    kk = min(int(k), total)
+    if weights is not None and alpha is None:
+        for st in steps:
+            st.alpha = default_alpha(total, len(labeled_rows))
     for st in steps:
         st.begin(kk)
     for t in range(kk):
         for st, records in zip(steps, ops.gather_row([st.propose(t) for st in steps])):
             st.commit(t, records)
-    return [Selection(scores=scores, indices=idx, selected_scores=sc)
-            for idx, sc, scores in (st.finish() for st in steps)]
+    sels = []
+    for st in steps:
+        idx, sc, scores = st.finish()
+        sel = Selection(scores=scores, indices=idx, selected_scores=sc)
+        if weights is not None:
+            sel.selected_similarity = st.selected_similarity
+        sels.append(sel)
+    return sels
 
 
 def kcenter_select_sharded(x_local, row_base: int, labeled_rows, k: int, comm, candidates=None, device=None,
@@ -1299,16 +1322,57 @@ def emulate_kcenter(shards, labeled_rows, k: int, candidates=None, steps=None):
     called once per shard (None: HipKCenterSteps).  The P jobs must agree on
     the picks; the Selection carries them and the shards' scores concatenated
     in shard order."""
-    from .engine import Selection
     from .similarity import HipKCenterSteps
 
-    torch = __import__("torch")
     shards = list(shards)
     sels = _kcenter(shards, _LocalOps(), [(steps or HipKCenterSteps)() for _ in shards], labeled_rows, k, candidates)
+    return _same_selection(sels)
+
+
+def _same_selection(sels):
+    """The one Selection of P emulated jobs, which must agree on the picks: it
+    carries them and the shards' scores concatenated in shard order."""
+    from .engine import Selection
+
+    torch = __import__("torch")
     first = sels[0]
+    ranked = hasattr(first, "selected_similarity")
     for s in sels[1:]:
         if not (torch.equal(s.indices.cpu(), first.indices.cpu())
-                and torch.equal(s.selected_scores.cpu().view(torch.int64), first.selected_scores.cpu().view(torch.int64))):
+                and torch.equal(s.selected_scores.cpu().view(torch.int64), first.selected_scores.cpu().view(torch.int64))
+                and (not ranked or torch.equal(s.selected_similarity.cpu().view(torch.int64),
+                                               first.selected_similarity.cpu().view(torch.int64)))):
             raise RuntimeError("the shards' k-center selections differ")
-    return Selection(scores=torch.cat([s.scores.to(first.scores.device) for s in sels]), indices=first.indices,
-                     selected_scores=first.selected_scores)
+    sel = Selection(scores=torch.cat([s.scores.to(first.scores.device) for s in sels]), indices=first.indices,
+                    selected_scores=first.selected_scores)
+    if ranked:
+        sel.selected_similarity = first.selected_similarity
+    return sel
+
+
+def ranked_batch_select_sharded(x_local, row_base: int, labeled_rows, weights_local, k: int, comm, alpha=None,
+                                candidates=None, device=None, steps=None):
+    """dal.similarity.ranked_batch_select over a row-sharded bf16 pool, as
+    kcenter_select_sharded: on every rank the indices, fp64 scores and
+    ``selected_similarity`` of the single-device selection of the whole pool,
+    for every shard count.  ``weights_local``: fp64, one per row of x_local.
+    alpha None: |C| / (|C| + m) from the candidate count that the up-front
+    all-reduce already sums, so every rank forms the same float; it is one
+    number per call, not recomputed per pick.  Still ONE all-gather of one
+    record per rank per step (the record's reserved word carries the pick's
+    similarity)."""
+    from .similarity import HipKCenterSteps
+
+    return _kcenter([(x_local, row_base)], _GroupOps(comm), [steps or HipKCenterSteps(device)], labeled_rows, k,
+                    candidates, weights=[weights_local], alpha=alpha)[0]
+
+
+def emulate_ranked_batch(shards, labeled_rows, weights, k: int, alpha=None, candidates=None, steps=None):
+    """ranked_batch_select_sharded with P shards [(x_local, row_base), ...] and
+    their weights [w_local, ...] in one process (tests), as emulate_kcenter."""
+    from .similarity import HipKCenterSteps
+
+    shards = list(shards)
+    sels = _kcenter(shards, _LocalOps(), [(steps or HipKCenterSteps)() for _ in shards], labeled_rows, k, candidates,
+                    weights=list(weights), alpha=alpha)
+    return _same_selection(sels)

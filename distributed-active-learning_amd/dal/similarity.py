@@ -382,6 +382,24 @@ def diversity_select(pool, labeled_idx, k: int, candidates=None, device=None, ro
 # ---------------------------------------------------------------------------
 # Greedy k-center (farthest-first) batch selection
 # ---------------------------------------------------------------------------
+def check_alpha(alpha) -> float:
+    """alpha of a ranked batch-mode job as a float in (0, 1]."""
+    try:
+        a = float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"alpha must be a float in (0, 1], not {alpha!r}") from None
+    if not (0.0 < a <= 1.0):
+        raise ValueError(f"alpha must be a float in (0, 1], not {alpha!r}")
+    return a
+
+
+def default_alpha(n_candidates: int, m: int) -> float:
+    """The ranked batch-mode default |C| / (|C| + m), in Python floats from the
+    two integers (1.0 without a candidate: no step runs)."""
+    n_candidates, m = int(n_candidates), int(m)
+    return n_candidates / (n_candidates + m) if n_candidates > 0 else 1.0
+
+
 class HipKCenterSteps:
     """The local half of a greedy k-center selection on one device: the
     dal_kcenter_* step entries over one row shard.  The single-device
@@ -391,19 +409,25 @@ class HipKCenterSteps:
     prepare(x_local, row_base, labeled_rows, candidates) -> int64 [1] tensor,
         the number of candidates inside this shard (``candidates`` None: every
         row); computes m(0) and the row flags, nothing is read back;
-    begin(kk)       the job for kk steps (dal_kcenter_begin);
+        ``weights`` (fp64, one per row of x_local) and ``alpha`` make it a
+        ranked batch-mode job (dal_kcenter_ranked_*); the driver stores the
+        default alpha in ``self.alpha`` before begin;
+    begin(kk)       the job for kk steps (dal_kcenter_begin, and
+        dal_kcenter_ranked_attach when weights were given);
     propose(t)      -> the shard's record of step t, an int64 [w] tensor,
         w = DAL_KCENTER_RECORD_BYTES(d) / 8;
     commit(t, records)  records int64 [P, w], the same on every rank;
     finish()        -> (indices int64 [kk'], selected_scores fp64 [kk'], scores
         fp32 of this shard's candidates after the last pick), kk' = the steps
-        that found a candidate; the status words' one host read.
+        that found a candidate; the status words' one host read.  A ranked
+        job's scores are s_t; its r_t are left in ``self.selected_similarity``.
     Nothing between begin and finish reads the device."""
 
     def __init__(self, device=None):
         self.device = device
 
-    def prepare(self, x_local, row_base, labeled_rows, candidates):
+    def prepare(self, x_local, row_base, labeled_rows, candidates, weights=None, alpha=None):
+        import numpy as np
         import torch
 
         from . import _lib
@@ -411,6 +435,13 @@ class HipKCenterSteps:
         from .engine import _as_index, _ptr, _stream
 
         x, dev = _bf16_pool(x_local, self.device)
+        self.weights, self.alpha, self.selected_similarity = None, alpha, None
+        if weights is not None:
+            w = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.asarray(weights, dtype=np.float64))
+            w = w.to(device=dev, dtype=torch.float64).contiguous()
+            if w.dim() != 1 or w.shape[0] != x.shape[0]:
+                raise ValueError("ranked batch selection needs one weight per pool row")
+            self.weights = w
         lab_rows, _ = _bf16_pool(labeled_rows, dev)
         if lab_rows.shape[0] < 1 or lab_rows.shape[1] != x.shape[1]:
             raise ValueError("k-center needs at least one labeled row of the pool's width")
@@ -464,9 +495,19 @@ class HipKCenterSteps:
         self.ws, wsp = workspace(wsb, dev)
         self.job = ctypes.create_string_buffer(_lib.DAL_KCENTER_JOB_BYTES)
         self.record = torch.empty(_lib.kcenter_record_bytes(d) // 8, dtype=torch.int64, device=dev)
-        _lib.call("dal_kcenter_select" if select else "dal_kcenter_begin", self.job, _ptr(self.x), n, d, d,
-                  self.row_base, _ptr(self.flags), _ptr(self.m32), _ptr(self.inv), _ptr(self.centers), m, kk, wsp, wsb,
+        ranked = self.weights is not None
+        _lib.call("dal_kcenter_select" if select and not ranked else "dal_kcenter_begin", self.job, _ptr(self.x), n, d,
+                  d, self.row_base, _ptr(self.flags), _ptr(self.m32), _ptr(self.inv), _ptr(self.centers), m, kk, wsp, wsb,
                   _ptr(self.out_idx), _ptr(self.out_sc), _ptr(self.status), _stream(dev))
+        if ranked:
+            rwsb = int(lib.dal_kcenter_ranked_workspace_bytes(n))
+            self.rws = torch.empty(rwsb + 256, dtype=torch.uint8, device=dev)  # (kept: c lives here until the last step)
+            rwsp = (_ptr(self.rws) + 255) // 256 * 256
+            self.out_sim = torch.empty(kk, dtype=torch.float64, device=dev)
+            _lib.call("dal_kcenter_ranked_attach", self.job, _ptr(self.weights), check_alpha(self.alpha), rwsp, rwsb,
+                      _ptr(self.out_sim), _stream(dev))
+            if select:
+                _lib.call("dal_kcenter_run", self.job, _stream(dev))
 
     def propose(self, t: int):
         from . import _lib
@@ -485,10 +526,16 @@ class HipKCenterSteps:
     def finish(self):
         import torch
 
+        from ._lib import DAL_FLAG_NONFINITE
+
         found = (self.out_idx >= 0).sum().to(torch.int32).reshape(1)
         st, st_lab, kk = torch.cat([self.status, self.lab.status, found]).tolist()  # the one host read
         if (st | st_lab) & 1:
             raise ValueError("zero-norm row: cosine undefined")
+        if st & DAL_FLAG_NONFINITE:
+            raise ValueError("ranked batch selection: a candidate's weight is not a finite number in [0, 1]")
+        if self.weights is not None:
+            self.selected_similarity = self.out_sim[:kk] if self.kk >= 1 else self.out_sc[:0]
         if self.cand is None:
             scores = self.m32
         else:
@@ -528,5 +575,49 @@ def kcenter_select(pool, labeled_idx, k: int, candidates=None, device=None, row_
     return Selection(scores=scores, indices=idx, selected_scores=sc)
 
 
+def ranked_batch_select(pool, labeled_idx, weights, k: int, alpha=None, candidates=None, device=None,
+                        row_base: int = 0, labeled_rows=None):
+    """Ranked batch-mode selection (Cardoso et al. 2017; modAL's batch
+    uncertainty sampling), exact against the canonical fp64 definition
+    (include/dal.h, dal_kcenter_ranked_*): k times, pick the candidate that
+    maximises
+
+        alpha * (1 - max-cosine to the labeled rows and the picks so far)
+        + (1 - alpha) * weights[i]
+
+    (ties -> lower index) and add it to the comparison set.  ``weights``: fp64,
+    one per pool row, finite and in [0, 1] for every candidate (higher = more
+    wanted, e.g. dal.luts.batch_weight_lut gathered by the forest votes); a
+    candidate outside that range raises ValueError.  ``alpha`` in (0, 1] is ONE
+    number for the whole call; None means |C| / (|C| + m) with |C| the
+    candidates inside the pool and m the labeled rows.  It is NOT recomputed
+    per pick (modAL re-derives it as the sets change; here the batch is ranked
+    under one rule).  alpha = 1 is ``kcenter_select``'s farthest-first batch.
+
+    Same pool contract as ``kcenter_select``.  Returns Selection(scores = the
+    fp32 max-cosine of the candidates after the last pick; indices = the
+    min(k, |C|) picks in pick order; selected_scores = their fp64 scores at
+    pick time, non-increasing) with the extra attribute
+    ``selected_similarity``: the picks' canonical max-cosine at pick time."""
+    from .engine import Selection, _as_index
+
+    if int(k) < 1:
+        raise ValueError("k must be >= 1")
+    if alpha is not None:
+        alpha = check_alpha(alpha)
+    x, dev = _bf16_pool(pool, device)
+    if labeled_rows is None:
+        labeled_rows = x[_as_index(labeled_idx, dev)]
+    st = HipKCenterSteps(dev)
+    count = st.prepare(x, row_base, labeled_rows, candidates, weights=weights, alpha=alpha)
+    if alpha is None:
+        st.alpha = default_alpha(st.n if candidates is None else int(count.item()), st.lab.m)
+    st.begin(min(int(k), st.n_cand), select=True)
+    idx, sc, scores = st.finish()
+    sel = Selection(scores=scores, indices=idx, selected_scores=sc)
+    sel.selected_similarity = st.selected_similarity
+    return sel
+
+
 __all__ = ["column_similarities", "cosine_pair_candidates", "cosine_pair_values", "max_cosine", "diversity_select",
-           "LabeledSet", "HipKCenterSteps", "kcenter_select"]
+           "LabeledSet", "HipKCenterSteps", "kcenter_select", "ranked_batch_select", "check_alpha", "default_alpha"]

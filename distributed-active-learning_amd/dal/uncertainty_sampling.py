@@ -41,4 +41,65 @@ def select(pool, unlabeled_idx, forest: Forest, k: int, strategy: str = "least_c
     return uncertainty_step(state, unlabeled_idx, forest, k, strategy)
 
 
-__all__ = ["select", "PoolState", "Selection"]
+def select_batch(pool, unlabeled_idx, labeled_idx, forest: Forest, k: int, strategy: str = "least_confidence",
+                 alpha=None, sim_pool=None, device=None) -> Selection:
+    """Ranked batch-mode uncertainty sampling (Cardoso et al. 2017; modAL's
+    batch uncertainty sampling): the k picks of
+    dal.similarity.ranked_batch_select with the forest's uncertainty as the
+    weight, so a batch is spread over the pool instead of being the first k
+    rows of the top tie group.
+
+    The votes (binary) or per-class counts and scores (multiclass) come from
+    the score entries ``select`` uses.  Weights in [0, 1], higher = more
+    uncertain: binary, dal.luts.batch_weight_lut(strategy, T) gathered by the
+    votes; multiclass, dal.luts.batch_weights_multiclass of the scores.  They
+    are scattered to pool rows on the device; the candidates are the unlabeled
+    rows, the comparison set starts as ``labeled_idx`` (at least one row).
+
+    sim_pool: the bf16 [N, 64|128|256] matrix the cosines are taken on (e.g. an
+    embedding of the pool); None: the pool itself rounded to bf16 -- ValueError
+    at other widths.  alpha: see ranked_batch_select (one number per call;
+    None: U / (U + labeled count)).  The whole pool on one device (no shard).
+
+    Returns Selection(scores = fp32 max-cosine of the unlabeled rows after the
+    last pick, indices, selected_scores = the fp64 ranked scores at pick time)
+    with ``selected_similarity``, ``weights`` (fp64 [U]) and ``votes`` /
+    ``counts`` as ``select`` returns them."""
+    import torch
+
+    from . import luts
+    from .engine import _as_index
+    from .similarity import _bf16_pool, ranked_batch_select
+
+    if strategy not in STRATEGIES:
+        raise ValueError(f"strategy must be one of {STRATEGIES}")
+    state = as_pool_state(pool, device=device)
+    if state.row_base or state.n_total != state.n:
+        raise ValueError("select_batch needs the whole pool, not a row shard")
+    dev = state.device
+    if sim_pool is None:
+        if getattr(state, "_sim_bf16", None) is None:
+            state._sim_bf16, _ = _bf16_pool(state.x, dev)  # (rounded once per pool)
+        simx = state._sim_bf16
+    else:
+        simx, _ = _bf16_pool(sim_pool, dev)
+        if simx.shape[0] != state.n:
+            raise ValueError("sim_pool must have one row per pool row")
+    unl = _as_index(unlabeled_idx, dev)
+    scored = select(state, unl, forest, 1, strategy)  # votes / counts and scores of every unlabeled row
+    if forest.n_classes > 2:
+        w_unl = luts.batch_weights_multiclass(strategy, scored.scores, forest.n_classes)
+    else:
+        table = torch.from_numpy(luts.batch_weight_lut(strategy, forest.n_trees)).to(dev)
+        w_unl = table[scored.votes.to(torch.int64)]
+    weights = torch.zeros(state.n, dtype=torch.float64, device=dev)
+    weights[unl] = w_unl
+    ranked = ranked_batch_select(simx, labeled_idx, weights, k, alpha=alpha, candidates=unl, device=dev)
+    sel = Selection(scores=ranked.scores, indices=ranked.indices, selected_scores=ranked.selected_scores,
+                    votes=scored._votes, counts=scored._counts)
+    sel.selected_similarity = ranked.selected_similarity
+    sel.weights = w_unl
+    return sel
+
+
+__all__ = ["select", "select_batch", "PoolState", "Selection"]

@@ -1327,6 +1327,65 @@ int dal_kcenter_select(void* job, const uint16_t* pool, int64_t n, int64_t d, in
                        void* ws, size_t ws_bytes, int64_t* out_idx, double* out_score, int32_t* dev_status,
                        dal_stream_t stream);
 
+/* ---- ranked batch-mode selection (uncertainty x diversity, greedy) ----------
+ * The ranked batch-mode rule (Cardoso et al. 2017; modAL's batch uncertainty
+ * sampling) as a mode of the k-center job: a per-row weight joins the pick
+ * rule.  New symbols only: dal_abi_version() stays 10 (absent from older
+ * libraries; probe with dal_kcenter_ranked_attach).
+ *
+ * Canonical semantics.  The pool, L (m >= 1), C and cos64 are those of
+ * dal_kcenter_*.  weight: fp64 [n], finite, in [0, 1] (higher = more wanted);
+ * alpha in (0, 1], one number per job.  Every operation is one IEEE fp64
+ * operation in this order, no FMA contraction:
+ *   b      = 1 - alpha
+ *   c_i    = b * w_i
+ *   m_i(0) = max_{l in L} cos64(i, l)
+ *   for t = 1 .. k:
+ *     g_i(t) = alpha * (1 - m_i(t-1)) + c_i
+ *     p_t    = argmax_{i in C, not picked} g_i(t), ties -> the lower global
+ *              index;  s_t = g_{p_t}(t),  r_t = m_{p_t}(t-1)
+ *     m_i(t) = max(m_i(t-1), cos64(i, p_t)) for every row.
+ * out_idx[t-1] = p_t, out_score[t-1] = s_t (fp64, non-increasing in t: m only
+ * grows), out_sim[t-1] = r_t.  When no candidate is left the step writes
+ * index -1 and NaN to both.  alpha = 1 is farthest-first on 1 - m: the picks
+ * and similarities of the plain job.
+ *
+ *   dal_kcenter_ranked_workspace_bytes  the ranked workspace for n rows (c_i,
+ *                        the block maxima, the contenders' similarities); 0
+ *                        for n < 0 or n > INT32_MAX.
+ *   dal_kcenter_ranked_error_bound      B_g = alpha * dal_kcenter_error_bound(d)
+ *                        + 2^-48: the bound of the fp32-state score g~_i =
+ *                        alpha * (1 - (double)m32_i) + c_i against g_i
+ *                        (csrc/kcenter.hip derives it).  Every live candidate
+ *                        with g~_i >= max g~ - 2 B_g is re-decided in
+ *                        canonical fp64, any number of them.
+ *   dal_kcenter_ranked_attach           after dal_kcenter_begin and before the
+ *                        first propose of the job: computes c_i into the
+ *                        ranked workspace (device, 256-B aligned, kept until
+ *                        the last step), refolds the block extremes, and
+ *                        switches the descriptor to the ranked mode.
+ *                        dal_kcenter_propose / dal_kcenter_commit then serve
+ *                        the job with unchanged signatures; the record's
+ *                        reserved word carries r (fp64) and its key is that of
+ *                        -g, so the minimum (key, index) is still the pick.
+ *                        out_sim: fp64 [k], device.
+ *   dal_kcenter_run      all k steps of a one-shard job (propose, then commit
+ *                        on the job's own record) enqueued by one host call,
+ *                        for either mode.
+ *
+ * Before any HIP call: a null job, workspace or out_sim, a null weight with
+ * n > 0, a descriptor that no dal_kcenter_begin filled, or an alpha that is
+ * NaN, <= 0 or > 1 is DAL_ERR_ARG; a workspace that is short or not 256-B
+ * aligned, or a weight / out_sim that is not 8-B aligned, is DAL_ERR_SHAPE.  A
+ * live candidate whose weight is NaN, infinite or outside [0, 1] raises
+ * DAL_FLAG_NONFINITE in the job's *dev_status (the selection is then
+ * meaningless); the weights of other rows decide nothing. */
+size_t dal_kcenter_ranked_workspace_bytes(int64_t n);
+double dal_kcenter_ranked_error_bound(int64_t d, double alpha);
+int dal_kcenter_ranked_attach(void* job, const double* weight, double alpha, void* ws, size_t ws_bytes,
+                              double* out_sim, dal_stream_t stream);
+int dal_kcenter_run(const void* job, dal_stream_t stream);
+
 /* ---- standalone similarity kernels --------------------------------------
  * cosine_similarity.py:42-45: every entry of U.U^T (fp32 MFMA), written to
  * out[n_pad][n_pad] (fp32).  similarity.py:38 (columnSimilarities, i<j) is
