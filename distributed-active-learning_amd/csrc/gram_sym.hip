@@ -1131,7 +1131,8 @@ namespace {
 // kForm != fp16: the closed form of the int8 or fp4 form's terms (h', l'), gram_i8.hpp / gram_fp4.hpp
 template <int kForm>
 int gram_sym_residual(const uint16_t* ops, int64_t nb_active, int64_t row_block0, int64_t n_row_blocks, int64_t d_pad,
-                      int64_t* acc, void* ws, size_t ws_bytes, dal_stream_t stream) {
+                      int64_t* acc, void* ws, size_t ws_bytes, dal_stream_t stream,
+                      const int64_t* pre_sigma_h = nullptr, const int64_t* pre_s_l = nullptr) {
   if (!ops || !acc || !ws) return DAL_ERR_ARG;
   if (nb_active <= 0 || row_block0 < 0 || n_row_blocks <= 0 || ((row_block0 | n_row_blocks | nb_active) & 1))
     return DAL_ERR_SHAPE;
@@ -1154,15 +1155,21 @@ int gram_sym_residual(const uint16_t* ops, int64_t nb_active, int64_t row_block0
   // sigma^H and, behind it (the layout's padding between), the d_pad words of S^L
   static_assert(sizeof(long long) == sizeof(double), "S^L and S~ share their words");
   long long* sl = reinterpret_cast<long long*>(rb);
-  if (hipMemsetAsync(sig_u, 0, L.rb - L.sig_u + static_cast<size_t>(d_pad) * 8, st) != hipSuccess) return DAL_ERR_HIP;
-  // rows of a super block over 4 blocks (more loads in flight: 196 super blocks at config 2);
-  // super blocks per block: what leaves about four blocks per CU, at most 32
-  const int64_t ny = ceil_div(ldh / 8, 256);
-  const int64_t qg0 = na * ny * 4 / (4 * device_cus()), qg = qg0 < 1 ? 1 : qg0 > 32 ? 32 : qg0;
-  hipLaunchKernelGGL(csym_sigma_kernel<kForm>,
-                     dim3(static_cast<unsigned>(ceil_div(na, qg)), static_cast<unsigned>(ny), 4), dim3(256), 0, st,
-                     ops, ldh, ks, static_cast<int>(d_pad), static_cast<int>(na), static_cast<int>(qg), sig_u, sl);
-  DAL_RETURN_IF_LAUNCH_FAILED();
+  if (pre_sigma_h) {  // launch 1 already ran (dal_prep_split_fp4): the caller's sums, read in place
+    sig_u = const_cast<long long*>(reinterpret_cast<const long long*>(pre_sigma_h));
+    sl = const_cast<long long*>(reinterpret_cast<const long long*>(pre_s_l));
+  } else {
+    if (hipMemsetAsync(sig_u, 0, L.rb - L.sig_u + static_cast<size_t>(d_pad) * 8, st) != hipSuccess)
+      return DAL_ERR_HIP;
+    // rows of a super block over 4 blocks (more loads in flight: 196 super blocks at config 2);
+    // super blocks per block: what leaves about four blocks per CU, at most 32
+    const int64_t ny = ceil_div(ldh / 8, 256);
+    const int64_t qg0 = na * ny * 4 / (4 * device_cus()), qg = qg0 < 1 ? 1 : qg0 > 32 ? 32 : qg0;
+    hipLaunchKernelGGL(csym_sigma_kernel<kForm>,
+                       dim3(static_cast<unsigned>(ceil_div(na, qg)), static_cast<unsigned>(ny), 4), dim3(256), 0, st,
+                       ops, ldh, ks, static_cast<int>(d_pad), static_cast<int>(na), static_cast<int>(qg), sig_u, sl);
+    DAL_RETURN_IF_LAUNCH_FAILED();
+  }
   const int64_t n_rows = ns * kSB;
   const dim3 grid(static_cast<unsigned>(ceil_div(n_rows, kResRows)));
   const size_t smem = static_cast<size_t>(2 * d_pad) * 8;
@@ -1273,4 +1280,18 @@ extern "C" int dal_gram_sym_residual_fp4(const uint16_t* ops, int64_t nb_active,
                                          dal_stream_t stream) {
   if (d_pad % 256) return DAL_ERR_SHAPE;
   return gram_sym_residual<kFormFp4>(ops, nb_active, row_block0, n_row_blocks, d_pad, acc, ws, ws_bytes, stream);
+}
+
+// The same with launch 1 done by the caller: sigma_h [nb_active / 2][d_pad] and
+// s_l [d_pad] as dal_prep_split_fp4 wrote them (read only; the scan and launch
+// 3 run, no memset and no sigma pass).
+extern "C" int dal_gram_sym_residual_fp4_pre(const uint16_t* ops, int64_t nb_active, int64_t row_block0,
+                                             int64_t n_row_blocks, int64_t d_pad, int64_t* acc,
+                                             const int64_t* sigma_h, const int64_t* s_l, void* ws, size_t ws_bytes,
+                                             dal_stream_t stream) {
+  if (d_pad % 256) return DAL_ERR_SHAPE;
+  if (!sigma_h || !s_l) return DAL_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(sigma_h) | reinterpret_cast<uintptr_t>(s_l)) & 7) return DAL_ERR_SHAPE;
+  return gram_sym_residual<kFormFp4>(ops, nb_active, row_block0, n_row_blocks, d_pad, acc, ws, ws_bytes, stream,
+                                     sigma_h, s_l);
 }

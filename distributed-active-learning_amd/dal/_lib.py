@@ -92,6 +92,12 @@ SIGNATURES = {
     "dal_split_f16": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "dal_prep_split": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dal_prep_split_fp4_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "dal_prep_split_fp4": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_size_t, c_void_p, c_void_p]),
+    "dal_gram_sym_residual_fp4_pre": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_size_t, c_void_p]),
     "dal_density_error_bound_sym": (c_double, [c_int64]),
     "dal_density_error_bound_sym_d": (c_double, [c_int64, c_int64]),
     "dal_gram_rowsum_sym": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,

@@ -139,7 +139,7 @@ class PoolState:
     """
 
     def __init__(self, pool, excluded=None, device=None, row_base: int = 0, n_total=None,
-                 n_pad=None, gram: str = None, gram_i8=None, gram_fp4=None):
+                 n_pad=None, gram: str = None, gram_i8=None, gram_fp4=None, prep_fused=None):
         torch = _torch()
         self.gram = _gram_kind(gram)
         dev = _require_cuda(device)
@@ -185,6 +185,18 @@ class PoolState:
         self.gram_fp4 = bool(gram_fp4)
         self.gram_i8 = bool(gram_i8) and not self.gram_fp4  # (one form runs)
         self._split_i8 = self._split_fp4 = None
+        # The fp4 form's one-pass preparation (dal_prep_split_fp4: operand,
+        # codes, partials and the residual's sigma sums from one read of the
+        # pool; the same bytes as the separate entries, so the rule is about
+        # speed only).  None: whole pools on one GPU with enough 256-row chunks
+        # to fill the chip; True / False: tests and A/B runs.
+        whole = self.row_base == 0 and self.n == self.n_total and self.n_pad == self.nb_active() * 256
+        if prep_fused and not (self.gram_fp4 and whole):
+            raise ValueError("prep_fused needs the fp4 form on a whole pool (one GPU, the default n_pad)")
+        if prep_fused is None:
+            prep_fused = self.gram_fp4 and whole and -(-self.n // DAL_CANON_CHUNK) >= PREP_FUSED_MIN_CHUNKS
+        self.prep_fused = bool(prep_fused)
+        self._sigma_pre = None  # (sigma^H', S^L') of the fused prep, for the residual that follows
         # after exclude(): the column count the cached Gram density summed and the
         # downdates' share of its error bound (density_error); None / 0: a cold density
         self._density_cols = None
@@ -238,6 +250,7 @@ class PoolState:
         (forces a cold step)."""
         self._u = self._norm64 = self._density = self._colsum = self._colsum_partials = None
         self._split = self._density_exact = self._xb = self._split_i8 = self._split_fp4 = None
+        self._sigma_pre = None
         self._graphs = {}
         self._density_cols, self._downdate_err = None, 0.0
 
@@ -296,6 +309,7 @@ class PoolState:
             self.flags[torch.from_numpy(local).to(self.device)] = DAL_ROW_EXCLUDED
         self._u = self._norm64 = self._density = self._colsum = self._colsum_partials = None
         self._split = self._density_exact = self._split_i8 = self._split_fp4 = None
+        self._sigma_pre = None
         self._graphs = {}
         self._density_cols, self._downdate_err = None, 0.0
 
@@ -362,6 +376,7 @@ class PoolState:
         if self._density_cols is None:
             self._density_cols = max(self.n_total - self.n_excluded_global(), 1)
         ops = self.gram_operand()
+        self._sigma_pre = None  # (sums of the operand before these rows left it)
         if self.n:
             if int(self._density.shape[0]) < self.n_pad or not self._density.is_contiguous():
                 raise ValueError("the cached density must hold one contiguous word per padded row")
@@ -422,7 +437,8 @@ class PoolState:
         with_partials: the fused prep also writes the canonical column-sum
         partials (else they are left to colsum_partials()).  acc_zero: an
         int64 [n_pad] density accumulator to zero (by the prep kernel when it
-        runs here, else by a fill)."""
+        runs here, else by a fill).  With ``prep_fused`` the same pass also
+        writes the fp4 codes and the residual's sigma sums (dal_prep_split_fp4)."""
         if self.gram == "f32":
             u, _ = self.normalized()
             if acc_zero is not None:
@@ -445,10 +461,26 @@ class PoolState:
                 parts = None
                 if self._colsum_partials is None and with_partials:
                     parts = torch.empty((chunks, self.d), dtype=torch.float64, device=self.device)
-                call("dal_prep_split", _ptr(self.x), self.n, self.d, self.d, _ptr(self.flags),
-                     self.n_pad, self.d_pad, _ptr(self._split), _ptr(norm64),
-                     0 if parts is None else _ptr(parts), 0 if acc_zero is None else _ptr(acc_zero),
-                     _ptr(self.status), _stream(self.device))
+                if self.prep_fused and self._split_fp4 is None:
+                    # one pass: the codes and the residual's sigma sums as well
+                    self._split_fp4 = torch.empty((self.n_pad, self.d_pad // 2), dtype=torch.uint8,
+                                                  device=self.device)
+                    sig = torch.empty((self.n_pad // 512, self.d_pad), dtype=torch.int64, device=self.device)
+                    s_l = torch.empty(self.d_pad, dtype=torch.int64, device=self.device)
+                    wsb = int(_lib.load().dal_prep_split_fp4_workspace_bytes(self.n_pad, self.d_pad))
+                    ws, wsp = workspace(wsb, self.device)
+                    call("dal_prep_split_fp4", _ptr(self.x), self.n, self.d, self.d, _ptr(self.flags),
+                         self.n_pad, self.d_pad, _ptr(self._split), _ptr(norm64),
+                         0 if parts is None else _ptr(parts), 0 if acc_zero is None else _ptr(acc_zero),
+                         _ptr(self._split_fp4), _ptr(sig), _ptr(s_l), wsp, wsb, _ptr(self.status),
+                         _stream(self.device))
+                    del ws
+                    self._sigma_pre = (sig, s_l)
+                else:
+                    call("dal_prep_split", _ptr(self.x), self.n, self.d, self.d, _ptr(self.flags),
+                         self.n_pad, self.d_pad, _ptr(self._split), _ptr(norm64),
+                         0 if parts is None else _ptr(parts), 0 if acc_zero is None else _ptr(acc_zero),
+                         _ptr(self.status), _stream(self.device))
                 zeroed = True
                 if self._norm64 is None:
                     self._norm64 = norm64
@@ -608,9 +640,14 @@ class PoolState:
         if self.gram_events is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
-        name = ("dal_gram_sym_residual_fp4" if self.gram_fp4 else
-                "dal_gram_sym_residual_i8" if self.gram_i8 else "dal_gram_sym_residual")
-        call(name, _ptr(ops), nb, rb0, nrb, self.d_pad, _ptr(acc), wsp, wsb, _stream(self.device))
+        pre, self._sigma_pre = self._sigma_pre, None  # the fused prep's sums serve one residual
+        if pre is not None and self.gram_fp4 and ops is self._split:
+            call("dal_gram_sym_residual_fp4_pre", _ptr(ops), nb, rb0, nrb, self.d_pad, _ptr(acc), _ptr(pre[0]),
+                 _ptr(pre[1]), wsp, wsb, _stream(self.device))
+        else:
+            name = ("dal_gram_sym_residual_fp4" if self.gram_fp4 else
+                    "dal_gram_sym_residual_i8" if self.gram_i8 else "dal_gram_sym_residual")
+            call(name, _ptr(ops), nb, rb0, nrb, self.d_pad, _ptr(acc), wsp, wsb, _stream(self.device))
         if ev is not None:
             ev[1].record()
             self.residual_events.append(ev)
@@ -688,6 +725,10 @@ class PoolState:
 
 GRAM_KINDS = ("sym", "f32")
 GRAM_I8_MIN_BYTES = 32 << 20  # split operands above the contiguous schedule's limit take the int8 form
+# 256-row chunks from which the fp4 form's one-pass preparation runs by default
+# (PoolState(prep_fused=None)): its blocks own whole 512-row super blocks, so a
+# small pool leaves most of the chip idle
+PREP_FUSED_MIN_CHUNKS = 512
 
 
 def _gram_kind(gram) -> str:

@@ -276,6 +276,26 @@ int dal_gram_rowsum_sym_fp4_skip(const uint8_t* rows_fp4, int64_t row_block0, in
                                  int grid_blocks, dal_stream_t stream);
 int dal_gram_sym_residual_fp4(const uint16_t* ops, int64_t nb_active, int64_t row_block0, int64_t n_row_blocks,
                               int64_t d_pad, int64_t* acc, void* ws, size_t ws_bytes, dal_stream_t stream);
+/* The fp4 form's preparation in one pass over the pool (new symbols, the ABI
+ * number stays): what dal_prep_split (norm64, the status flag, the zeroed
+ * acc_zero, the split operand, the canonical partials), dal_quant_fp4 over
+ * all n_pad rows (out_fp4) and launch 1 of dal_gram_sym_residual_fp4 write, the
+ * same bytes: sigma_h [n_pad / 512][d_pad] = the sum of h' over each 512-row
+ * super block and s_l [d_pad] = the sum of l' over the pool, int64 in units of
+ * 2^-24.  One fp64 quotient and one a4 per element.  x_stride: dal_prep_split's
+ * ldx (floats between rows, >= d).  d_pad % 256 == 0, n >= 1, n_pad % 512 == 0; partials and acc_zero nullable; ws: scratch of
+ * dal_prep_split_fp4_workspace_bytes (8-byte aligned), free once the call's
+ * work has run.  dal_gram_sym_residual_fp4_pre is dal_gram_sym_residual_fp4
+ * with those sums given (nb_active * 256 == n_pad of the prep call; read
+ * only): the scan and the row launch alone. */
+size_t dal_prep_split_fp4_workspace_bytes(int64_t n_pad, int64_t d_pad);
+int dal_prep_split_fp4(const float* x, int64_t n, int64_t d, int64_t x_stride, const uint8_t* row_flags, int64_t n_pad,
+                       int64_t d_pad, uint16_t* out, double* norm64, double* partials, int64_t* acc_zero,
+                       uint8_t* out_fp4, int64_t* sigma_h, int64_t* s_l, void* ws, size_t ws_bytes,
+                       int32_t* dev_status, dal_stream_t stream);
+int dal_gram_sym_residual_fp4_pre(const uint16_t* ops, int64_t nb_active, int64_t row_block0, int64_t n_row_blocks,
+                                  int64_t d_pad, int64_t* acc, const int64_t* sigma_h, const int64_t* s_l, void* ws,
+                                  size_t ws_bytes, dal_stream_t stream);
 double dal_density_error_bound_sym(int64_t n_cols);
 /* The same bound for the kernel that runs features padded to d_pad (ABI v8):
  * the row-side chain length charged depends on the slice width KS (1,024
