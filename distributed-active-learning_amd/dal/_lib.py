@@ -61,6 +61,13 @@ DAL_RF_SPAN_I32 = 0
 DAL_RF_SPAN_I64 = 1
 DAL_ROW_PICKED = 4
 DAL_KCENTER_JOB_BYTES = 512
+DAL_SOFT_MAX_DEPTH = 16
+DAL_SOFT_MAX_CLASSES = 32
+DAL_SOFT_MAX_TREES = 255
+DAL_SOFT_ONE = 1 << 31
+DAL_SOFT_LEAST_CONFIDENCE = 0
+DAL_SOFT_MARGIN = 1
+DAL_SOFT_ENTROPY = 2
 
 
 def kcenter_record_bytes(d: int) -> int:
@@ -147,6 +154,10 @@ SIGNATURES = {
                                                        c_void_p, c_int, c_double, c_void_p, c_double, c_void_p,
                                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                        c_void_p]),
+    "dal_forest_soft_max_depth": (c_int, []),
+    "dal_forest_score_soft": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                      c_int32, c_int32, c_int32, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
     "dal_density_separable": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]),
     "dal_topk_workspace_bytes": (c_size_t, [c_int64, c_int64]),

@@ -71,19 +71,24 @@ class Selection:
                     (a multiclass step; None otherwise)
     lut             fp64 [T+1]: a LAL step (lal_step) also sets this attribute,
                     the regressor's prediction per vote count
+    sums            int64 [U, C]: the exact class sums S_c of every unlabeled
+                    row (a soft-vote step, soft_step; None otherwise);
+                    ``proba()`` gives them over M = T 2^31 as fp64
 
-    ``scores`` / ``votes`` / ``counts`` may be given as (per-row tensor, positions): they are
+    ``scores`` / ``votes`` / ``counts`` / ``sums`` may be given as (per-row tensor, positions): they are
     gathered into unlabeled order on first access (the per-row arrays are
     complete in HBM when the step returns; the gather is only a re-layout, so
     a caller that reads just the selection pays no extra launches).
     """
 
-    def __init__(self, scores, indices, selected_scores, votes=None, counts=None):
+    def __init__(self, scores, indices, selected_scores, votes=None, counts=None, sums=None, denominator=None):
         self._scores = scores
         self.indices = indices
         self.selected_scores = selected_scores
         self._votes = votes
         self._counts = counts
+        self._sums = sums
+        self.denominator = denominator  # M = T 2^31 of a soft-vote step
 
     @staticmethod
     def _gathered(v):
@@ -107,12 +112,25 @@ class Selection:
         self._counts = self._gathered(self._counts)
         return self._counts
 
+    @property
+    def sums(self):
+        self._sums = self._gathered(self._sums)
+        return self._sums
+
+    def proba(self):
+        """fp64 [U, C]: the averaged class probabilities of a soft-vote step,
+        (double)S_c / (double)M, one IEEE division per entry."""
+        if self._sums is None:
+            raise ValueError("proba() belongs to a soft-vote step (a ProbabilityForest)")
+        return soft_proba(self.sums, self.denominator)
+
     def _detach(self):
         """Materialise the per-row arrays now (their source buffers are about
         to be reused: a warm-step graph replay)."""
         self._scores = self._gathered(self._scores)
         self._votes = self._gathered(self._votes)
         self._counts = self._gathered(self._counts)
+        self._sums = self._gathered(self._sums)
 
     def __iter__(self):
         """Unpacks as the reference-shaped triple (scores, indices, selected_scores)."""
@@ -869,6 +887,38 @@ def forest_score_multiclass(state: PoolState, forest: Forest, lut_dev, flags, or
     return counts, pred, scores, keys
 
 
+def soft_proba(sums, denominator: int):
+    """fp64 (double)S_c / (double)M of int64 class sums: one IEEE division per
+    entry (a tensor divisor: dividing a device tensor by a Python float
+    multiplies by its reciprocal)."""
+    torch = _torch()
+    p = sums.to(torch.float64)
+    return p / p.new_full((1,), float(denominator))
+
+
+SOFT_KINDS = {"least_confidence": _lib.DAL_SOFT_LEAST_CONFIDENCE, "margin": _lib.DAL_SOFT_MARGIN,
+              "entropy": _lib.DAL_SOFT_ENTROPY}
+
+
+def forest_score_soft(state: PoolState, forest, flags, order: int, kind: int):
+    """Launch dal_forest_score_soft over the shard: the exact class sums of a
+    ProbabilityForest's leaf distributions and the soft-vote score; returns
+    (sums int64 [n, C], pred uint8 [n], scores, keys).  flags None: every row
+    is a candidate."""
+    torch = _torch()
+    forest.check_features(state.d)
+    inner, leaf_id, leaf_q = forest.device(state.device)  # (checks the limits and the leaf ids before the upload)
+    n, C = state.n, int(forest.n_classes)
+    sums = torch.empty((n, C), dtype=torch.int64, device=state.device)
+    pred = torch.empty(n, dtype=torch.uint8, device=state.device)
+    scores = torch.empty(n, dtype=torch.float64, device=state.device)
+    keys = torch.empty(n, dtype=torch.int64, device=state.device)
+    call("dal_forest_score_soft", _ptr(state.x), n, state.d, state.d, _ptr(inner), _ptr(leaf_id), _ptr(leaf_q),
+         forest.n_leaves, forest.n_trees, int(forest.depth), C, int(kind), 0 if flags is None else _ptr(flags),
+         int(order), _ptr(sums), _ptr(pred), _ptr(scores), _ptr(keys), _stream(state.device))
+    return sums, pred, scores, keys
+
+
 def forest_score_multiclass_dw(state: PoolState, forest: Forest, flags, density, density_kind: int,
                                density_err: float = 0.0, beta: float = 1.0, want_hi: bool = True, xb=None):
     """Launch dal_forest_score_multiclass_dw (dal_forest_score_multiclass_dw_
@@ -1180,6 +1230,27 @@ def multiclass_step(state: PoolState, unlabeled_idx, forest: Forest, k: int,
     idx, _ = topk_keys(keys, kk, state.row_base)
     sel_scores = scores[idx - state.row_base]
     return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, counts=(counts, loc))
+
+
+def soft_step(state: PoolState, unlabeled_idx, forest, k: int, strategy: str = "least_confidence") -> Selection:
+    """One uncertainty iteration over a ProbabilityForest: the averaged leaf
+    class distributions and the soft-vote score (dal_forest_score_soft), then
+    the top-k of the keys.  Scores, indices and selected scores as
+    multiclass_step; the Selection carries ``sums`` ([U, C] int64) and
+    ``proba()``; ``votes`` and ``counts`` are None."""
+    if strategy not in SOFT_KINDS:
+        raise ValueError(f"strategy must be one of {tuple(SOFT_KINDS)}")
+    flags, unl, n_cand = state.row_flags(unlabeled_idx)
+    if n_cand == 0:
+        raise ValueError("unlabeled set is empty (the reference loop breaks here)")
+    kk = min(int(k), n_cand)
+    loc = state.local_positions(unl)
+    order = DAL_ASCENDING if MULTICLASS_ASCENDING[strategy] else DAL_DESCENDING
+    sums, _, scores, keys = forest_score_soft(state, forest, flags, order, SOFT_KINDS[strategy])
+    idx, _ = topk_keys(keys, kk, state.row_base)
+    sel_scores = scores[idx - state.row_base]
+    return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, sums=(sums, loc),
+                     denominator=forest.denominator)
 
 
 def multiclass_density_step(state: PoolState, unlabeled_idx, forest: Forest, k: int, beta: float = 1.0,

@@ -28,7 +28,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import DAL_MAX_TREE_DEPTH, DAL_MC_MAX_CLASSES, DAL_REG_MAX_DEPTH
+from ._lib import (DAL_MAX_TREE_DEPTH, DAL_MC_MAX_CLASSES, DAL_REG_MAX_DEPTH, DAL_SOFT_MAX_CLASSES,
+                   DAL_SOFT_MAX_DEPTH, DAL_SOFT_MAX_TREES, DAL_SOFT_ONE)
 
 _POS_INF_BITS = np.array([np.inf], dtype=np.float32).view(np.int32)[0]
 
@@ -531,3 +532,233 @@ class RegressionForest:
         leaf = sign * np.power(10.0, e.astype(np.float64))
         return cls(inner_feature=inner_feature, inner_threshold=inner_threshold.astype(np.float64),
                    leaf=leaf, depth=depth)
+
+
+def quantize_distribution(distribution) -> np.ndarray:
+    """Leaf class distributions [L, C] (weights or fractions, fp64) as the
+    fixed-point leaf words of a ProbabilityForest: q = rint(p 2^31) as uint32,
+    p = value / total in fp64, one division per class, total the fp64 sum of
+    the row taken in class order; rounding to even, q <= 2^31.  A negative,
+    NaN, infinite or all-zero row raises ValueError."""
+    v = np.asarray(distribution, dtype=np.float64)
+    if v.ndim != 2 or v.shape[0] < 1:
+        raise ValueError("distribution must be a non-empty [leaves, classes] array")
+    if not np.isfinite(v).all():
+        raise ValueError("a leaf distribution holds a NaN or an infinite weight")
+    if (v < 0).any():
+        raise ValueError("a leaf distribution holds a negative weight")
+    total = np.zeros(v.shape[0], dtype=np.float64)
+    for c in range(v.shape[1]):  # class order: the restatement's sum
+        total = total + v[:, c]
+    if not (total > 0).all() or not np.isfinite(total).all():
+        raise ValueError("a leaf distribution is all zero (or its sum overflows)")
+    q = np.rint((v / total[:, None]) * float(DAL_SOFT_ONE))
+    return q.astype(np.uint32)
+
+
+@dataclass
+class ProbabilityForest:
+    """A forest of soft-voting trees: a leaf contributes its class distribution
+    (scikit-learn's ``predict_proba``), not one class id.
+
+    Layout (dal_forest_score_soft):
+      inner    int32  [T, 2^D - 1, 2]  Forest's heap, (0, +inf) below a shallow leaf
+      leaf_id  int32  [T, 2^D]         row of ``leaf_q`` of every heap leaf (a
+                                       shallow leaf's id repeated over its subtree)
+      leaf_q   uint32 [L, C]           rint(p 2^31) per class (quantize_distribution)
+    1 <= T <= 255, 2 <= C <= 32, D <= DAL_SOFT_MAX_DEPTH.  A row's class sums
+    S_c = sum_t leaf_q[leaf_id[t, leaf_t(x)], c] are exact integers and the
+    averaged probability is S_c / (T 2^31)."""
+
+    inner: np.ndarray
+    leaf_id: np.ndarray
+    leaf_q: np.ndarray
+    depth: int
+    n_classes: int
+    classes_: np.ndarray = None
+    _dev: dict = field(default_factory=dict, repr=False)
+
+    @property
+    def n_trees(self) -> int:
+        return int(self.inner.shape[0])
+
+    @property
+    def n_leaves(self) -> int:
+        return int(self.leaf_q.shape[0])
+
+    @property
+    def denominator(self) -> int:
+        """M = T 2^31: a row's class sums divided by it are its probabilities."""
+        return self.n_trees * DAL_SOFT_ONE
+
+    def check(self):
+        """Raise unless the forest is within the kernel's limits and its tables
+        are consistent (before any upload)."""
+        _check_soft_limits(self.n_trees, int(self.n_classes), int(self.depth))
+        T, D, C = self.n_trees, int(self.depth), int(self.n_classes)
+        if self.inner.shape != (T, (1 << D) - 1, 2) or self.leaf_id.shape != (T, 1 << D):
+            raise ValueError("inner must be [T, 2^D - 1, 2] and leaf_id [T, 2^D]")
+        if self.leaf_q.ndim != 2 or self.leaf_q.shape[1] != C or self.leaf_q.shape[0] < 1:
+            raise ValueError(f"leaf_q must be [L, {C}] with at least one leaf")
+        if int(self.leaf_id.min()) < 0 or int(self.leaf_id.max()) >= self.n_leaves:
+            raise ValueError(f"a leaf id lies outside the leaf table's {self.n_leaves} rows")
+        if int(self.leaf_q.max()) > DAL_SOFT_ONE:
+            raise ValueError("a leaf word exceeds 2^31")
+
+    def check_features(self, d: int):
+        """Raise unless every inner node tests a feature in [0, d)."""
+        if "range" not in self._dev:
+            f = self.inner[..., 0]
+            self._dev["range"] = (int(f.min()), int(f.max())) if f.size else (0, 0)
+        lo, hi = self._dev["range"]
+        if lo < 0 or hi >= d:
+            raise ValueError(f"forest tests feature {lo if lo < 0 else hi}, outside the pool's {d} features")
+
+    def device(self, device):
+        """(inner, leaf_id, leaf_q) as device tensors, uploaded once per device
+        (leaf_q travels as its int32 bit pattern)."""
+        import torch
+
+        key = str(device)
+        if key not in self._dev:
+            self.check()
+            self._dev[key] = (
+                torch.from_numpy(np.ascontiguousarray(self.inner, dtype=np.int32)).to(device),
+                torch.from_numpy(np.ascontiguousarray(self.leaf_id, dtype=np.int32)).to(device),
+                torch.from_numpy(np.ascontiguousarray(self.leaf_q, dtype=np.uint32).view(np.int32)).to(device),
+            )
+        return self._dev[key]
+
+    def hard(self) -> Forest:
+        """The hard-voting Forest of arg-max leaves (the lowest class among
+        equal largest words), over the same heap."""
+        if "hard" not in self._dev:
+            cls_ = np.argmax(self.leaf_q, axis=1).astype(np.uint8)
+            self._dev["hard"] = Forest(inner=self.inner, leaf=cls_[self.leaf_id], depth=int(self.depth),
+                                       n_classes=int(self.n_classes), classes_=self.classes_)
+        return self._dev["hard"]
+
+    # ------------------------------------------------------------ builders
+    @classmethod
+    def from_nodes(cls, feature, threshold, left, right, distribution, roots, n_classes: int,
+                   classes_=None) -> "ProbabilityForest":
+        """Flattened node arrays (global node ids), as Forest.from_nodes:
+        feature < 0 marks a leaf whose class distribution is
+        distribution[node] (C weights or fractions; rows of inner nodes are
+        ignored).  Leaves are numbered tree by tree in the order a depth-first
+        walk (left first) meets them."""
+        n_classes = int(n_classes)
+        feature = np.asarray(feature, dtype=np.int64)
+        threshold = np.asarray(threshold, dtype=np.float64)
+        left = np.asarray(left, dtype=np.int64)
+        right = np.asarray(right, dtype=np.int64)
+        roots = np.asarray(roots, dtype=np.int64)
+        distribution = np.asarray(distribution, dtype=np.float64)
+        if roots.size == 0:
+            raise ValueError("forest has no trees")
+        _check_soft_limits(int(roots.size), n_classes, 1)
+        if distribution.ndim != 2 or distribution.shape != (feature.shape[0], n_classes):
+            raise ValueError(f"distribution must be [nodes, {n_classes}]")
+        placed = []  # (tree, node, heap index, level)
+        D = 1
+        for t, root in enumerate(roots):
+            stack = [(int(root), 0, 0)]
+            while stack:
+                nd, h, lv = stack.pop()
+                placed.append((t, nd, h, lv))
+                if feature[nd] < 0:
+                    D = max(D, lv)
+                    continue
+                if lv >= DAL_SOFT_MAX_DEPTH:
+                    raise ValueError(f"tree depth exceeds DAL_SOFT_MAX_DEPTH={DAL_SOFT_MAX_DEPTH}")
+                stack.append((int(right[nd]), 2 * h + 2, lv + 1))  # (popped after the left child)
+                stack.append((int(left[nd]), 2 * h + 1, lv + 1))
+        leaf_nodes = np.array([nd for _, nd, _, _ in placed if feature[nd] < 0], dtype=np.int64)
+        leaf_q = quantize_distribution(distribution[leaf_nodes])
+        n_inner, n_leaf = (1 << D) - 1, 1 << D
+        T = roots.size
+        inner = np.zeros((T, n_inner, 2), dtype=np.int32)
+        inner[:, :, 1] = _POS_INF_BITS
+        leaf_id = np.zeros((T, n_leaf), dtype=np.int32)
+        thr32 = threshold_to_f32(threshold).view(np.int32)
+        next_id = 0
+        for t, nd, h, lv in placed:
+            if feature[nd] < 0:
+                span = 1 << (D - lv)  # the leaves below heap position h
+                first_leaf = (h + 1) * span - 1 - n_inner
+                leaf_id[t, first_leaf:first_leaf + span] = next_id
+                next_id += 1
+            else:
+                inner[t, h, 0] = feature[nd]
+                inner[t, h, 1] = thr32[nd]
+        return cls(inner=inner, leaf_id=leaf_id, leaf_q=leaf_q, depth=D, n_classes=n_classes,
+                   classes_=None if classes_ is None else np.asarray(classes_))
+
+    @classmethod
+    def from_sklearn(cls, rf) -> "ProbabilityForest":
+        """From a fitted ``sklearn.ensemble.RandomForestClassifier``: every
+        tree's ``tree_.value[:, 0, :]``, normalised per leaf; class id c is
+        ``rf.classes_[c]`` (kept in ``classes_``).  A forest fitted on one
+        label gets a second, empty class."""
+        classes = np.asarray(rf.classes_)
+        C = max(2, int(classes.size))
+        feat, thr, lft, rgt, val, roots = [], [], [], [], [], []
+        base = 0
+        for est in rf.estimators_:
+            tr = est.tree_
+            roots.append(base)
+            cl = np.asarray(tr.children_left)
+            cr = np.asarray(tr.children_right)
+            is_leaf = cl < 0
+            v = np.zeros((tr.node_count, C), dtype=np.float64)
+            v[:, :classes.size] = tr.value[:, 0, :]
+            feat.append(np.where(is_leaf, -1, tr.feature))
+            thr.append(np.where(is_leaf, 0.0, tr.threshold))
+            lft.append(np.where(is_leaf, -1, cl + base))
+            rgt.append(np.where(is_leaf, -1, cr + base))
+            val.append(v)
+            base += tr.node_count
+        return cls.from_nodes(np.concatenate(feat), np.concatenate(thr), np.concatenate(lft), np.concatenate(rgt),
+                              np.concatenate(val), np.array(roots), n_classes=C, classes_=classes)
+
+    @classmethod
+    def synthetic(cls, n_trees: int, depth: int, n_features: int, n_classes: int, seed: int = 1,
+                  dist: str = "uniform", one_hot=None) -> "ProbabilityForest":
+        """T complete depth-``depth`` trees for tests and benchmarks, tree by
+        tree: the inner nodes as Forest.synthetic draws them (feature ~
+        U{0..n_features-1}, threshold ~ U(0,1), or N(0,1) with dist="normal",
+        as fp32), then the tree's leaf distributions ~ Dirichlet(1, ..., 1) (C
+        unit exponentials, normalised by the quantisation); one table row per
+        leaf, leaf (t, l) at row t 2^depth + l.  one_hot: (tree, leaf, class) triples whose
+        leaves get the word 2^31 for that class and zero elsewhere (applied
+        after every draw, so the other draws do not move)."""
+        n_classes = int(n_classes)
+        _check_soft_limits(int(n_trees), n_classes, int(depth))
+        rng = np.random.default_rng(seed)
+        n_inner, n_leaf = (1 << depth) - 1, 1 << depth
+        inner = np.zeros((n_trees, n_inner, 2), dtype=np.int32)
+        value = np.zeros((n_trees, n_leaf, n_classes), dtype=np.float64)
+        for t in range(n_trees):
+            f = rng.integers(0, n_features, size=n_inner)
+            if dist == "uniform":
+                th = rng.random(n_inner).astype(np.float32)
+            else:
+                th = rng.standard_normal(n_inner).astype(np.float32)
+            inner[t, :, 0] = f
+            inner[t, :, 1] = th.view(np.int32)
+            value[t] = rng.standard_exponential((n_leaf, n_classes))
+        for t, l, c in (one_hot or ()):
+            value[t, l] = 0.0
+            value[t, l, c] = 1.0
+        leaf_id = np.arange(n_trees * n_leaf, dtype=np.int32).reshape(n_trees, n_leaf)
+        return cls(inner=inner, leaf_id=leaf_id, leaf_q=quantize_distribution(value.reshape(-1, n_classes)),
+                   depth=int(depth), n_classes=n_classes)
+
+
+def _check_soft_limits(n_trees: int, n_classes: int, depth: int):
+    if not 1 <= n_trees <= DAL_SOFT_MAX_TREES:
+        raise ValueError(f"a soft-vote forest holds 1 to {DAL_SOFT_MAX_TREES} trees, not {n_trees}")
+    if not 2 <= n_classes <= DAL_SOFT_MAX_CLASSES:
+        raise ValueError(f"n_classes must lie in [2, {DAL_SOFT_MAX_CLASSES}], not {n_classes}")
+    if not 1 <= depth <= DAL_SOFT_MAX_DEPTH:
+        raise ValueError(f"tree depth must lie in [1, DAL_SOFT_MAX_DEPTH={DAL_SOFT_MAX_DEPTH}], not {depth}")

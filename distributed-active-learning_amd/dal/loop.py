@@ -97,7 +97,7 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
              seed: int = 0, select_fn=None, device=None, beta: float = 1.0,
              verbose: bool = False, trainer="gpu", num_classes=None, lal_model=None,
              initial_labeled=None, measures=None, hist_fn=None, density_over: str = "initial",
-             alpha=None, sim_pool=None) -> LoopResult:
+             alpha=None, sim_pool=None, soft_votes: bool = False) -> LoopResult:
     """Run the AL loop.  strategy: "uncertainty" (uncertainty_sampling.py),
     "density" (density_weighting.py, E = L0 = range(window_size)),
     "information_density" (class entropy x density, E = L0;
@@ -154,7 +154,22 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     value is only validated: the callback sees ``unlabeled`` and can derive E.
     Any other value, or "unlabeled" with a strategy that has no density,
     raises ValueError.
+
+    soft_votes ("uncertainty" and "ranked_batch" only, with trainer="sklearn"
+    or a callable that returns a scikit-learn forest): score the averaged leaf
+    class distributions (scikit-learn's ``predict_proba``; modAL's uncertainty
+    sampling) instead of the hard votes -- every iteration's forest goes
+    through dal.forest.ProbabilityForest.from_sklearn, for any label count.
+    trainer="gpu" (its forests keep no leaf distributions) or any other
+    strategy raises ValueError.  False, the default, makes the calls it made.
     """
+    if soft_votes:
+        if strategy not in ("uncertainty", "ranked_batch"):
+            raise ValueError(f"soft_votes=True belongs to strategy 'uncertainty' or 'ranked_batch': {strategy!r} "
+                             "scores hard votes")
+        if trainer == "gpu":
+            raise ValueError("soft_votes=True needs trainer='sklearn' or a callable returning a scikit-learn "
+                             "forest: trainer='gpu' keeps no leaf distributions")
     if density_over not in ("initial", "unlabeled"):
         raise ValueError(f"density_over must be 'initial' or 'unlabeled', not {density_over!r}")
     if density_over == "unlabeled" and strategy not in ("density", "information_density"):
@@ -260,9 +275,17 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
         elif select_fn is not None:
             chosen = np.asarray(select_fn(strategy, X, unlabeled, rf, k))
         else:
-            forest = rf.forest if isinstance(rf, GpuForestModel) else \
-                Forest.from_sklearn(rf, multiclass=True) if multiclass or strategy == "information_density" \
-                else Forest.from_sklearn(rf)
+            if soft_votes:
+                from .forest import ProbabilityForest
+
+                if isinstance(rf, (GpuForestModel, Forest)):
+                    raise ValueError("soft_votes=True needs a scikit-learn forest from the trainer: "
+                                     f"{type(rf).__name__} keeps no leaf distributions")
+                forest = ProbabilityForest.from_sklearn(rf)
+            else:
+                forest = rf.forest if isinstance(rf, GpuForestModel) else \
+                    Forest.from_sklearn(rf, multiclass=True) if multiclass or strategy == "information_density" \
+                    else Forest.from_sklearn(rf)
             if strategy == "uncertainty":
                 from .uncertainty_sampling import select
                 sel = select(state, unlabeled, forest, k)

@@ -46,6 +46,19 @@ RCCL_RESERVED_CUS = 8
 DENSITY_MODES = ("dw", "dw_multiclass")
 
 
+def _soft_forest(forest, mode: str) -> bool:
+    """True for a dal.forest.ProbabilityForest (soft votes), which mode "us"
+    alone scores; any other mode raises ValueError, before any work."""
+    from .forest import ProbabilityForest
+
+    soft = isinstance(forest, ProbabilityForest)
+    if soft and mode != "us":
+        raise ValueError(f"a ProbabilityForest (soft votes) is scored by mode='us' only: mode={mode!r} has no "
+                         "soft-vote form (the density-weighted and LAL scores take hard votes; "
+                         "forest.hard() gives the hard-voting Forest)")
+    return soft
+
+
 def shard_rows(n_total: int, world: int) -> int:
     """Rows per shard: ceil(N / P) rounded up to the row granule (512)."""
     per = -(-n_total // world)
@@ -313,7 +326,8 @@ class ShardedSelector:
         """This rank's exact local top-k.  mode: "us" (uncertainty), "dw"
         (binary density weighting) or "dw_multiclass" (class entropy x
         density, any forest of two or more classes; the C-class score kernel
-        and dal_dw_select).  ``warm``: the density was cached
+        and dal_dw_select).  A dal.forest.ProbabilityForest (soft votes) is
+        scored by mode "us" alone; every other mode raises ValueError.  ``warm``: the density was cached
         before this step (the score kernel then reads the shard's blocked
         copy, as the single-GPU warm step does; a cold step keeps the
         row-major kernel and builds no copy).  None: cached now."""
@@ -329,6 +343,7 @@ class ShardedSelector:
                              torch.full((k,), -1, dtype=torch.int64, device=st.device),
                              torch.full((k,), float("nan"), dtype=torch.float64, device=st.device))
 
+        soft = _soft_forest(forest, mode)
         if mode == "dw" and forest.n_classes > 2:
             raise ValueError(f"density weighting is binary only: the forest has {forest.n_classes} classes")
         if st.n == 0:
@@ -384,6 +399,14 @@ class ShardedSelector:
                     want_hi=True, xb=xb)
                 i, s, kk_keys = dw_select_local(st, flags, rix, klo, khi, ent, kk, beta, colsum,
                                                 cap_scale=self.cap_scale, sync=False)
+        elif soft:  # soft votes: the averaged leaf distributions, the same merge
+            from .engine import SOFT_KINDS, forest_score_soft
+            from .luts import MULTICLASS_ASCENDING
+
+            order = DAL_ASCENDING if MULTICLASS_ASCENDING[strategy] else DAL_DESCENDING
+            _, _, sc, kys = forest_score_soft(st, forest, flags, order, SOFT_KINDS[strategy])
+            i, kk_keys = topk_keys(kys, kk, st.row_base)
+            s = sc[i - st.row_base]
         elif forest.n_classes > 2:  # multiclass uncertainty: the C-class kernel, the same merge
             from .engine import MULTICLASS_KINDS, device_multiclass_lut, forest_score_multiclass
             from .luts import MULTICLASS_ASCENDING
@@ -517,6 +540,7 @@ def select(sel: ShardedSelector, comm, unlabeled_idx, forest, k: int, mode: str 
            density_mode: str = "gram"):
     """One selection step across all ranks; returns (indices [k], scores [k]),
     identical on every rank."""
+    _soft_forest(forest, mode)
     unl = sel.index_tensor(unlabeled_idx)
     u_full = parts_full = None
     warm = sel._density is not None  # (a cold step's score kernel keeps the row-major pool)
@@ -638,6 +662,7 @@ def emulate(selectors, unlabeled_idx, forest, k: int, mode: str = "dw",
             density_mode: str = "gram"):
     """Run P shards in one process (tests): the all-gathers become concatenations."""
     torch = __import__("torch")
+    _soft_forest(forest, mode)
     u_full = parts_full = None
     if mode in DENSITY_MODES:  # uncertainty sampling never normalises
         preps = [s.prep() for s in selectors]
@@ -805,6 +830,7 @@ def _lal_local_votes(sel: ShardedSelector, unl, forest):
     """(flags, votes, local vote histogram int64 [T + 1]) of a rank's shard."""
     from .engine import lal_votes
 
+    _soft_forest(forest, "lal")
     torch = __import__("torch")
     st = sel.state
     if st.n == 0:

@@ -518,13 +518,22 @@ def predict(forest: Forest, X, device=None):
     ties -> class 0) on the GPU: (labels uint8 [n], votes int32 [n]).  A
     multiclass forest (n_classes > 2) returns (pred uint8 [n], counts uint8
     [n, C]): pred is the class id with the most trees, ties to the lowest id
-    (``forest.classes_[pred]`` is the label where the forest carries labels)."""
+    (``forest.classes_[pred]`` is the label where the forest carries labels).
+    A ProbabilityForest returns (pred uint8 [n], sums int64 [n, C]): pred is
+    the class of the largest averaged probability (scikit-learn's
+    ``rf.predict``), ties to the lowest id; predict_proba gives the
+    probabilities."""
     import torch
 
     from . import engine
     from ._lib import DAL_ASCENDING, DAL_MC_LEAST_CONFIDENCE
+    from .forest import ProbabilityForest
 
     state = X if isinstance(X, engine.PoolState) else engine.PoolState(X, device=device)
+    if isinstance(forest, ProbabilityForest):
+        sums, pred, _, _ = engine.forest_score_soft(state, forest, None, DAL_ASCENDING,
+                                                    engine.SOFT_KINDS["least_confidence"])
+        return pred, sums
     if forest.n_classes > 2:
         lut = engine.device_multiclass_lut("least_confidence", forest.n_trees, state.device)
         counts, pred, _, _ = engine.forest_score_multiclass(state, forest, lut, None, DAL_ASCENDING,
@@ -533,6 +542,21 @@ def predict(forest: Forest, X, device=None):
     lut = engine.device_lut("least_confidence", forest.n_trees, state.device)
     votes, _, _, _ = engine.forest_score(state, forest, lut, state.flags, DAL_ASCENDING)
     return (2 * votes > forest.n_trees).to(torch.uint8), votes
+
+
+def predict_proba(forest, X, device=None):
+    """scikit-learn's ``RandomForestClassifier.predict_proba`` of a
+    ProbabilityForest on the GPU: (proba fp64 [n, C], pred uint8 [n]).
+    proba[i, c] = (double)S_c / (double)(T 2^31), the exact class sums of the
+    quantised leaf distributions over one IEEE division: within 2^-31 of
+    ``rf.predict_proba``; pred is the lowest class of the largest sum."""
+    from .engine import soft_proba
+    from .forest import ProbabilityForest
+
+    if not isinstance(forest, ProbabilityForest):
+        raise ValueError("predict_proba needs a dal.forest.ProbabilityForest (a Forest keeps no leaf distributions)")
+    pred, sums = predict(forest, X, device=device)
+    return soft_proba(sums, forest.denominator), pred
 
 
 def predict_regression(model, X, device=None):

@@ -12,8 +12,8 @@ Ties (frequent: only T+1 distinct scores) go to the lower pool index.
 """
 from __future__ import annotations
 
-from .engine import PoolState, Selection, as_pool_state, multiclass_step, uncertainty_step
-from .forest import Forest
+from .engine import PoolState, Selection, as_pool_state, multiclass_step, soft_step, uncertainty_step
+from .forest import Forest, ProbabilityForest
 from .luts import STRATEGIES
 
 
@@ -32,10 +32,18 @@ def select(pool, unlabeled_idx, forest: Forest, k: int, strategy: str = "least_c
     trees) is scored by the C-class forms of the three strategies
     (dal.luts.multiclass_lut): the Selection then carries ``counts`` [U, C]
     and ``votes`` is None.
+
+    A dal.forest.ProbabilityForest (soft votes: the averaged leaf class
+    distributions, scikit-learn's ``predict_proba``) is scored by the same
+    three strategies on the averaged probabilities, exactly
+    (dal.engine.soft_step): the Selection then carries ``sums`` [U, C] and
+    ``proba()``; ``votes`` and ``counts`` are None.
     """
     if strategy not in STRATEGIES:
         raise ValueError(f"strategy must be one of {STRATEGIES}")
     state = as_pool_state(pool, device=device)
+    if isinstance(forest, ProbabilityForest):
+        return soft_step(state, unlabeled_idx, forest, k, strategy)
     if forest.n_classes > 2:
         return multiclass_step(state, unlabeled_idx, forest, k, strategy)
     return uncertainty_step(state, unlabeled_idx, forest, k, strategy)
@@ -52,7 +60,8 @@ def select_batch(pool, unlabeled_idx, labeled_idx, forest: Forest, k: int, strat
     The votes (binary) or per-class counts and scores (multiclass) come from
     the score entries ``select`` uses.  Weights in [0, 1], higher = more
     uncertain: binary, dal.luts.batch_weight_lut(strategy, T) gathered by the
-    votes; multiclass, dal.luts.batch_weights_multiclass of the scores.  They
+    votes; multiclass and soft votes (a ProbabilityForest),
+    dal.luts.batch_weights_multiclass of the scores.  They
     are scattered to pool rows on the device; the candidates are the unlabeled
     rows, the comparison set starts as ``labeled_idx`` (at least one row).
 
@@ -87,7 +96,7 @@ def select_batch(pool, unlabeled_idx, labeled_idx, forest: Forest, k: int, strat
             raise ValueError("sim_pool must have one row per pool row")
     unl = _as_index(unlabeled_idx, dev)
     scored = select(state, unl, forest, 1, strategy)  # votes / counts and scores of every unlabeled row
-    if forest.n_classes > 2:
+    if forest.n_classes > 2 or isinstance(forest, ProbabilityForest):
         w_unl = luts.batch_weights_multiclass(strategy, scored.scores, forest.n_classes)
     else:
         table = torch.from_numpy(luts.batch_weight_lut(strategy, forest.n_trees)).to(dev)
@@ -96,7 +105,8 @@ def select_batch(pool, unlabeled_idx, labeled_idx, forest: Forest, k: int, strat
     weights[unl] = w_unl
     ranked = ranked_batch_select(simx, labeled_idx, weights, k, alpha=alpha, candidates=unl, device=dev)
     sel = Selection(scores=ranked.scores, indices=ranked.indices, selected_scores=ranked.selected_scores,
-                    votes=scored._votes, counts=scored._counts)
+                    votes=scored._votes, counts=scored._counts, sums=scored._sums,
+                    denominator=scored.denominator)
     sel.selected_similarity = ranked.selected_similarity
     sel.weights = w_unl
     return sel

@@ -512,6 +512,62 @@ int dal_forest_score_multiclass_dw_blocked(const float* x, const float* xb, cons
                                            double* entropy, int32_t* row_index, double* scores, uint64_t* keys,
                                            uint64_t* keys_hi, dal_stream_t stream);
 
+/* ---- soft votes: averaged leaf class distributions, exact ----------------
+ * New symbols only: dal_abi_version() stays 10, and a caller probes for the
+ * feature with dal_forest_soft_max_depth() (DAL_SOFT_MAX_DEPTH; absent from
+ * older libraries).  The uncertainty of scikit-learn's predict_proba (modAL's
+ * uncertainty, margin and entropy sampling; spark.ml's probabilityCol): a tree
+ * contributes its leaf's class distribution, not one class id.
+ *
+ * The forest: inner is dal_forest_score's complete heap (int32 [T][2^D - 1][2],
+ * feature and fp32 threshold bits, x[f] <= thr goes left); leaf_id
+ * (int32 [T][2^D]) names, for every heap leaf, a row of the leaf table leaf_q
+ * (uint32 [n_leaves][n_classes]); leaf_q[l][c] = rint(p_l[c] 2^31), the
+ * leaf's class distribution in fixed point (<= DAL_SOFT_ONE; a row's words
+ * need not sum to DAL_SOFT_ONE).  1 <= n_trees <= 255, 2 <= n_classes <= 32,
+ * 1 <= depth <= DAL_SOFT_MAX_DEPTH.
+ *
+ *   S_c(i)   = sum_t leaf_q[leaf_id[t][leaf_t(x_i)]][c]   exact, < 2^39
+ *   sums[i][c] = S_c(i) (nullable);  pred[i] = the smallest c with maximal S_c
+ *   (nullable);  with M = n_trees 2^31 and by score_kind
+ *   DAL_SOFT_LEAST_CONFIDENCE  scores[i] = (double)max_c S_c / (double)M
+ *   DAL_SOFT_MARGIN            scores[i] = (double)(S_(1) - S_(2)) / (double)M,
+ *                              largest minus second largest, an integer
+ *                              difference, then the one division
+ *   DAL_SOFT_ENTROPY           scores[i] = ((0.0 + h(p_0)) + h(p_1)) + ...,
+ *                              p_c = (double)S_c / (double)M, h(p) = -p log2(p),
+ *                              h(0) = +0.0; sequential fp64 adds in class order,
+ *                              no FMA; never NaN or -0.0
+ * Every division is the IEEE one, so sums, pred and the first two scores are
+ * the same bits for every launch shape and on every device; the entropy
+ * carries the device log2's error (within n_classes 2^-49 of the host's).
+ * keys[i] = the score key for ``order``, DAL_KEY_NONE when the row is not
+ * DAL_ROW_CANDIDATE (row_flags NULL: every row is a candidate); select with
+ * dal_topk.
+ *
+ * x_stride is the row stride of x in elements, with the semantics of the other
+ * entries' ldx: any x_stride >= d and any 4-byte alignment of x (16-byte
+ * aligned rows with d % 4 == 0 take the wider staging forms).
+ * Before any device call: a null x, inner, leaf_id, leaf_q, scores or keys, or
+ * a bad order or score_kind, is DAL_ERR_ARG; then n < 0, d < 1, d > 2^30,
+ * x_stride < d, n_leaves < 1 or n_leaves > 2^26 DAL_ERR_SHAPE; then a depth,
+ * n_classes or n_trees outside the limits DAL_ERR_UNSUPPORTED.  n == 0 returns
+ * DAL_OK and launches nothing.  A leaf_id outside [0, n_leaves) is the caller's
+ * error (dal.forest.ProbabilityForest checks it before upload): the kernel
+ * clamps it into the table.  Every inner node's feature must lie in [0, d). */
+#define DAL_SOFT_MAX_DEPTH 16
+#define DAL_SOFT_MAX_CLASSES 32
+#define DAL_SOFT_MAX_TREES 255
+#define DAL_SOFT_ONE 2147483648u
+#define DAL_SOFT_LEAST_CONFIDENCE 0
+#define DAL_SOFT_MARGIN 1
+#define DAL_SOFT_ENTROPY 2
+int dal_forest_soft_max_depth(void);
+int dal_forest_score_soft(const float* x, int64_t n, int64_t d, int64_t x_stride, const int32_t* inner,
+                          const int32_t* leaf_id, const uint32_t* leaf_q, int64_t n_leaves, int32_t n_trees,
+                          int32_t depth, int32_t n_classes, int score_kind, const uint8_t* row_flags, int order,
+                          uint64_t* sums, uint8_t* pred, double* scores, uint64_t* keys, dal_stream_t stream);
+
 /* ---- (a11) top-k: sortBy(score).take(k) --------------------------------
  * Replaces uncertainty_sampling.py:106,109 / density_weighting.py:168,172.
  * The k smallest keys, ties -> lower index; out_idx = idx_base + row, sorted
