@@ -25,8 +25,12 @@ density is accumulated in exact int64 fixed point, and the canonical column
 sum is reduced over the same 256-row chunks in the same order, so every
 density bit, every score and the selected set are identical for P = 1..8.
 
-The phases are methods so that tests can drive P shards in one process
-(GPU, ``emulate``) or replace the local HIP steps with the oracle (CPU, gloo).
+Every sharded operation has ONE body, over a list of jobs and an ``ops``
+object that supplies the collectives: a rank calls it with its one job and
+_GroupOps (the real group), the ``emulate_*`` functions with P jobs in one
+process and _LocalOps (sums, stacks, concatenations), so a test that drives P
+emulated shards on the GPU runs the code the ranks run.  The local phases are
+selector methods, which the CPU tests replace with the oracle.
 """
 from __future__ import annotations
 
@@ -79,6 +83,14 @@ class LocalTopk:
     keys: object  # int64 [k] (uint64 bit patterns)
     idx: object  # int64 [k] global row indices
     scores: object  # fp64 [k]
+
+    @classmethod
+    def empty(cls, k: int, device):
+        """k padding slots: DAL_KEY_NONE, index -1, score NaN."""
+        torch = __import__("torch")
+        return cls(torch.full((k,), _as_i64(DAL_KEY_NONE), dtype=torch.int64, device=device),
+                   torch.full((k,), -1, dtype=torch.int64, device=device),
+                   torch.full((k,), float("nan"), dtype=torch.float64, device=device))
 
 
 def merge_topk(keys_all, idx_all, scores_all, k: int, sort_fn, all_valid: bool = False):
@@ -335,19 +347,12 @@ class ShardedSelector:
                              topk_keys, uncertainty_blocked)
         from .luts import ASCENDING
 
-        torch = __import__("torch")
         st = self.state
-
-        def empty():
-            return LocalTopk(torch.full((k,), _as_i64(DAL_KEY_NONE), dtype=torch.int64, device=st.device),
-                             torch.full((k,), -1, dtype=torch.int64, device=st.device),
-                             torch.full((k,), float("nan"), dtype=torch.float64, device=st.device))
-
         soft = _soft_forest(forest, mode)
         if mode == "dw" and forest.n_classes > 2:
             raise ValueError(f"density weighting is binary only: the forest has {forest.n_classes} classes")
         if st.n == 0:
-            return empty()
+            return LocalTopk.empty(k, st.device)
         flags, unl, _ = st.row_flags(unlabeled_idx)
         # no host count of this shard's candidates (a sync): rows that are not
         # candidates carry the padding key, so with fewer than k candidates
@@ -425,7 +430,7 @@ class ShardedSelector:
             s = sc[i - st.row_base]
         if kk == k:  # every slot written by the selection
             return LocalTopk(kk_keys, i, s)
-        out = empty()
+        out = LocalTopk.empty(k, st.device)
         out.keys[:kk], out.idx[:kk], out.scores[:kk] = kk_keys, i, s
         return out
 
@@ -535,84 +540,204 @@ class TorchComm:
             work.wait()
 
 
-def select(sel: ShardedSelector, comm, unlabeled_idx, forest, k: int, mode: str = "dw",
-           strategy: str = "least_confidence", beta: float = 1.0, sort_fn=hip_sort_positions,
-           density_mode: str = "gram"):
-    """One selection step across all ranks; returns (indices [k], scores [k]),
-    identical on every rank."""
+class _GroupOps:
+    """The collectives of a sharded operation over a real group (one local job)."""
+
+    def __init__(self, comm):
+        self.comm = comm
+
+    def reduce(self, tensors, op: str):
+        dist = self.comm.dist
+        ops = {"sum": dist.ReduceOp.SUM, "min": dist.ReduceOp.MIN, "max": dist.ReduceOp.MAX}
+        dist.all_reduce(tensors[0], op=ops[op], group=self.comm.group)  # in place, stream-ordered
+        return tensors
+
+    def gather_rows(self, tensors):
+        """Every rank's rows [c_r, w] as one [sum c_r, w]: the counts first,
+        then the rows padded to the largest count."""
+        torch = __import__("torch")
+        t = tensors[0]
+        counts = self.comm.all_gather(torch.tensor([t.shape[0]], dtype=torch.int64, device=t.device)).cpu().tolist()
+        top = max(counts)
+        pad = torch.zeros((top,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+        pad[:t.shape[0]] = t
+        got = self.comm.all_gather(pad).reshape((len(counts), top) + tuple(t.shape[1:]))
+        return [torch.cat([got[r, :c] for r, c in enumerate(counts)])]
+
+    def all_gather(self, tensors):
+        """Every rank's block [m, ...] of ONE shape as [P * m, ...]: no counts, no host read."""
+        return [self.comm.all_gather(tensors[0])]
+
+    def gather_row(self, rows):
+        """One int64 row per rank as [P, w] (TorchComm.all_gather_rows: stream-ordered, no host
+        read; a comm without that method gathers the row as a [1, w] block)."""
+        comm = self.comm
+        if hasattr(comm, "all_gather_rows"):
+            return [comm.all_gather_rows(rows[0])]
+        return [comm.all_gather(rows[0].reshape(1, -1))]
+
+    def exchange_density(self, sels, preps):
+        """The operand / partials exchange beside the own-shard Gram
+        (ShardedSelector.exchange_density); [(gathered operand, gathered partials)]."""
+        return [sels[0].exchange_density(self.comm, *preps[0])]
+
+
+class _LocalOps:
+    """The same collectives over P jobs in one process (emulate_*)."""
+
+    def reduce(self, tensors, op: str):
+        torch = __import__("torch")
+        stack = torch.stack([t.to(tensors[0].device) for t in tensors])
+        red = {"sum": stack.sum(dim=0), "min": stack.amin(dim=0), "max": stack.amax(dim=0)}[op]
+        return [red.to(dtype=t.dtype, device=t.device) for t in tensors]
+
+    def gather_rows(self, tensors):
+        torch = __import__("torch")
+        return [torch.cat([t.to(u.device) for t in tensors]) for u in tensors]
+
+    all_gather = gather_rows  # (equal shapes: the same concatenation)
+
+    def gather_row(self, rows):
+        torch = __import__("torch")
+        return [torch.stack([t.to(u.device) for t in rows]) for u in rows]
+
+    def exchange_density(self, sels, preps):
+        u_fulls = self.all_gather([p[0] for p in preps])
+        for s, u in zip(sels, u_fulls):
+            s.set_density(s.density_contribution(u))
+        return list(zip(u_fulls, self.all_gather([p[1] for p in preps])))
+
+
+def _select(sels, ops, unlabeled_idx, forest, k, mode, strategy, beta, sort_fn, density_mode):
+    """select over the jobs ``sels`` (one rank's selector, or P emulated
+    shards) with the collectives ``ops``: one (indices, scores) per job.  Every
+    decision is taken from values that are the same on every rank."""
     _soft_forest(forest, mode)
-    unl = sel.index_tensor(unlabeled_idx)
-    u_full = parts_full = None
-    warm = sel._density is not None  # (a cold step's score kernel keeps the row-major pool)
+    unls = [s.index_tensor(unlabeled_idx) for s in sels]
+    u_fulls = parts_fulls = [None] * len(sels)
+    warm = [s._density is not None for s in sels]  # (a cold step's score kernel keeps the row-major pool)
     if mode in DENSITY_MODES:  # uncertainty sampling never normalises (no density, no zero-norm check)
-        need_u = density_mode == "gram" and sel._density is None
-        if need_u or sel._parts_full is None:
-            u_local, parts = sel.prep()
+        need_u = density_mode == "gram" and not all(warm)
+        if need_u or any(s._parts_full is None for s in sels):
+            preps = [s.prep() for s in sels]
             if need_u:  # the (small) canonical partials travel with the operand, beside the Gram
-                u_full, parts_full = sel.exchange_density(comm, u_local, parts)
+                u_fulls, parts_fulls = zip(*ops.exchange_density(sels, preps))
             else:
-                parts_full = comm.all_gather(parts)
-            sel._parts_full = parts_full
-            sel._colsum = None  # derived from the partials, as the plans' captured column sum
-            sel._plans = {}
-        parts_full = sel._parts_full
-    n_unl_global = int(unl.shape[0])  # single source of truth for the candidate count
-    stt = getattr(sel, "state", None)  # (the CPU tests' oracle shards have none)
-    if (stt is not None and mode == "dw" and density_mode == "gram" and u_full is None
-            and sel._density is not None and sort_fn is hip_sort_positions and sel.world * k <= _lib.DAL_SORT_CAP and stt.use_graphs
-            and stt.events_off() and stt.n >= k and unl.is_cuda):
+                parts_fulls = ops.all_gather([p[1] for p in preps])
+            for s, parts in zip(sels, parts_fulls):
+                s._parts_full = parts
+                s._colsum = None  # derived from the partials, as the plans' captured column sum
+                s._plans = {}
+        parts_fulls = [s._parts_full for s in sels]
+    all_valid = int(unls[0].shape[0]) >= k  # single source of truth for the candidate count
+
+    def planned(s, u_full, unl):
+        st = getattr(s, "state", None)  # (the CPU tests' oracle shards have none)
+        return (st is not None and u_full is None and s._density is not None and s.world * k <= _lib.DAL_SORT_CAP
+                and st.use_graphs and st.events_off() and st.n >= k and unl.is_cuda)
+
+    if (mode == "dw" and density_mode == "gram" and sort_fn is hip_sort_positions
+            and all(planned(s, u, unl) for s, u, unl in zip(sels, u_fulls, unls))):
         # warm step (density cached): the local step is one plan replay whose
         # outputs ARE the packed all-gather row; no host wait before the merge
-        plan = sel.warm_plan(forest, k, beta)
-        plan.launch(forest, unl)
-        out, st = merge_row(comm, plan.packed, k, all_valid=n_unl_global >= k)
-        return _finish(sel, comm, unlabeled_idx, forest, k, mode, strategy, beta, sort_fn, density_mode, out, st)
-    top = sel.local_select(u_full, parts_full, unl, forest, k, mode, strategy, beta, density_mode, warm=warm)
-    # every rank's status word (zero-norm rows, re-rank capacity overflow)
-    # rides in the top-k all-gather and is read once, after the merge is
-    # queued: the step's one host sync, and every rank sees the same bits
-    if sort_fn is hip_sort_positions and sel.world * k <= _lib.DAL_SORT_CAP and top.keys.is_cuda:
-        out, st = merge_packed(comm, top, sel.status_word(), k, all_valid=n_unl_global >= k)
+        plans = [s.warm_plan(forest, k, beta) for s in sels]
+        for plan, unl in zip(plans, unls):
+            plan.launch(forest, unl)
+        merged = [_merge_rows(g, k, all_valid) for g in ops.gather_row([plan.packed for plan in plans])]
     else:
-        keys_all, idx_all, sc_all, st_all = gather_topk(comm, top, sel.status_word())
-        out = merge_topk(keys_all, idx_all, sc_all, k, sort_fn, all_valid=n_unl_global >= k)
-        st = 0
-        for v in st_all.tolist():
-            st |= int(v)
-    return _finish(sel, comm, unlabeled_idx, forest, k, mode, strategy, beta, sort_fn, density_mode, out, st)
-
-
-def _finish(sel, comm, unlabeled_idx, forest, k, mode, strategy, beta, sort_fn, density_mode, out, st):
-    """Act on the OR of every rank's status word (identical on all ranks)."""
+        tops = [s.local_select(u, parts, unl, forest, k, mode, strategy, beta, density_mode, warm=w)
+                for s, u, parts, unl, w in zip(sels, u_fulls, parts_fulls, unls, warm)]
+        # every rank's status word (zero-norm rows, re-rank capacity overflow)
+        # rides in the top-k all-gather and is read once, after the merge is
+        # queued: the step's one host sync, and every rank sees the same bits
+        merged = _merge(ops, tops, [s.status_word() for s in sels], sels[0].world, k, sort_fn, all_valid)
+    st = merged[0][1]  # the OR of every rank's status word: identical on all ranks and jobs
     if mode not in DENSITY_MODES:
         st &= ~_lib.DAL_FLAG_ZERO_NORM  # a zero row only matters to the cosine density
     if st & _lib.DAL_FLAG_ZERO_NORM:
         raise ValueError("pool contains a zero-norm row: cosine similarity is undefined "
                          "(the reference would propagate NaN into every density)")
     if st & (_lib.DAL_FLAG_CAND_OVERFLOW | _lib.DAL_FLAG_SAMPLE_MISS):  # rare: redo on every rank
-        sel.prepare_retry(sample_miss=bool(st & _lib.DAL_FLAG_SAMPLE_MISS))
-        return select(sel, comm, unlabeled_idx, forest, k, mode, strategy, beta, sort_fn, density_mode)
-    return out
+        for s in sels:
+            s.prepare_retry(sample_miss=bool(st & _lib.DAL_FLAG_SAMPLE_MISS))
+        return _select(sels, ops, unlabeled_idx, forest, k, mode, strategy, beta, sort_fn, density_mode)
+    return [out for out, _ in merged]
 
 
-def gather_topk(comm, top: LocalTopk, status=None):
-    """ONE all-gather of every rank's (key, index, score) triples, packed as
-    int64 [3k] (scores by bit pattern), plus the rank's status word when
-    given: a collective's latency, not its bytes, dominates at k = 100-1000.
-    Returns (keys, idx, scores) rank-major [P*k] (+ statuses [P])."""
+def select(sel: ShardedSelector, comm, unlabeled_idx, forest, k: int, mode: str = "dw",
+           strategy: str = "least_confidence", beta: float = 1.0, sort_fn=hip_sort_positions,
+           density_mode: str = "gram"):
+    """One selection step across all ranks; returns (indices [k], scores [k]),
+    identical on every rank."""
+    return _select([sel], _GroupOps(comm), unlabeled_idx, forest, k, mode, strategy, beta, sort_fn, density_mode)[0]
+
+
+def emulate(selectors, unlabeled_idx, forest, k: int, mode: str = "dw",
+            strategy: str = "least_confidence", beta: float = 1.0, sort_fn=hip_sort_positions,
+            density_mode: str = "gram"):
+    """select with P shards in one process (tests).  The P jobs must agree;
+    their one (indices, scores) is returned."""
+    return _same_topk(_select(list(selectors), _LocalOps(), unlabeled_idx, forest, k, mode, strategy, beta, sort_fn,
+                              density_mode))
+
+
+def _agreed(results, fingerprint, what: str):
+    """emulate_*: the one result of P jobs, whose fingerprints must agree."""
+    first = fingerprint(results[0])
+    if any(fingerprint(r) != first for r in results[1:]):
+        raise RuntimeError(f"the shards' {what} differ")
+    return results[0]
+
+
+def _same_topk(outs):
+    """emulate, emulate_lal: every job must have merged the same (indices, score bits)."""
+    return _agreed(outs, lambda o: [t.cpu().numpy().tobytes() for t in o], "merged selections")
+
+
+def _pack_topk(top: LocalTopk, status=None):
+    """A rank's (key, index, score) triples as one int64 row [3k] (scores by
+    bit pattern), plus its status word when given ([3k + 1])."""
     torch = __import__("torch")
-    k = int(top.keys.shape[0])
     parts = [top.keys, top.idx, top.scores.view(torch.int64)]
     if status is not None:
         parts.append(status.reshape(1).to(torch.int64))
-    packed = torch.cat(parts)
-    w = int(packed.shape[0])
-    g = comm.all_gather(packed.reshape(1, w)).reshape(-1, w)              # [P, 3k (+1)]
+    return torch.cat(parts)
+
+
+def _unpack_topk(g, k: int):
+    """Gathered rows [P, 3k (+1)] -> (keys, idx, scores) rank-major [P*k] (+ statuses [P])."""
+    torch = __import__("torch")
     out = (g[:, :k].reshape(-1), g[:, k:2 * k].reshape(-1),
            g[:, 2 * k:3 * k].reshape(-1).contiguous().view(torch.float64))
-    if status is not None:
-        out = out + (g[:, 3 * k],)
-    return out
+    return out + (g[:, 3 * k],) if int(g.shape[1]) > 3 * k else out
+
+
+def gather_topk(comm, top: LocalTopk, status=None):
+    """ONE all-gather of every rank's packed row (_pack_topk): a collective's
+    latency, not its bytes, dominates at k = 100-1000.
+    Returns (keys, idx, scores) rank-major [P*k] (+ statuses [P])."""
+    row = _pack_topk(top, status)
+    w = int(row.shape[0])
+    return _unpack_topk(comm.all_gather(row.reshape(1, w)).reshape(-1, w), int(top.keys.shape[0]))
+
+
+def _merge(ops, tops, statuses, world: int, k: int, sort_fn, all_valid: bool, want_status: bool = True):
+    """The merge of every rank's local top-k, per job: [((indices, scores), OR
+    of the status words)].  ONE all-gather of the packed rows [3k + 1], then
+    dal_topk_merge (_merge_rows) where the HIP sort takes world * k keys, else
+    merge_topk with ``sort_fn`` and the statuses OR-ed on the host
+    (want_status False: not read there, 0)."""
+    gathered = ops.gather_row([_pack_topk(top, status) for top, status in zip(tops, statuses)])
+    if sort_fn is hip_sort_positions and world * k <= _lib.DAL_SORT_CAP and tops[0].keys.is_cuda:
+        return [_merge_rows(g, k, all_valid) for g in gathered]
+    merged = []
+    for g in gathered:
+        keys_all, idx_all, sc_all, st_all = _unpack_topk(g, k)
+        st = 0
+        for v in (st_all.tolist() if want_status else ()):
+            st |= int(v)
+        merged.append((merge_topk(keys_all, idx_all, sc_all, k, sort_fn, all_valid=all_valid), st))
+    return merged
 
 
 def merge_packed(comm, top: LocalTopk, status, k: int, all_valid: bool = False):
@@ -621,23 +746,24 @@ def merge_packed(comm, top: LocalTopk, status, k: int, all_valid: bool = False):
     by (key, rank-major position), gather; the status words OR-ed on the
     device).  Returns ((indices, scores), status) -- the status read is the
     step's one host sync."""
-    torch = __import__("torch")
-    packed = torch.cat([top.keys, top.idx, top.scores.view(torch.int64), status.reshape(1).to(torch.int64)])
-    return merge_row(comm, packed, k, all_valid)
+    return merge_row(comm, _pack_topk(top, status), k, all_valid)
 
 
 def merge_row(comm, packed, k: int, all_valid: bool = False):
     """All-gather this rank's packed row int64 [3k+1] (keys | indices | score
     bits | status) and merge the rows with dal_topk_merge; returns ((indices,
     scores), OR of the status words)."""
+    return _merge_rows(_GroupOps(comm).gather_row([packed])[0], k, all_valid)
+
+
+def _merge_rows(g, k: int, all_valid: bool = False):
+    """dal_topk_merge over the gathered packed rows [P, 3k+1]."""
     torch = __import__("torch")
     from .engine import _ptr, _stream
     from ._lib import call
 
-    dev = packed.device
-    w = int(packed.shape[0])
-    g = comm.all_gather_rows(packed) if hasattr(comm, "all_gather_rows") else comm.all_gather(packed.reshape(1, w))
-    n_ranks = int(g.shape[0])
+    dev = g.device
+    n_ranks, w = int(g.shape[0]), int(g.shape[1])
     lib = _lib.load()
     wsb = int(lib.dal_topk_merge_workspace_bytes(n_ranks, k))
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None  # (the one-launch merge needs none)
@@ -655,41 +781,6 @@ def merge_row(comm, packed, k: int, all_valid: bool = False):
         valid = out_keys != _as_i64(DAL_KEY_NONE)
         out_idx, out_sc = out_idx[valid], out_sc[valid]
     return (out_idx, out_sc), st
-
-
-def emulate(selectors, unlabeled_idx, forest, k: int, mode: str = "dw",
-            strategy: str = "least_confidence", beta: float = 1.0, sort_fn=hip_sort_positions,
-            density_mode: str = "gram"):
-    """Run P shards in one process (tests): the all-gathers become concatenations."""
-    torch = __import__("torch")
-    _soft_forest(forest, mode)
-    u_full = parts_full = None
-    if mode in DENSITY_MODES:  # uncertainty sampling never normalises
-        preps = [s.prep() for s in selectors]
-        u_full = torch.cat([p[0] for p in preps])
-        parts_full = torch.cat([p[1] for p in preps])
-    if mode in DENSITY_MODES and density_mode == "gram" and selectors and selectors[0]._density is None:
-        for s in selectors:
-            s.set_density(s.density_contribution(u_full))
-    tops = [s.local_select(u_full, parts_full, unlabeled_idx, forest, k, mode, strategy, beta,
-                           density_mode)
-            for s in selectors]
-    keys_all = torch.cat([t.keys for t in tops])
-    idx_all = torch.cat([t.idx for t in tops])
-    sc_all = torch.cat([t.scores for t in tops])
-    n_unl = int(np.asarray(unlabeled_idx).reshape(-1).shape[0]) if not hasattr(unlabeled_idx, "shape") \
-        else int(unlabeled_idx.shape[0])
-    out = merge_topk(keys_all, idx_all, sc_all, k, sort_fn, all_valid=n_unl >= k)
-    st = 0
-    for s in selectors:
-        st |= int(s.state.status.item())
-    if st & (_lib.DAL_FLAG_SAMPLE_MISS | _lib.DAL_FLAG_CAND_OVERFLOW):  # as select(): redo on every shard
-        for s in selectors:
-            s.prepare_retry(sample_miss=bool(st & _lib.DAL_FLAG_SAMPLE_MISS))
-        return emulate(selectors, unlabeled_idx, forest, k, mode, strategy, beta, sort_fn, density_mode)
-    for s in selectors:
-        s.state.check_status()
-    return out
 
 
 def _exclude_chunks(st, rows):
@@ -720,6 +811,26 @@ def _exclude_cold(sel: ShardedSelector, new):
     sel._plans = {}
 
 
+def _exclude(sels, ops, rows) -> int:
+    """exclude over the jobs ``sels`` with the collectives ``ops``; the count
+    of newly excluded rows (E is global: one number for every job)."""
+    new, chunks = _exclude_chunks(sels[0].state, rows)
+    if new.size == 0:
+        return 0
+    if any(s._density is None for s in sels) or sels[0].state.gram == "f32":
+        for s in sels:
+            _exclude_cold(s, new)
+        return int(new.size)
+    for chunk in chunks:
+        for s, blocks in zip(sels, ops.all_gather([s.state.delta_operand(chunk) for s in sels])):
+            s.state.apply_exclude(chunk, _sum_delta(blocks, s.world))
+    for s, parts in zip(sels, ops.all_gather([s.prep()[1] for s in sels])):
+        s._parts_full = parts
+        s._colsum = None
+        s._plans = {}
+    return int(new.size)
+
+
 def exclude(sel: ShardedSelector, comm, rows) -> int:
     """PoolState.exclude across all ranks (every rank calls it with the same
     ``rows``, global indices): one small all-gather per chunk carries the
@@ -730,45 +841,12 @@ def exclude(sel: ShardedSelector, comm, rows) -> int:
     rebuilt on the next step.  Ranks that own none of Delta, and empty
     shards, take part in the collectives and leave their rows as they are.
     Returns the count of newly excluded rows."""
-    st = sel.state
-    new, chunks = _exclude_chunks(st, rows)
-    if new.size == 0:
-        return 0
-    if sel._density is None or st.gram == "f32":
-        _exclude_cold(sel, new)
-        return int(new.size)
-    for chunk in chunks:
-        delta = _sum_delta(comm.all_gather(st.delta_operand(chunk)), sel.world)
-        st.apply_exclude(chunk, delta)
-    sel._parts_full = comm.all_gather(sel.prep()[1])
-    sel._colsum = None
-    sel._plans = {}
-    return int(new.size)
+    return _exclude([sel], _GroupOps(comm), rows)
 
 
 def emulate_exclude(selectors, rows) -> int:
-    """``exclude`` for P shards in one process (tests): the all-gathers become
-    concatenations."""
-    torch = __import__("torch")
-    if not selectors:
-        return 0
-    new, chunks = _exclude_chunks(selectors[0].state, rows)
-    if new.size == 0:
-        return 0
-    if any(s._density is None for s in selectors) or selectors[0].state.gram == "f32":
-        for s in selectors:
-            _exclude_cold(s, new)
-        return int(new.size)
-    for chunk in chunks:
-        delta = _sum_delta(torch.cat([s.state.delta_operand(chunk) for s in selectors]), len(selectors))
-        for s in selectors:
-            s.state.apply_exclude(chunk, delta)
-    parts_full = torch.cat([s.prep()[1] for s in selectors])
-    for s in selectors:
-        s._parts_full = parts_full
-        s._colsum = None
-        s._plans = {}
-    return int(new.size)
+    """exclude with P shards in one process (tests)."""
+    return _exclude(list(selectors), _LocalOps(), rows) if selectors else 0
 
 
 def diversity_select_sharded(x_local, row_base: int, labeled_rows, k: int, comm, candidates=None,
@@ -779,20 +857,17 @@ def diversity_select_sharded(x_local, row_base: int, labeled_rows, k: int, comm,
     merged identically on every rank."""
     from .similarity import diversity_select
 
-    torch = __import__("torch")
     n = int(x_local.shape[0])
     dev = x_local.device if device is None else device
-    keys = torch.full((k,), _as_i64(DAL_KEY_NONE), dtype=torch.int64, device=dev)
-    idx = torch.full((k,), -1, dtype=torch.int64, device=dev)
-    sc = torch.full((k,), float("nan"), dtype=torch.float64, device=dev)
+    top = LocalTopk.empty(k, dev)
     if n:
         sel = diversity_select(x_local, None, k, candidates=candidates, device=dev, row_base=row_base,
                                labeled_rows=labeled_rows)
         kk = int(sel.indices.shape[0])
-        idx[:kk] = sel.indices
-        sc[:kk] = sel.selected_scores
-        keys[:kk] = _score_keys_asc(sel.selected_scores)
-    return merge_topk(*gather_topk(comm, LocalTopk(keys, idx, sc)), k, sort_fn)
+        top.idx[:kk] = sel.indices
+        top.scores[:kk] = sel.selected_scores
+        top.keys[:kk] = _score_keys_asc(sel.selected_scores)
+    return merge_topk(*gather_topk(comm, top), k, sort_fn)
 
 
 def _score_keys_asc(s):
@@ -812,11 +887,8 @@ def _lal_local_topk(sel: ShardedSelector, flags, votes, hist_global, forest, lal
     the same T + 1 rows and the same LUT) and its exact local top-k."""
     from .engine import lal_scores, topk_keys
 
-    torch = __import__("torch")
     st = sel.state
-    out = LocalTopk(torch.full((k,), _as_i64(DAL_KEY_NONE), dtype=torch.int64, device=st.device),
-                    torch.full((k,), -1, dtype=torch.int64, device=st.device),
-                    torch.full((k,), float("nan"), dtype=torch.float64, device=st.device))
+    out = LocalTopk.empty(k, st.device)
     if st.n == 0:
         return out
     _, sc, kys = lal_scores(st, forest, lal_model, flags, votes, hist_global, n_labeled, n_positive)
@@ -840,6 +912,26 @@ def _lal_local_votes(sel: ShardedSelector, unl, forest):
     return flags, votes, hist
 
 
+def _select_lal(sels, ops, unlabeled_idx, forest, lal_model, k, n_labeled, n_positive, sort_fn):
+    """select_lal over the jobs ``sels`` with the collectives ``ops``: one
+    (indices, scores) per job."""
+    from .engine import check_lal_inputs
+
+    check_lal_inputs(forest, lal_model, n_labeled, n_positive)
+    unls = [s.index_tensor(unlabeled_idx) for s in sels]
+    n_unl_global = int(unls[0].shape[0])
+    if n_unl_global == 0:
+        raise ValueError("unlabeled set is empty (the reference loop breaks here)")
+    local = [_lal_local_votes(s, unl, forest) for s, unl in zip(sels, unls)]
+    hists = ops.reduce([hist for _, _, hist in local], "sum")
+    tops = [_lal_local_topk(s, flags, votes, hist, forest, lal_model, k, n_labeled, n_positive)
+            for s, (flags, votes, _), hist in zip(sels, local, hists)]
+    # (the status word rides in the packed row and is not acted on: nothing here sets it)
+    merged = _merge(ops, tops, [s.status_word() for s in sels], sels[0].world, k, sort_fn,
+                    all_valid=n_unl_global >= k, want_status=False)
+    return [out for out, _ in merged]
+
+
 def select_lal(sel: ShardedSelector, comm, unlabeled_idx, forest, lal_model, k: int, n_labeled: int,
                n_positive: int, sort_fn=hip_sort_positions):
     """One LAL selection step across all ranks (dal.active_learner.select_lal
@@ -848,45 +940,15 @@ def select_lal(sel: ShardedSelector, comm, unlabeled_idx, forest, lal_model, k: 
     the histograms are summed by ONE all_reduce of T + 1 int64 (integers: the
     same bits in any order); every rank then builds the same rows and LUT,
     rescores its rows and keeps its local top-k, merged as mode "us" does."""
-    from .engine import check_lal_inputs
-
-    check_lal_inputs(forest, lal_model, n_labeled, n_positive)
-    unl = sel.index_tensor(unlabeled_idx)
-    n_unl_global = int(unl.shape[0])
-    if n_unl_global == 0:
-        raise ValueError("unlabeled set is empty (the reference loop breaks here)")
-    flags, votes, hist = _lal_local_votes(sel, unl, forest)
-    comm.dist.all_reduce(hist, group=comm.group)  # SUM
-    top = _lal_local_topk(sel, flags, votes, hist, forest, lal_model, k, n_labeled, n_positive)
-    if sort_fn is hip_sort_positions and sel.world * k <= _lib.DAL_SORT_CAP and top.keys.is_cuda:
-        out, _ = merge_packed(comm, top, sel.status_word(), k, all_valid=n_unl_global >= k)
-        return out
-    keys_all, idx_all, sc_all = gather_topk(comm, top)
-    return merge_topk(keys_all, idx_all, sc_all, k, sort_fn, all_valid=n_unl_global >= k)
+    return _select_lal([sel], _GroupOps(comm), unlabeled_idx, forest, lal_model, k, n_labeled, n_positive, sort_fn)[0]
 
 
 def emulate_lal(selectors, unlabeled_idx, forest, lal_model, k: int, n_labeled: int, n_positive: int,
                 sort_fn=hip_sort_positions):
-    """select_lal with P shards in one process (tests): the all_reduce becomes
-    a sum, the all-gather a concatenation."""
-    from .engine import check_lal_inputs
-
-    torch = __import__("torch")
-    check_lal_inputs(forest, lal_model, n_labeled, n_positive)
-    unls = [s.index_tensor(unlabeled_idx) for s in selectors]
-    n_unl = int(unls[0].shape[0])
-    if n_unl == 0:
-        raise ValueError("unlabeled set is empty (the reference loop breaks here)")
-    local = [_lal_local_votes(s, u, forest) for s, u in zip(selectors, unls)]
-    hist = local[0][2].clone()
-    for _, _, h in local[1:]:
-        hist += h.to(hist.device)
-    tops = [_lal_local_topk(s, fl, v, hist.to(s.state.device), forest, lal_model, k, n_labeled, n_positive)
-            for s, (fl, v, _) in zip(selectors, local)]
-    keys_all = torch.cat([t.keys for t in tops])
-    idx_all = torch.cat([t.idx for t in tops])
-    sc_all = torch.cat([t.scores for t in tops])
-    return merge_topk(keys_all, idx_all, sc_all, k, sort_fn, all_valid=n_unl >= k)
+    """select_lal with P shards in one process (tests).  The P jobs must
+    agree; their one (indices, scores) is returned."""
+    return _same_topk(_select_lal(list(selectors), _LocalOps(), unlabeled_idx, forest, lal_model, k, n_labeled,
+                                  n_positive, sort_fn))
 
 
 # --------------------------------------------------------- StandardScaler --
@@ -921,6 +983,25 @@ def _cells_and_rows(cells, n_local: int):
     return torch.cat([cells.reshape(-1), torch.tensor([n_local], dtype=torch.int64, device=cells.device)])
 
 
+def _fit_scaler(shards, ops, accumulate_fn, with_mean: bool, with_std: bool):
+    """fit_scaler over the jobs ``shards`` with the collectives ``ops``: one
+    StandardScalerModel per job."""
+    from . import dataset as ds
+
+    torch = __import__("torch")
+    fn = accumulate_fn or _device_moments
+    lows, his = [], []
+    for x_local in shards:
+        low, top, bad = fn(x_local, None)
+        lows.append(low.clone())
+        his.append(torch.cat([top.reshape(-1), torch.as_tensor(bad, dtype=torch.int32, device=top.device).reshape(1)]))
+    low = ops.reduce(lows, "min")[0]
+    hi = ops.reduce(his, "max")[0].cpu().numpy()  # the columns' tops, then any rank's non-finite flag
+    k1, k2, q = ds.check_format(low.cpu().numpy(), hi[:-1], int(hi[-1]))
+    bufs = ops.reduce([_cells_and_rows(fn(x_local, (q, k1, k2)), int(x_local.shape[0])) for x_local in shards], "sum")
+    return [_scaler_model(buf, q, k1, k2, with_mean, with_std) for buf in bufs]
+
+
 def fit_scaler(x_local, comm, accumulate_fn=None, with_mean: bool = True, with_std: bool = True):
     """dal.dataset.StandardScaler.fit over row shards: the same mean and std
     bytes on every rank and for every P.  All-reduce MIN of the columns' lowest
@@ -930,39 +1011,14 @@ def fit_scaler(x_local, comm, accumulate_fn=None, with_mean: bool = True, with_s
     accumulate_fn(x_local, fmt): the two local steps (tests inject the
     restatement; None: the HIP kernels) -- fmt None returns (low, top,
     nonfinite flag), fmt = (q, k1, k2) returns the shard's cells [d, k1 + k2]."""
-    from . import dataset as ds
-
-    torch = __import__("torch")
-    dist = comm.dist
-    fn = accumulate_fn or _device_moments
-    low, top, bad = fn(x_local, None)
-    low = low.clone()
-    hi = torch.cat([top.reshape(-1), torch.as_tensor(bad, dtype=torch.int32, device=top.device).reshape(1)])
-    dist.all_reduce(low, op=dist.ReduceOp.MIN, group=comm.group)
-    dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=comm.group)
-    hi = hi.cpu().numpy()
-    k1, k2, q = ds.check_format(low.cpu().numpy(), hi[:-1], int(hi[-1]))
-    buf = _cells_and_rows(fn(x_local, (q, k1, k2)), int(x_local.shape[0]))
-    dist.all_reduce(buf, group=comm.group)  # SUM
-    return _scaler_model(buf, q, k1, k2, with_mean, with_std)
+    return _fit_scaler([x_local], _GroupOps(comm), accumulate_fn, with_mean, with_std)[0]
 
 
 def emulate_fit_scaler(shards, accumulate_fn=None, with_mean: bool = True, with_std: bool = True):
-    """fit_scaler with P shards in one process (tests): each all-reduce
-    becomes an elementwise min / max / sum over the shards."""
-    from . import dataset as ds
-
-    torch = __import__("torch")
-    fn = accumulate_fn or _device_moments
-    fmts = [fn(s, None) for s in shards]
-    low = torch.stack([f[0] for f in fmts]).amin(dim=0)
-    top = torch.stack([f[1] for f in fmts]).amax(dim=0)
-    k1, k2, q = ds.check_format(low.cpu().numpy(), top.cpu().numpy(), max(int(f[2]) for f in fmts))
-    buf = None
-    for s in shards:
-        b = _cells_and_rows(fn(s, (q, k1, k2)), int(s.shape[0]))
-        buf = b.clone() if buf is None else buf + b.to(buf.device)
-    return _scaler_model(buf, q, k1, k2, with_mean, with_std)
+    """fit_scaler with P shards in one process (tests).  The P jobs must
+    agree; their one model is returned."""
+    models = _fit_scaler(list(shards), _LocalOps(), accumulate_fn, with_mean, with_std)
+    return _agreed(models, lambda m: (m.mean.tobytes(), m.std.tobytes(), m.n), "scaler fits")
 
 
 # ------------------------------------------------------------ evaluation --
@@ -990,6 +1046,17 @@ def _shard_table(fn, x_local, y_local, forest):
     return t
 
 
+def _evaluate(shards, forest, ops, hist_fn, measures):
+    """evaluate over the jobs ``shards`` = [(x_local, y_local)] with the
+    collectives ``ops``: one dict per job."""
+    from . import metrics
+
+    names = metrics.check_measures(measures, forest.n_classes)
+    fn = hist_fn or _device_table
+    bufs = ops.reduce([_shard_table(fn, x, y, forest).clone() for x, y in shards], "sum")
+    return [metrics.finish(buf.cpu().numpy(), forest.n_trees, forest.n_classes, names) for buf in bufs]
+
+
 def evaluate(x_local, y_local, forest, comm, hist_fn=None, measures=("accuracy",)):
     """dal.metrics.evaluate over row shards: every rank computes its shard's
     joint table, ONE all_reduce SUM of the int64 cells, then every rank
@@ -998,76 +1065,17 @@ def evaluate(x_local, y_local, forest, comm, hist_fn=None, measures=("accuracy",
     [0, d] is legal.  hist_fn(x_local, y_local, forest) -> table: the local
     step (tests inject the restatement; None: the HIP kernel, with x_local an
     array or a PoolState)."""
-    from . import metrics
-
-    names = metrics.check_measures(measures, forest.n_classes)
-    buf = _shard_table(hist_fn or _device_table, x_local, y_local, forest).clone()
-    comm.dist.all_reduce(buf, group=comm.group)  # SUM
-    return metrics.finish(buf.cpu().numpy(), forest.n_trees, forest.n_classes, names)
+    return _evaluate([(x_local, y_local)], forest, _GroupOps(comm), hist_fn, measures)[0]
 
 
 def emulate_evaluate(shards, forest, hist_fn=None, measures=("accuracy",)):
-    """evaluate with P shards [(x, y), ...] in one process (tests): the
-    all_reduce becomes an elementwise sum over the shards."""
-    from . import metrics
-
-    names = metrics.check_measures(measures, forest.n_classes)
-    fn = hist_fn or _device_table
-    buf = None
-    for x, y in shards:
-        t = _shard_table(fn, x, y, forest)
-        buf = t.clone() if buf is None else buf + t.to(buf.device)
-    return metrics.finish(buf.cpu().numpy(), forest.n_trees, forest.n_classes, names)
+    """evaluate with P shards [(x, y), ...] in one process (tests).  The P
+    jobs must agree; their one dict is returned."""
+    dicts = _evaluate(list(shards), forest, _LocalOps(), hist_fn, measures)
+    return _agreed(dicts, lambda d: [(name, np.asarray(v).tobytes()) for name, v in sorted(d.items())], "measures")
 
 
 # --------------------------------------------------------- forest training --
-class _GroupOps:
-    """The collectives of a sharded fit over a real group (one local job)."""
-
-    def __init__(self, comm):
-        self.comm = comm
-
-    def reduce(self, tensors, op: str):
-        dist = self.comm.dist
-        ops = {"sum": dist.ReduceOp.SUM, "min": dist.ReduceOp.MIN, "max": dist.ReduceOp.MAX}
-        dist.all_reduce(tensors[0], op=ops[op], group=self.comm.group)  # in place, stream-ordered
-        return tensors
-
-    def gather_rows(self, tensors):
-        """Every rank's rows [c_r, w] as one [sum c_r, w]: the counts first,
-        then the rows padded to the largest count."""
-        torch = __import__("torch")
-        t = tensors[0]
-        counts = self.comm.all_gather(torch.tensor([t.shape[0]], dtype=torch.int64, device=t.device)).cpu().tolist()
-        top = max(counts)
-        pad = torch.zeros((top,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
-        pad[:t.shape[0]] = t
-        got = self.comm.all_gather(pad).reshape((len(counts), top) + tuple(t.shape[1:]))
-        return [torch.cat([got[r, :c] for r, c in enumerate(counts)])]
-
-    def gather_row(self, rows):
-        """One int64 row per rank as [P, w] (TorchComm.all_gather_rows: stream-ordered, no host read)."""
-        return [self.comm.all_gather_rows(rows[0])]
-
-
-class _LocalOps:
-    """The same collectives over P jobs in one process (emulate_*)."""
-
-    def reduce(self, tensors, op: str):
-        torch = __import__("torch")
-        stack = torch.stack([t.to(tensors[0].device) for t in tensors])
-        red = {"sum": stack.sum(dim=0), "min": stack.amin(dim=0), "max": stack.amax(dim=0)}[op]
-        return [red.to(dtype=t.dtype, device=t.device) for t in tensors]
-
-    def gather_rows(self, tensors):
-        torch = __import__("torch")
-        return [torch.cat([t.to(u.device) for t in tensors]) for u in tensors]
-
-    def gather_row(self, rows):
-        torch = __import__("torch")
-        return [torch.stack([t.to(u.device) for t in rows]) for u in rows]
-
-
 def _sharded_fit(regress: bool, shards, n_total: int, ops, steps, num_trees, max_depth, max_bins, seed,
                  feature_subset_strategy, weights, feature_subsets, min_instances_per_node, min_info_gain,
                  num_classes=2, tree_chunk=None):
@@ -1176,11 +1184,7 @@ def _sharded_fit(regress: bool, shards, n_total: int, ops, steps, num_trees, max
 def _same_model(models, regress: bool):
     """emulate_*: every job must have grown the same forest."""
     names = ("inner_feature", "inner_threshold", "leaf") if regress else ("inner", "leaf")
-    for m in models[1:]:
-        for a in names:
-            if getattr(m, a).tobytes() != getattr(models[0], a).tobytes():
-                raise RuntimeError(f"the shards' fits differ in {a}")
-    return models[0]
+    return _agreed(models, lambda m: [getattr(m, a).tobytes() for a in names], "fits")
 
 
 def train_classifier(x_local, y_local, positions, n_total: int, comm, num_trees: int = 10, max_depth: int = 4,
@@ -1361,14 +1365,9 @@ def _same_selection(sels):
     from .engine import Selection
 
     torch = __import__("torch")
-    first = sels[0]
-    ranked = hasattr(first, "selected_similarity")
-    for s in sels[1:]:
-        if not (torch.equal(s.indices.cpu(), first.indices.cpu())
-                and torch.equal(s.selected_scores.cpu().view(torch.int64), first.selected_scores.cpu().view(torch.int64))
-                and (not ranked or torch.equal(s.selected_similarity.cpu().view(torch.int64),
-                                               first.selected_similarity.cpu().view(torch.int64)))):
-            raise RuntimeError("the shards' k-center selections differ")
+    ranked = hasattr(sels[0], "selected_similarity")
+    picks = ("indices", "selected_scores") + (("selected_similarity",) if ranked else ())
+    first = _agreed(sels, lambda s: [getattr(s, a).cpu().numpy().tobytes() for a in picks], "k-center selections")
     sel = Selection(scores=torch.cat([s.scores.to(first.scores.device) for s in sels]), indices=first.indices,
                     selected_scores=first.selected_scores)
     if ranked:

@@ -342,3 +342,102 @@ def test_sharded_exclude(cuda, world):
         idx, sc = parallel.emulate(sels, unl, ref.F, K, mode="dw")
         assert np.array_equal(_np(idx), sel_ref[0]) and np.array_equal(_bits(sc), _bits(sel_ref[1]))
     _same_selection(dw.select(one, unl, ref.F, K), sel_ref)
+
+
+SHARDED_DELTA = [12, 511, 512, 700, 1023, 1024, 1290, 1499, 1499, 3]  # test_sharded_exclude's, n = 1,500
+BIG_N, BIG_D, BIG_K = 5000, 64, 40                                     # test_gpu_multiprocess.py's pool
+BIG_DELTA = np.arange(50, BIG_N, 4)                                    # 1,238 new rows: two downdate chunks
+
+
+def _pair(idx, sc):
+    return _np(idx), _np(sc)
+
+
+def _exclude_rank(rank, world):
+    """parallel.exclude on one of two ranks sharing cuda:0 (collectives over
+    gloo, counted).  Rank 0 also runs the big delta through emulate_exclude
+    over the same two shards and through the single-device PoolState.exclude."""
+    import torch
+
+    from dal import density_weighting as dw
+    from dal import parallel
+    from sharded_comm import CountingComm
+
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    comm = CountingComm()
+    out = {}
+
+    def shard(X, n, r, **kw):
+        lo, hi, _ = parallel.shard_range(n, world, r)
+        return parallel.ShardedSelector(X[lo:hi], n, r, world, excluded=E0, device=dev, **kw)
+
+    # -- the 1,500 x 30 pool: a delta over both shards with a repeat and a member of E
+    ref = _ref("synthetic_1500x30_T100.npz")
+    n = ref.n
+    sel = shard(ref.X, n, rank)
+    parallel.select(sel, comm, np.arange(10, n), ref.F, K, mode="dw")  # the cold step: density cached
+    addr = sel._density.data_ptr()
+    comm.take()
+    out["new"] = parallel.exclude(sel, comm, SHARDED_DELTA)
+    out["warm_counts"] = comm.take()
+    out["plans"] = dict(sel._plans)
+    out["again"] = parallel.exclude(sel, comm, SHARDED_DELTA)
+    out["again_counts"] = comm.take()
+    out["in_place"] = sel._density.data_ptr() == addr
+    unl = np.setdiff1d(np.arange(n), np.union1d(E0, SHARDED_DELTA))
+    out["next"] = [_pair(*parallel.select(sel, comm, unl, ref.F, K, mode="dw")) for _ in range(2)]
+    comm.take()
+    out["cold_new"] = parallel.exclude(shard(ref.X, n, rank), comm, [20, 21, 3])  # no cached density
+    out["cold_counts"] = comm.take()
+    # -- more new rows than one downdate takes: the chunk loop runs twice
+    X = O.synthetic_pool(BIG_N, BIG_D, seed=21)
+    F = Forest.synthetic(10, 4, BIG_D, seed=1)
+    unl = np.setdiff1d(np.arange(BIG_N), np.union1d(E0, BIG_DELTA))
+    sel = shard(X, BIG_N, rank)
+    parallel.select(sel, comm, np.arange(10, BIG_N), F, BIG_K, mode="dw")
+    comm.take()
+    out["big_new"] = parallel.exclude(sel, comm, BIG_DELTA)
+    out["big_counts"] = comm.take()
+    out["big"] = _pair(*parallel.select(sel, comm, unl, F, BIG_K, mode="dw"))
+    if rank == 0:
+        sels = [shard(X, BIG_N, r) for r in range(world)]
+        parallel.emulate(sels, np.arange(10, BIG_N), F, BIG_K, mode="dw")
+        out["big_emulated_new"] = parallel.emulate_exclude(sels, BIG_DELTA)
+        out["big_emulated"] = _pair(*parallel.emulate(sels, unl, F, BIG_K, mode="dw"))
+        from dal.engine import PoolState
+
+        one = PoolState(X, excluded=E0, device=dev)
+        one.density_fixed()
+        one.colsum()
+        out["big_one_new"] = one.exclude(BIG_DELTA)
+        s = dw.select(one, unl, F, BIG_K)
+        out["big_one"] = _pair(s.indices, s.selected_scores)
+    return out
+
+
+def test_exclude_on_two_ranks(cuda):
+    """parallel.exclude over a real group: counts, the density lowered in
+    place, the plans dropped, the next selections the reference's bytes; a
+    delta of two chunks equals emulate_exclude's and the single device's step;
+    one all-gather per chunk and one of the partials when warm, none cold."""
+    from sharded_comm import run_ranks
+
+    ref = _ref("synthetic_1500x30_T100.npz")
+    assert ref.n == 1500
+    union = np.union1d(E0, SHARDED_DELTA)
+    _, _, sel_ref, _ = ref.at(union.tobytes())
+    assert BIG_DELTA.size > _lib.DAL_DOWNDATE_MAX_ROWS and BIG_DELTA.size <= 2 * _lib.DAL_DOWNDATE_MAX_ROWS
+    res = run_ranks(_exclude_rank, 2)
+    for out in res:
+        assert out["new"] == union.size - E0.size and out["again"] == 0
+        assert out["warm_counts"] == (2, 0) and out["again_counts"] == (0, 0)  # one chunk + the partials
+        assert out["in_place"] and out["plans"] == {}
+        for idx, sc in out["next"]:
+            assert np.array_equal(idx, sel_ref[0]) and np.array_equal(_bits(sc), _bits(sel_ref[1]))
+        assert out["cold_new"] == 2 and out["cold_counts"] == (0, 0)
+        assert out["big_new"] == BIG_DELTA.size and out["big_counts"] == (3, 0)  # two chunks + the partials
+        for name in ("big_emulated", "big_one"):
+            assert res[0][name + "_new"] == BIG_DELTA.size
+            assert np.array_equal(out["big"][0], res[0][name][0]), name
+            assert np.array_equal(_bits(out["big"][1]), _bits(res[0][name][1])), name

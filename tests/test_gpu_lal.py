@@ -355,6 +355,48 @@ def test_emulate_lal_matches_single_gpu(cuda, P):
     assert L.bits_equal(got_sc.cpu().numpy(), sel_sc)
 
 
+def _lal_rank(rank, world):
+    """parallel.select_lal on one of two ranks sharing cuda:0 (collectives
+    over gloo), its collectives counted; rank 0 also runs the single-device
+    step and emulate_lal over the same two shards."""
+    import torch
+
+    from dal import parallel
+    from dal.active_learner import select_lal
+    from sharded_comm import CountingComm
+
+    T, TR, k = 10, _regressor_sizes()[1], 10
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    X, unl = _pool()
+    args = (unl, _classifier(T), _lal_model(TR), k, N_LABELED, N_POSITIVE)
+    shards = [parallel.shard_range(N_POOL, world, r)[:2] for r in range(world)]
+    lo, hi = shards[rank]
+    comm = CountingComm()
+    idx, sc = parallel.select_lal(parallel.ShardedSelector(X[lo:hi], N_POOL, rank, world, device=dev), comm, *args)
+    out = {"counts": comm.take(), "ranks": (idx.cpu().numpy(), sc.cpu().numpy())}
+    if rank == 0:
+        one = select_lal(X, *args, device=dev)
+        out["one"] = (one.indices.cpu().numpy(), one.selected_scores.cpu().numpy())
+        sels = [parallel.ShardedSelector(X[a:b], N_POOL, r, world, device=dev) for r, (a, b) in enumerate(shards)]
+        idx, sc = parallel.emulate_lal(sels, *args)
+        out["emulated"] = (idx.cpu().numpy(), sc.cpu().numpy())
+    return out
+
+
+def test_select_lal_on_two_ranks(cuda):
+    """parallel.select_lal over a real group: the single-device selection and
+    emulate_lal's, byte for byte, with one all-reduce and one all-gather."""
+    from sharded_comm import run_ranks
+
+    res = run_ranks(_lal_rank, 2)
+    for name in ("one", "emulated"):
+        for out in res:
+            assert np.array_equal(out["ranks"][0], res[0][name][0]), name
+            assert L.bits_equal(out["ranks"][1], res[0][name][1]), name
+    assert [out["counts"] for out in res] == [(1, 1), (1, 1)]
+
+
 # ------------------------------------------------------- predict_regression
 def test_predict_regression(cuda):
     from dal import engine

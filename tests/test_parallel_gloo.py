@@ -58,6 +58,12 @@ class OracleShard(parallel.ShardedSelector):
     def exchange_density(self, comm, u_local, parts=None):
         return comm.all_gather(u_local), (comm.all_gather(parts) if parts is not None else None)
 
+    def density_contribution(self, u_full):  # (local_select takes the density from the gathered partials)
+        return None
+
+    def set_density(self, acc_local):
+        pass
+
     def index_tensor(self, unl):
         return torch.as_tensor(np.asarray(unl), dtype=torch.int64)
 
@@ -175,6 +181,75 @@ def test_gloo_sharded_density_select_matches_oracle(world, case):
         assert np.array_equal(idx, ref_idx), rank
         assert np.array_equal(sc, ref_sc), rank
         assert retries == (1 if case == "retry" else 0), (rank, retries)
+
+
+@pytest.mark.parametrize("world,case", [(2, "all"), (3, "all"), (4, "holes"), (8, "holes"), (8, "retry")])
+def test_emulate_runs_the_ranks_code_over_oracle_shards(world, case):
+    """parallel.emulate over the same OracleShards (no process, no .state):
+    the emulator and the gloo ranks above are one code path, retry included."""
+    X = O.synthetic_pool(N, D, seed=4)
+    of = O.synthetic_forest(10, 4, D, seed=1)
+    sels = [OracleShard(X, N, r, world, np.arange(10), of) for r in range(world)]
+    sels[world - 2].overflow_once = case == "retry"
+    idx, sc = parallel.emulate(sels, _unlabeled(case), None, K, mode="dw", sort_fn=_cpu_sort_positions)
+    _, ref_idx, ref_sc = O.density_select(X, _unlabeled(case), of, K, 1.0, np.arange(10))
+    assert np.array_equal(idx.numpy(), ref_idx)
+    assert sc.numpy().tobytes() == ref_sc.tobytes()
+    assert [getattr(s, "retries", 0) for s in sels] == [1 if case == "retry" else 0] * world
+
+
+class _UncertaintyShard(OracleShard):
+    """Mode "us" gathers no partials: the oracle step runs with zero ones
+    (every score 0; only the collectives are counted)."""
+
+    def local_select(self, u_full, parts_full, *args, **kwargs):
+        return super().local_select(u_full, torch.zeros((1, D), dtype=torch.float64), *args, **kwargs)
+
+
+def _count_run(rank, world):
+    import metrics_reference as MR
+    from sharded_comm import CountingComm
+    from test_metrics_host import BINARY, _cuts, _shard_case
+    from test_scaler_host import _gloo_pool, _restated_steps
+
+    X = O.synthetic_pool(N, D, seed=4)
+    of = O.synthetic_forest(10, 4, D, seed=1)
+    comm = CountingComm()
+    unl = _unlabeled("all")
+    out = {}
+    sel = OracleShard(X, N, rank, world, np.arange(10), of)
+    cold = parallel.select(sel, comm, unl, None, K, mode="dw", sort_fn=_cpu_sort_positions)
+    out["dw_cold"] = comm.take()
+    sel._density = True  # a double that marks its density cached (the partials are, since the cold step)
+    warm = parallel.select(sel, comm, unl, None, K, mode="dw", sort_fn=_cpu_sort_positions)
+    out["dw_warm"] = comm.take()
+    out["warm_equals_cold"] = all(torch.equal(a, b) for a, b in zip(cold, warm))
+    parallel.select(_UncertaintyShard(X, N, rank, world, np.arange(10), of), comm, unl, None, K, mode="us",
+                    sort_fn=_cpu_sort_positions)
+    out["us"] = comm.take()
+    P = _gloo_pool()
+    parallel.fit_scaler(torch.from_numpy(P[[0, 301][rank]:[301, 700][rank]]), comm, accumulate_fn=_restated_steps)
+    out["fit_scaler"] = comm.take()
+    Xe, ye, F = _shard_case()
+    c = _cuts(world)
+    parallel.evaluate(torch.from_numpy(Xe[c[rank]:c[rank + 1]]), torch.from_numpy(ye[c[rank]:c[rank + 1]]), F, comm,
+                      hist_fn=MR.hist_fn, measures=BINARY)
+    out["evaluate"] = comm.take()
+    return out
+
+
+def test_collectives_per_step():
+    """(all-gathers, all-reduces) of one call on each of two gloo ranks: a
+    cold density step gathers the operand, the partials and the top-k; a warm
+    one, and uncertainty sampling, the top-k alone."""
+    from sharded_comm import run_ranks
+
+    for out in run_ranks(_count_run, 2):
+        assert out["dw_cold"] == (3, 0)
+        assert out["dw_warm"] == (1, 0) and out["warm_equals_cold"]
+        assert out["us"] == (1, 0)
+        assert out["fit_scaler"] == (0, 3)
+        assert out["evaluate"] == (0, 1)
 
 
 def test_shard_ranges_cover_pool():

@@ -269,12 +269,9 @@ def test_run_loop_soft_votes_arguments_and_restatement():
 
 
 class _HostState:
-    """What parallel.emulate reads of a shard's PoolState."""
+    """What ShardedSelector.status_word reads of a shard's PoolState."""
 
     status = torch.zeros(1, dtype=torch.int32)
-
-    def check_status(self):
-        pass
 
 
 class RestatementShard(parallel.ShardedSelector):
@@ -286,6 +283,9 @@ class RestatementShard(parallel.ShardedSelector):
         self.x = X[self.lo:self.hi]
         self.state = _HostState()
         self._density = None
+
+    def index_tensor(self, unl):
+        return torch.as_tensor(np.asarray(unl), dtype=torch.int64)
 
     def local_select(self, u_full, parts_full, unl, forest, k, mode="dw", strategy="least_confidence", beta=1.0,
                      density_mode="gram", warm=None):
