@@ -240,6 +240,33 @@ int forest_multiclass_step_launch_rowmajor(const McStepScore& S, const uint8_t* 
                                            uint64_t* keys, uint64_t* keys_hi, const ForestStepHooks& hooks,
                                            hipStream_t st);
 
+// The soft-vote score of dal_dw_step_soft: dal_forest_score_soft_dw's operands
+// (DAL_DENSITY_FIXED) without the buffers the selection shares with the other
+// steps (row flags, scores, keys).
+struct SoftStepScore {
+  const float* x;
+  int64_t n, d, ldx;
+  const int32_t* inner;
+  const int32_t* leaf_id;
+  const uint32_t* leaf_q;
+  int64_t n_leaves;
+  int32_t n_trees, depth, n_classes;
+  const int64_t* density_fixed;
+  double density_err, beta;
+  uint64_t* sums;  // nullable
+  uint8_t* pred;   // nullable
+  double* entropy;
+  int32_t* row_index;
+};
+// The score entry's checks (forest_soft.hip, soft_validate), before n == 0;
+// args_ok: the caller's own operand tests.
+int forest_soft_step_check(const SoftStepScore& S, bool args_ok);
+// Rows per block of the soft-vote kernel for this shape.
+int forest_soft_rows_per_block(const float* x, int64_t d, int64_t ldx, int32_t n_trees);
+// The launch with the step's status hook (no plan flags, no group fold).
+int forest_soft_step_launch(const SoftStepScore& S, const uint8_t* row_flags, double* scores, uint64_t* keys,
+                            uint64_t* keys_hi, const ForestStepHooks& hooks, hipStream_t st);
+
 // dal_dw_step with the plan's publishing hooks (topk.hip, SortTail): the
 // selection is also written to *out_slot (a host-mapped word holding a device
 // address; nullable) and the final status word to *status_mirror (host-mapped).

@@ -29,7 +29,17 @@
 // The staging loops are this kernel's own copies of the forms of
 // forest_multi_body.inc (the existing kernels are held to the instructions
 // they have; forest_shared.hpp is included unchanged).
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // (the shared header's pow helpers: unused here)
+//
+// The density-weighted form (DW; dal_forest_score_soft_dw, and under
+// dal_dw_step_soft) is modAL's information density on predict_proba: the same
+// walk, accumulators, staging and entropy (forest_soft_body.inc, one text for
+// both kernels), and a row-leader epilogue that multiplies the class entropy
+// by density^beta and writes the interval keys of the hard-vote density
+// kernels, plus the row's entropy and its own index, so that dal_dw_select
+// (lut = entropy, votes = index) re-ranks it unchanged.  The row leader's
+// density word is loaded with its flags when the tile is staged; the
+// epilogue's fp64 temporaries exist after the cross-lane sum only.  The DW =
+// false kernels are the code they were without it.
 #include "forest_shared.hpp"
 
 namespace dal {
@@ -59,6 +69,23 @@ struct SoftArgs {
   uint8_t* pred;
   double* scores;
   uint64_t* keys;
+};
+
+// The density-weighted form (dal_forest_score_soft_dw): the class entropy
+// times density^beta with interval keys, the density epilogue of the hard-vote
+// kernels (forest_shared.hpp, row_epilogue<.., DW = true, POW>) on the
+// soft-vote entropy.  Its arguments extend SoftArgs (kind = DAL_SOFT_ENTROPY,
+// order = DAL_DESCENDING, keys = the pessimistic keys), so the uncertainty
+// form's kernels take the struct they always took.
+struct SoftDwArgs : SoftArgs {
+  const void* density;  // int64 fixed point (DAL_DENSITY_FIXED) or fp64 bits (DAL_DENSITY_EXACT), one word per row
+  int dkind;
+  double derr;
+  double beta;
+  double* entropy;
+  int32_t* row_index;
+  uint64_t* keys_hi;      // nullable
+  int32_t* status_reset;  // nullable; dal_dw_step_soft: zeroed by the grid's first thread
 };
 
 // Words per leaf row of the LDS copy of the leaf table: C rounded up to even,
@@ -114,10 +141,11 @@ __device__ __forceinline__ double soft_entropy(const unsigned long long (&s)[W],
 }
 
 // The row leader's epilogue: s holds the row's C class sums, entropy the
-// row's class entropy (DAL_SOFT_ENTROPY only).
-template <int W>
-__device__ __forceinline__ void soft_epilogue(const SoftArgs& A, const unsigned long long (&s)[W], int64_t row,
-                                              uint8_t fl, double M, double entropy) {
+// row's class entropy (DAL_SOFT_ENTROPY only; DW: always).  DW: dens_pre, the
+// row's density word, loaded with its flags.
+template <int W, bool DW, bool POW, class Args>
+__device__ __forceinline__ void soft_epilogue(const Args& A, const unsigned long long (&s)[W], int64_t row,
+                                              uint8_t fl, long long dens_pre, double M, double entropy) {
   const int C = A.n_classes;
   // largest and second-largest sum, the lowest class holding the largest
   long long m1 = -1, m2 = -1;
@@ -135,9 +163,12 @@ __device__ __forceinline__ void soft_epilogue(const SoftArgs& A, const unsigned 
       }
     }
   }
-  const double score = A.kind == DAL_SOFT_ENTROPY
-                           ? entropy
-                           : __ddiv_rn(static_cast<double>(A.kind == DAL_SOFT_MARGIN ? m1 - m2 : m1), M);
+  double score = entropy;  // DW: times density^beta below
+  if constexpr (!DW) {
+    score = A.kind == DAL_SOFT_ENTROPY
+                ? entropy
+                : __ddiv_rn(static_cast<double>(A.kind == DAL_SOFT_MARGIN ? m1 - m2 : m1), M);
+  }
   if (A.sums) {
     unsigned long long* sr = A.sums + row * C;
 #pragma unroll
@@ -145,18 +176,47 @@ __device__ __forceinline__ void soft_epilogue(const SoftArgs& A, const unsigned 
       if (c < C) sr[c] = s[c];
   }
   if (A.pred) A.pred[row] = static_cast<uint8_t>(arg);
-  A.scores[row] = score;
-  A.keys[row] = (fl & DAL_ROW_CANDIDATE) ? score_key(score, A.order) : DAL_KEY_NONE;
+  if constexpr (DW) {
+    // the hard-vote kernels' density epilogue (forest_shared.hpp) on the class
+    // entropy e (never NaN, >= +0.0): score = e d^beta, descending, and for
+    // the GEMM density the interval score -+ e err(d^beta) as two keys
+    const double e = entropy;
+    double d = A.dkind == DAL_DENSITY_FIXED ? from_fixed(dens_pre) : __builtin_bit_cast(double, dens_pre);
+    if (fl & DAL_ROW_EXCLUDED) d = __builtin_nan("");
+    score = e * density_pow_if<POW>(d, A.beta);
+    double err = 0.0;
+    if (A.dkind == DAL_DENSITY_FIXED && e != 0.0 && d == d) {
+      err = e * density_pow_err_if<POW>(d, A.derr, A.beta);
+      // keep the interval ends distinct from the score after rounding
+      err = fmax(err, fabs(score) * 4.5e-16);
+    }
+    unsigned long long klo = DAL_KEY_NONE, khi = DAL_KEY_NONE;
+    if (fl & DAL_ROW_CANDIDATE) {
+      klo = score_key(pessimistic(score, err, DAL_DESCENDING), DAL_DESCENDING);
+      khi = score_key(optimistic(score, err, DAL_DESCENDING), DAL_DESCENDING);
+    }
+    A.entropy[row] = e;
+    A.row_index[row] = static_cast<int32_t>(row);  // (n <= INT32_MAX, checked by the entry)
+    A.scores[row] = score;
+    A.keys[row] = klo;
+    if (A.keys_hi) A.keys_hi[row] = khi;
+  } else {
+    A.scores[row] = score;
+    A.keys[row] = (fl & DAL_ROW_CANDIDATE) ? score_key(score, A.order) : DAL_KEY_NONE;
+  }
 }
 
 // Sums, prediction, score and key of tile `tile` (R rows from LDS or global
 // memory): the walks, the cross-lane integer sum, then the row leader's
-// epilogue.  fl_pre: the row leader's flags, loaded with the tile.  qstride:
+// epilogue.  fl_pre: the row leader's flags, loaded with the tile; DW:
+// dens_pre, its density word, loaded with them (the epilogue's fp64
+// temporaries exist on the row leader after the cross-lane sum only).  qstride:
 // words per leaf row of leaf_q (the LDS copy's padded row, or C).
-template <int W, bool X_LDS, bool F_LDS>
-__device__ __forceinline__ void score_tile_soft(const SoftArgs& A, const float* xs, int xstride, int64_t tile, int R,
+template <int W, bool X_LDS, bool F_LDS, bool DW, bool POW, class Args>
+__device__ __forceinline__ void score_tile_soft(const Args& A, const float* xs, int xstride, int64_t tile, int R,
                                                 int tpr, const int2* inner, const int32_t* leaf_id,
-                                                const uint32_t* leaf_q, int qstride, uint8_t fl_pre) {
+                                                const uint32_t* leaf_q, int qstride, uint8_t fl_pre,
+                                                long long dens_pre) {
   const int n_inner = (1 << A.depth) - 1;
   const int n_leaf = 1 << A.depth;
   const int tid = threadIdx.x;
@@ -212,9 +272,24 @@ __device__ __forceinline__ void score_tile_soft(const SoftArgs& A, const float* 
   }
   const double M = static_cast<double>(A.n_trees) * 2147483648.0;  // T 2^31, exact
   double entropy = 0.0;
-  if (A.kind == DAL_SOFT_ENTROPY) entropy = soft_entropy<W>(s, A.n_classes, tpr, sub, M);  // (block-uniform)
+  if (DW || A.kind == DAL_SOFT_ENTROPY) entropy = soft_entropy<W>(s, A.n_classes, tpr, sub, M);  // (block-uniform)
   if (!(live && sub == 0)) return;
-  soft_epilogue<W>(A, s, row, fl_pre, M, entropy);
+  soft_epilogue<W, DW, POW>(A, s, row, fl_pre, dens_pre, M, entropy);
+}
+
+// What the body (forest_soft_body.inc) does for the density-weighted form
+// alone, on its argument struct (nothing for SoftArgs): the step's status
+// reset by the grid's first thread, and a row's density word.
+template <bool DW, class Args>
+__device__ __forceinline__ void soft_reset_status(const Args& A) {
+  if constexpr (DW) {
+    if (A.status_reset && blockIdx.x == 0 && threadIdx.x == 0) *A.status_reset = 0;
+  }
+}
+template <bool DW, class Args>
+__device__ __forceinline__ long long soft_density_word(const Args& A, int64_t row) {
+  if constexpr (DW) return static_cast<const long long*>(A.density)[row];
+  else return 0;
 }
 
 // One block per tile (grid = tiles), or PERSIST (LDS-DMA staging only; grid =
@@ -224,112 +299,32 @@ __device__ __forceinline__ void score_tile_soft(const SoftArgs& A, const float* 
 template <int W, bool X_LDS, bool F_LDS, bool PERSIST>
 __global__ __launch_bounds__(kSoftThreads) void forest_soft_kernel(SoftArgs A, int R, int tpr, int x_floats, bool vec4,
                                                                    bool pad4, bool dma, int64_t n_tiles) {
-  static_assert(!PERSIST || X_LDS, "the persistent form stages rows by LDS-DMA");
-  if (PERSIST) {
-    dma = true;
-    vec4 = false;
-    pad4 = true;
-  }
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* xs = reinterpret_cast<float*>(smem);
-  const int n_inner = (1 << A.depth) - 1;
-  const int n_leaf = 1 << A.depth;
-  const int2* inner = A.inner;
-  const int32_t* leaf_id = A.leaf_id;
-  const uint32_t* leaf_q = A.leaf_q;
-  int qstride = A.n_classes;
-  const int tid = threadIdx.x;
-  if (F_LDS) {
-    // (x_floats % 4 == 0: the nodes start 16-B aligned)
-    int2* fs = reinterpret_cast<int2*>(smem + static_cast<size_t>(x_floats) * 4);
-    int32_t* ls = reinterpret_cast<int32_t*>(fs + A.n_trees * n_inner);
-    const size_t q_off = static_cast<size_t>(
-        round_up(static_cast<int64_t>(x_floats) * 4 + static_cast<int64_t>(A.n_trees) * (n_inner * 8 + n_leaf * 4), 16));
-    uint32_t* qs = reinterpret_cast<uint32_t*>(smem + q_off);
-    qstride = soft_lds_stride(A.n_classes);
-    for (int e = tid; e < A.n_trees * n_inner; e += kSoftThreads) fs[e] = A.inner[e];
-    for (int e = tid; e < A.n_trees * n_leaf; e += kSoftThreads) ls[e] = A.leaf_id[e];
-    for (int e = tid; e < A.n_leaves * qstride; e += kSoftThreads) {
-      const int l = e / qstride, c = e - l * qstride;
-      qs[e] = c < A.n_classes ? A.leaf_q[l * A.n_classes + c] : 0u;
-    }
-    inner = fs;
-    leaf_id = ls;
-    leaf_q = qs;
-  }
-  // row stride in LDS: d + 1 words for scalar staging; d + 4 with 16-B staging
-  // (rows stay 16-B aligned, rows of a wave start 4 banks apart)
-  const int xstride = A.d + (pad4 ? 4 : 1);
-  const int r = tid / tpr;  // (the row / tree-phase mapping of score_tile_soft)
-  const int sub = tid - r * tpr;
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {  // block-uniform
-    const int64_t row0 = tile * R;
-    const int64_t row = row0 + r;
-    const bool live = r < R && row < A.n;
-    // the row leader's flags are loaded with the tile (one HBM latency per tile)
-    uint8_t fl_pre = DAL_ROW_CANDIDATE;
-    if (A.flags && live && sub == 0) fl_pre = A.flags[row];
-    if (X_LDS) {
-      const int rows_here = static_cast<int>(min(static_cast<int64_t>(R), A.n - row0));
-      if (dma) {
-        // LDS-DMA staging (d % 4 == 0, 16-B-aligned padded rows): one
-        // global_load_lds_dwordx4 per 1 KiB of a row (the last piece with only
-        // the lanes it needs), lane l's 16 B landing at M0 + 16 l
-        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-        const int row_bytes = A.d * 4;
-        for (int rr = wave; rr < rows_here; rr += kSoftThreads / 64) {
-          const float* src = A.x + (row0 + rr) * A.ldx;
-          for (int p = 0; p * 1024 < row_bytes; ++p) {
-            typedef __attribute__((address_space(3))) float lds_float;
-            const unsigned dst = __builtin_amdgcn_readfirstlane(
-                static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_float*)(xs + rr * xstride + p * 256))));
-            const unsigned voff = static_cast<unsigned>(p * 1024 + lane * 16);
-            if (static_cast<int>(voff) < row_bytes) lds_dma_x4(voff, dst, src);
-          }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      } else if (vec4) {
-        // 16-B loads, kStageBatch per thread issued before any LDS write
-        constexpr int kStageBatch = 8;
-        const int q = A.d >> 2, total = rows_here * q;
-        for (int e0 = 0; e0 < total; e0 += kSoftThreads * kStageBatch) {
-          typedef float v4f __attribute__((ext_vector_type(4)));
-          v4f v[kStageBatch];
-#pragma unroll
-          for (int j = 0; j < kStageBatch; ++j) {
-            const int e = e0 + j * kSoftThreads + tid;
-            if (e < total) {
-              const int rr = e / q, c = e - rr * q;
-              v[j] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(A.x + (row0 + rr) * A.ldx) + c);
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < kStageBatch; ++j) {
-            const int e = e0 + j * kSoftThreads + tid;
-            if (e < total) {
-              const int rr = e / q, c = e - rr * q;
-              *reinterpret_cast<v4f*>(xs + rr * xstride + 4 * c) = v[j];  // (vec4 implies pad4: 16-B aligned rows)
-            }
-          }
-        }
-      } else {
-        for (int e = tid; e < rows_here * A.d; e += kSoftThreads) {
-          const int rr = e / A.d, c = e - rr * A.d;
-          xs[rr * xstride + c] = A.x[(row0 + rr) * A.ldx + c];
-        }
-      }
-    }
-    __syncthreads();
-    score_tile_soft<W, X_LDS, F_LDS>(A, xs, xstride, tile, R, tpr, inner, leaf_id, leaf_q, qstride, fl_pre);
-    if (!PERSIST) break;
-    __syncthreads();  // every wave done with the tile before the next one is staged
-  }
+  constexpr bool DW = false, POW = false;
+#include "forest_soft_body.inc"
+}
+
+// The density-weighted form (dal_forest_score_soft_dw, dal_dw_step_soft): the
+// same body, the density epilogue on the row leader.
+template <int W, bool X_LDS, bool F_LDS, bool PERSIST, bool POW>
+__global__ __launch_bounds__(kSoftThreads) void forest_soft_dw_kernel(SoftDwArgs A, int R, int tpr, int x_floats,
+                                                                      bool vec4, bool pad4, bool dma,
+                                                                      int64_t n_tiles) {
+  constexpr bool DW = true;
+#include "forest_soft_body.inc"
+}
+
+// The kernel of a form.
+template <int W, bool XL, bool FL, bool PS, bool DW, bool POW>
+constexpr auto soft_kernel() {
+  if constexpr (DW) return &forest_soft_dw_kernel<W, XL, FL, PS, POW>;
+  else return &forest_soft_kernel<W, XL, FL, PS>;
 }
 
 // The row-major tiling rule of the hard-vote kernels (forest_shared.hpp,
-// forest_tiling).
-template <int W>
-int soft_launch(const SoftArgs& A, int64_t d, int64_t ldx, hipStream_t st) {
+// forest_tiling).  DW (Args = SoftDwArgs): the density-weighted kernels, POW
+// picked by beta -- the beta == 1 kernels hold no pow call.
+template <int W, bool DW, bool POW, class Args>
+int soft_launch(const Args& A, int64_t d, int64_t ldx, hipStream_t st) {
   const ForestTiling T = forest_tiling(A.x, d, ldx, A.n_trees, kSoftThreads);
   const int R = T.R, tpr = kSoftThreads / R;
   const int64_t blocks = ceil_div(A.n, R);
@@ -344,7 +339,7 @@ int soft_launch(const SoftArgs& A, int64_t d, int64_t ldx, hipStream_t st) {
   const size_t smem = static_cast<size_t>(xf) * 4 + (f_lds ? static_cast<size_t>(f_bytes) : 0);
 #define DAL_SOFT_LAUNCH(XL, FL, PS)                                                                          \
   do {                                                                                                       \
-    const auto kern = &forest_soft_kernel<W, XL, FL, PS>;                                                    \
+    const auto kern = soft_kernel<W, XL, FL, PS, DW, POW>();                                                 \
     const void* fn = reinterpret_cast<const void*>(kern);                                                    \
     int64_t grid = blocks;                                                                                   \
     if (PS) { /* a persistent grid of exactly the blocks resident at once */                                 \
@@ -368,7 +363,64 @@ int soft_launch(const SoftArgs& A, int64_t d, int64_t ldx, hipStream_t st) {
   return DAL_OK;
 }
 
+// f(std::integral_constant<int, W>{}) for the accumulator width of n_classes.
+template <class F>
+int dispatch_soft_width(int32_t n_classes, F&& f) {
+  if (n_classes <= 2) return f(std::integral_constant<int, 2>{});
+  if (n_classes <= 4) return f(std::integral_constant<int, 4>{});
+  if (n_classes <= 8) return f(std::integral_constant<int, 8>{});
+  if (n_classes <= 16) return f(std::integral_constant<int, 16>{});
+  return f(std::integral_constant<int, 32>{});
+}
+
+// What both soft-vote entries check, in the order they report it: DAL_ERR_ARG
+// (args_ok: the entry's own null-operand and enum tests) before DAL_ERR_SHAPE
+// before DAL_ERR_UNSUPPORTED.  index32: the entry writes int32 row indices.
+int soft_validate(bool args_ok, int64_t n, int64_t d, int64_t x_stride, int64_t n_leaves, int32_t n_trees,
+                  int32_t depth, int32_t n_classes, bool index32) {
+  if (!args_ok) return DAL_ERR_ARG;
+  if (n < 0 || d < 1 || x_stride < d || d > (int64_t{1} << 30) || n_leaves < 1 || n_leaves > kSoftMaxLeaves)
+    return DAL_ERR_SHAPE;
+  if (index32 && n > INT32_MAX) return DAL_ERR_SHAPE;  // row_index is int32 (dal_dw_select's vote type)
+  if (depth < 1 || depth > DAL_SOFT_MAX_DEPTH) return DAL_ERR_UNSUPPORTED;
+  if (n_classes < 2 || n_classes > DAL_SOFT_MAX_CLASSES) return DAL_ERR_UNSUPPORTED;
+  if (n_trees < 1 || n_trees > DAL_SOFT_MAX_TREES) return DAL_ERR_UNSUPPORTED;
+  return DAL_OK;
+}
+
+int soft_dw_launch(const SoftStepScore& S, const void* density, int density_kind, const uint8_t* row_flags,
+                   double* scores, uint64_t* keys, uint64_t* keys_hi, int32_t* status_reset, hipStream_t st) {
+  const SoftDwArgs A{{S.x, S.n, static_cast<int>(S.d), S.ldx, reinterpret_cast<const int2*>(S.inner), S.leaf_id,
+                      S.leaf_q, static_cast<int>(S.n_leaves), S.n_trees, S.depth, S.n_classes, DAL_SOFT_ENTROPY,
+                      row_flags, DAL_DESCENDING, reinterpret_cast<unsigned long long*>(S.sums), S.pred, scores, keys},
+                     density, density_kind, S.density_err, S.beta, S.entropy, S.row_index, keys_hi, status_reset};
+  return dispatch_soft_width(S.n_classes, [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    return S.beta == 1.0 ? soft_launch<W, true, false>(A, S.d, S.ldx, st)  // no pow, no call
+                         : soft_launch<W, true, true>(A, S.d, S.ldx, st);
+  });
+}
+
 }  // namespace
+
+int forest_soft_step_check(const SoftStepScore& S, bool args_ok) {
+  args_ok = args_ok && S.x && S.inner && S.leaf_id && S.leaf_q && S.density_fixed && S.entropy && S.row_index;
+  return soft_validate(args_ok, S.n, S.d, S.ldx, S.n_leaves, S.n_trees, S.depth, S.n_classes, true);
+}
+
+int forest_soft_rows_per_block(const float* x, int64_t d, int64_t ldx, int32_t n_trees) {
+  return forest_tiling(x, d, ldx, n_trees, kSoftThreads).R;
+}
+
+int forest_soft_step_launch(const SoftStepScore& S, const uint8_t* row_flags, double* scores, uint64_t* keys,
+                            uint64_t* keys_hi, const ForestStepHooks& hooks, hipStream_t st) {
+  // the status hook alone: no plan flags and no group fold in the soft kernel
+  if (hooks.gmin || hooks.base_flags) return DAL_ERR_ARG;
+  if (S.n == 0) return DAL_OK;
+  return soft_dw_launch(S, S.density_fixed, DAL_DENSITY_FIXED, row_flags, scores, keys, keys_hi, hooks.status_reset,
+                        st);
+}
+
 }  // namespace dal
 
 using namespace dal;
@@ -383,12 +435,7 @@ extern "C" int dal_forest_score_soft(const float* x, int64_t n, int64_t d, int64
   const bool args_ok =
       x && inner && leaf_id && leaf_q && scores && keys && (order == DAL_ASCENDING || order == DAL_DESCENDING) &&
       (score_kind == DAL_SOFT_LEAST_CONFIDENCE || score_kind == DAL_SOFT_MARGIN || score_kind == DAL_SOFT_ENTROPY);
-  if (!args_ok) return DAL_ERR_ARG;
-  if (n < 0 || d < 1 || x_stride < d || d > (int64_t{1} << 30) || n_leaves < 1 || n_leaves > kSoftMaxLeaves)
-    return DAL_ERR_SHAPE;
-  if (depth < 1 || depth > DAL_SOFT_MAX_DEPTH) return DAL_ERR_UNSUPPORTED;
-  if (n_classes < 2 || n_classes > DAL_SOFT_MAX_CLASSES) return DAL_ERR_UNSUPPORTED;
-  if (n_trees < 1 || n_trees > DAL_SOFT_MAX_TREES) return DAL_ERR_UNSUPPORTED;
+  if (const int rc = soft_validate(args_ok, n, d, x_stride, n_leaves, n_trees, depth, n_classes, false)) return rc;
   if (n == 0) return DAL_OK;
   const SoftArgs A{x,
                    n,
@@ -409,9 +456,22 @@ extern "C" int dal_forest_score_soft(const float* x, int64_t n, int64_t d, int64
                    scores,
                    keys};
   const hipStream_t st = as_stream(stream);
-  if (n_classes <= 2) return soft_launch<2>(A, d, x_stride, st);
-  if (n_classes <= 4) return soft_launch<4>(A, d, x_stride, st);
-  if (n_classes <= 8) return soft_launch<8>(A, d, x_stride, st);
-  if (n_classes <= 16) return soft_launch<16>(A, d, x_stride, st);
-  return soft_launch<32>(A, d, x_stride, st);
+  return dispatch_soft_width(n_classes, [&](auto w) {
+    return soft_launch<decltype(w)::value, false, false>(A, d, x_stride, st);
+  });
+}
+
+extern "C" int dal_forest_score_soft_dw(const float* x, int64_t n, int64_t d, int64_t x_stride, const int32_t* inner,
+                                        const int32_t* leaf_id, const uint32_t* leaf_q, int64_t n_leaves,
+                                        int32_t n_trees, int32_t depth, int32_t n_classes, const void* density,
+                                        int density_kind, double density_err, const uint8_t* row_flags, double beta,
+                                        uint64_t* sums, uint8_t* pred, double* entropy, int32_t* row_index,
+                                        double* scores, uint64_t* keys, uint64_t* keys_hi, dal_stream_t stream) {
+  const bool args_ok = x && inner && leaf_id && leaf_q && density && entropy && row_index && scores && keys &&
+                       (density_kind == DAL_DENSITY_FIXED || density_kind == DAL_DENSITY_EXACT);
+  if (const int rc = soft_validate(args_ok, n, d, x_stride, n_leaves, n_trees, depth, n_classes, true)) return rc;
+  if (n == 0) return DAL_OK;
+  const SoftStepScore S{x,     n,         d,       x_stride, inner, leaf_id, leaf_q,  n_leaves, n_trees,
+                        depth, n_classes, nullptr, density_err, beta, sums,   pred,    entropy,  row_index};
+  return soft_dw_launch(S, density, density_kind, row_flags, scores, keys, keys_hi, nullptr, as_stream(stream));
 }

@@ -2526,6 +2526,36 @@ extern "C" int dal_dw_step_multiclass(const float* x, const float* xb, const voi
                                  colsum_ready, stream, nullptr, nullptr, nullptr);
 }
 
+// One density-weighted iteration over a soft-vote forest: the soft kernel
+// (forest_soft.hip) under the same step.  As for the C-class step the re-rank's
+// "LUT" is the per-row entropy and its "vote" the row's own index; the kernel
+// does not fold, so the fast level 1 takes the group_min_kernel pass (form 1).
+extern "C" int dal_dw_step_soft(const float* x, int64_t n, int64_t d, int64_t x_stride, const int32_t* inner,
+                                const int32_t* leaf_id, const uint32_t* leaf_q, int64_t n_leaves, int32_t n_trees,
+                                int32_t depth, int32_t n_classes, const int64_t* density_fixed, double density_err,
+                                const uint8_t* row_flags, double beta, int64_t idx_base, const double* norm64,
+                                const double* colsum, int64_t k, int64_t cap, int32_t level1_passes,
+                                uint32_t step_flags, void* ws, size_t ws_bytes, uint64_t* sums, uint8_t* pred,
+                                double* entropy, int32_t* row_index, double* scores, uint64_t* keys_lo,
+                                uint64_t* keys_hi, int64_t* out_idx, double* out_scores, uint64_t* out_keys,
+                                int32_t* dev_status, dal_event_t colsum_ready, dal_stream_t stream) {
+  const SoftStepScore M{x,     n,         d,             x_stride,    inner, leaf_id, leaf_q, n_leaves, n_trees,
+                        depth, n_classes, density_fixed, density_err, beta,  sums,    pred,   entropy,  row_index};
+  const bool args_ok = norm64 && colsum && ws && scores && keys_lo && keys_hi && out_idx && out_scores &&
+                       dev_status && !(step_flags & ~static_cast<uint32_t>(DAL_STEP_RESET_STATUS | DAL_STEP_WS_CLEAN));
+  if (const int rc = forest_soft_step_check(M, args_ok)) return rc;
+  if (n == 0) return DAL_OK;
+  level1_passes = mc_step_passes(cap, level1_passes);
+  const StepScore sc{forest_soft_rows_per_block(x, d, x_stride, n_trees), false, entropy, row_index, 0};
+  const hipStream_t st = as_stream(stream);
+  auto launch = [&](const ForestStepHooks& hooks) {
+    return forest_soft_step_launch(M, row_flags, scores, keys_lo, keys_hi, hooks, st);
+  };
+  return dw_step_core(sc, launch, x, n, d, x_stride, row_flags, beta, idx_base, norm64, colsum, k, cap, level1_passes,
+                      step_flags, ws, ws_bytes, keys_lo, keys_hi, out_idx, out_scores, out_keys, dev_status,
+                      colsum_ready, stream, nullptr, nullptr, nullptr);
+}
+
 // Pure host code: the branch dal_dw_step_multiclass takes for this shape (the
 // values of step_form), or the negative status its shape checks give.
 // blocked: the call is given a blocked copy (and a prepared forest).

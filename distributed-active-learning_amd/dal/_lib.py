@@ -158,6 +158,15 @@ SIGNATURES = {
     "dal_forest_score_soft": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                       c_int32, c_int32, c_int32, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]),
+    "dal_forest_score_soft_dw": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                         c_int32, c_int32, c_int32, c_void_p, c_int, c_double, c_void_p, c_double,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
+    "dal_dw_step_soft": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                 c_int32, c_int32, c_int32, c_void_p, c_double, c_void_p, c_double, c_int64,
+                                 c_void_p, c_void_p, c_int64, c_int64, c_int32, ctypes.c_uint32, c_void_p, c_size_t,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dal_density_separable": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]),
     "dal_topk_workspace_bytes": (c_size_t, [c_int64, c_int64]),

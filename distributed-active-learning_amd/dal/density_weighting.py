@@ -21,8 +21,8 @@ from __future__ import annotations
 import numpy as np
 
 from ._lib import DAL_MC_MAX_TREES
-from .engine import PoolState, Selection, as_pool_state, density_step, multiclass_density_step
-from .forest import Forest
+from .engine import PoolState, Selection, as_pool_state, density_step, multiclass_density_step, soft_density_step
+from .forest import Forest, ProbabilityForest
 
 
 def information_density(pool, excluded_idx=None, device=None, mode: str = "gram"):
@@ -142,4 +142,27 @@ def select_multiclass(pool, unlabeled_idx, forest: Forest, k: int, beta: float =
     return multiclass_density_step(state, unlabeled_idx, forest, k, beta=beta, density_fixed=density, mode=mode)
 
 
-__all__ = ["information_density", "select", "select_multiclass", "PoolState", "Selection", "L0", "LABELED"]
+def select_soft(pool, unlabeled_idx, forest: ProbabilityForest, k: int, beta: float = 1.0, excluded_idx=L0,
+                density=None, device=None, mode: str = "gram", window_size=None) -> Selection:
+    """Score every unlabeled row by entropy(predict_proba) x density^beta and
+    select the top k: modAL's information density over a soft-voting forest.
+
+    score_i = H_i * d_i^beta, H_i the class-ordered entropy of the averaged
+    leaf class distributions S_c / (T 2^31) (dal.uncertainty_sampling's
+    soft-vote "entropy" score, the same bits); d_i the density of ``select``.
+    Descending, NaN last, ties to the lower index; the selection and
+    ``selected_scores`` are the canonical fp64 ones on the entropy the device
+    computed (within n_classes 2^-49 of the host's).  ``forest`` must be a
+    dal.forest.ProbabilityForest; a hard-voting Forest belongs to ``select``
+    (binary) or ``select_multiclass``.  The other arguments are those of
+    ``select``.  The Selection carries ``sums`` ([U, C] int64) and
+    ``proba()``; ``votes`` and ``counts`` are None."""
+    if not isinstance(forest, ProbabilityForest):
+        raise ValueError("select_soft scores a dal.forest.ProbabilityForest (soft votes): a hard-voting Forest "
+                         "belongs to select (binary) or select_multiclass")
+    state = _pool_state(pool, unlabeled_idx, k, excluded_idx, window_size, device)
+    return soft_density_step(state, unlabeled_idx, forest, k, beta=beta, density_fixed=density, mode=mode)
+
+
+__all__ = ["information_density", "select", "select_multiclass", "select_soft", "PoolState", "Selection", "L0",
+           "LABELED"]

@@ -919,6 +919,45 @@ def forest_score_soft(state: PoolState, forest, flags, order: int, kind: int):
     return sums, pred, scores, keys
 
 
+def forest_score_soft_dw(state: PoolState, forest, flags, density, density_kind: int, density_err: float = 0.0,
+                         beta: float = 1.0, want_hi: bool = True):
+    """Launch dal_forest_score_soft_dw over the shard: the soft-vote class
+    entropy (dal_forest_score_soft's, the same bits) x density^beta,
+    descending, with interval keys.  ``density``: one 8-byte word per row,
+    int64 fixed point (DAL_DENSITY_FIXED) or canonical fp64
+    (DAL_DENSITY_EXACT).  Returns (sums int64 [n, C], pred uint8 [n], entropy
+    fp64 [n], row_index int32 [n], scores, keys, keys_hi or None).  flags
+    None: every row is a candidate."""
+    torch = _torch()
+    forest.check_features(state.d)
+    if density_kind not in (DAL_DENSITY_FIXED, DAL_DENSITY_EXACT):
+        raise ValueError("density_kind must be DAL_DENSITY_FIXED or DAL_DENSITY_EXACT")
+    if density is None or int(density.shape[0]) < state.n or density.element_size() != 8:
+        raise ValueError("density must hold one 8-byte word per row of the pool")
+    inner, leaf_id, leaf_q = forest.device(state.device)  # (checks the limits and the leaf ids before the upload)
+    dev = state.device
+    n, C = state.n, int(forest.n_classes)
+    sums = torch.empty((n, C), dtype=torch.int64, device=dev)
+    pred = torch.empty(n, dtype=torch.uint8, device=dev)
+    entropy = torch.empty(n, dtype=torch.float64, device=dev)
+    row_index = torch.empty(n, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, dtype=torch.float64, device=dev)
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    keys_hi = torch.empty(n, dtype=torch.int64, device=dev) if want_hi else None
+    ev = None
+    if state.forest_events is not None:  # bench: K2 launch timing on the launch stream
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+    call("dal_forest_score_soft_dw", _ptr(state.x), n, state.d, state.d, _ptr(inner), _ptr(leaf_id), _ptr(leaf_q),
+         forest.n_leaves, forest.n_trees, int(forest.depth), C, _ptr(density), int(density_kind), float(density_err),
+         0 if flags is None else _ptr(flags), float(beta), _ptr(sums), _ptr(pred), _ptr(entropy), _ptr(row_index),
+         _ptr(scores), _ptr(keys), 0 if keys_hi is None else _ptr(keys_hi), _stream(dev))
+    if ev is not None:
+        ev[1].record()
+        state.forest_events.append(ev)
+    return sums, pred, entropy, row_index, scores, keys, keys_hi
+
+
 def forest_score_multiclass_dw(state: PoolState, forest: Forest, flags, density, density_kind: int,
                                density_err: float = 0.0, beta: float = 1.0, want_hi: bool = True, xb=None):
     """Launch dal_forest_score_multiclass_dw (dal_forest_score_multiclass_dw_
@@ -1085,7 +1124,8 @@ def dw_select_local(state: PoolState, flags, votes, keys_lo, keys_hi, lut_dev, k
 
 
 def dw_step_local(state: PoolState, forest: Forest, flags, dens, lut_dev, k: int, beta: float, colsum,
-                  colsum_ready=None, cap_scale: int = None, sync: bool = True, xb=None, n_classes=None):
+                  colsum_ready=None, cap_scale: int = None, sync: bool = True, xb=None, n_classes=None,
+                  soft: bool = False):
     """dal_dw_step on this pool or shard: votes, scores and interval keys
     of every row, then the exact canonical top-k -- one C call with fused
     launches (the fast level 1; ``xb``: the pool's blocked copy for the score
@@ -1094,6 +1134,9 @@ def dw_step_local(state: PoolState, forest: Forest, flags, dens, lut_dev, k: int
     C-class forest -- ``lut_dev`` is then the multiclass entropy table, ``xb``
     the copy the C-class rule allowed, and per-class counts ([n, C] uint8)
     come back in the place of the votes.
+    ``soft``: dal_dw_step_soft over a ProbabilityForest on the row-major pool
+    (``lut_dev``, ``xb`` and ``n_classes`` unused); the class sums ([n, C]
+    int64) come back in the place of the votes.
     Returns (votes, scores, indices, selected scores); sync=False (the
     multi-GPU path: the caller reads the status word after the merge and
     re-runs with a larger ``cap_scale``) also returns the selected keys."""
@@ -1101,14 +1144,23 @@ def dw_step_local(state: PoolState, forest: Forest, flags, dens, lut_dev, k: int
     lib = _lib.load()
     n = state.n
     forest.check_features(state.d)
-    inner, leaf = forest.device(state.device)
     norm64 = state.norms()
     derr = float(density_error(state))
     dev = state.device
-    if n_classes is None:
+    if soft:
+        inner, leaf_id, leaf_q = forest.device(dev)  # (checks the limits and the leaf ids before the upload)
+        votes = torch.empty((n, int(forest.n_classes)), dtype=torch.int64, device=dev)  # the class sums
+        entropy = torch.empty(n, dtype=torch.float64, device=dev)
+        row_index = torch.empty(n, dtype=torch.int32, device=dev)
+        entry, rows = "dal_dw_step_soft", (_ptr(votes), 0, _ptr(entropy), _ptr(row_index))
+        head = (_ptr(state.x), n, state.d, state.d, _ptr(inner), _ptr(leaf_id), _ptr(leaf_q), forest.n_leaves,
+                forest.n_trees, int(forest.depth), int(forest.n_classes))
+    elif n_classes is None:
+        inner, leaf = forest.device(dev)
         votes = torch.empty(n, dtype=torch.int32, device=dev)
         entry, classes, rows = "dal_dw_step", (), (_ptr(votes),)
     else:
+        inner, leaf = forest.device(dev)
         forest.check_classes()
         if forest.n_trees > DAL_MC_MAX_TREES:
             raise ValueError(f"a multiclass forest may hold at most {DAL_MC_MAX_TREES} trees, not {forest.n_trees}")
@@ -1123,6 +1175,9 @@ def dw_step_local(state: PoolState, forest: Forest, flags, dens, lut_dev, k: int
     keys_hi = torch.empty(n, dtype=torch.int64, device=dev)
     base = candidate_cap(n, k) if state.cap_base is None else max(int(k), int(state.cap_base))
     cap = int(min(n, base * (state.cap_scale if cap_scale is None else cap_scale)))
+    if not soft:
+        head = (_ptr(state.x), 0 if xb is None else _ptr(xb), _fprep(forest, state, xb), n, state.d, state.d,
+                _ptr(inner), _ptr(leaf), forest.n_trees, forest.depth, *classes, _ptr(lut_dev))
     while True:
         passes = level1_passes(state, n, k, cap)
         wsb = int(lib.dal_dw_step_workspace_bytes(n, k, cap))
@@ -1138,10 +1193,7 @@ def dw_step_local(state: PoolState, forest: Forest, flags, dens, lut_dev, k: int
         out_scores = torch.empty(k, dtype=torch.float64, device=dev)
         out_keys = None if sync else torch.empty(k, dtype=torch.int64, device=dev)
         try:
-            call(entry, _ptr(state.x), 0 if xb is None else _ptr(xb), _fprep(forest, state, xb), n,
-                 state.d, state.d, _ptr(inner),
-                 _ptr(leaf), forest.n_trees, forest.depth, *classes, _ptr(lut_dev), _ptr(dens), derr, _ptr(flags),
-                 float(beta), state.row_base,
+            call(entry, *head, _ptr(dens), derr, _ptr(flags), float(beta), state.row_base,
                  _ptr(norm64), _ptr(colsum), k, cap, passes, DAL_STEP_WS_CLEAN, wsp, wsb, *rows,
                  _ptr(scores), _ptr(keys_lo), _ptr(keys_hi), _ptr(out_idx), _ptr(out_scores),
                  0 if out_keys is None else _ptr(out_keys), _ptr(state.status),
@@ -1249,6 +1301,62 @@ def soft_step(state: PoolState, unlabeled_idx, forest, k: int, strategy: str = "
     sums, _, scores, keys = forest_score_soft(state, forest, flags, order, SOFT_KINDS[strategy])
     idx, _ = topk_keys(keys, kk, state.row_base)
     sel_scores = scores[idx - state.row_base]
+    return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, sums=(sums, loc),
+                     denominator=forest.denominator)
+
+
+def soft_density_step(state: PoolState, unlabeled_idx, forest, k: int, beta: float = 1.0, density_fixed=None,
+                      mode: str = "gram") -> Selection:
+    """One density-weighted iteration over a ProbabilityForest: score =
+    entropy(predict_proba) x d^beta, descending; exact canonical selection on
+    the entropy the kernel returned ("K2 soft votes,
+    density-weighted").
+
+    mode "gram": as multiclass_density_step -- on a cold pool the Gram goes
+    first with the canonical column sum on the side stream, then one
+    dal_dw_step_soft call (dw_step_local's clean workspace): interval keys,
+    per-row entropy and the identity index, and the selection with lut =
+    entropy, votes = row index, whose fp64 re-rank forms entropy[i] *
+    (canonical density)^beta.  With ``forest_events`` or ``select_events`` set
+    the unfused pair runs (dal_forest_score_soft_dw, dal_dw_select).  The
+    soft kernel reads the row-major pool on every step: there is no blocked
+    copy and no graph plan.
+    mode "separable": the exact O(N*D) density, canonical scores for every
+    row and a plain top-k.
+    The Selection carries ``sums`` ([U, C] int64) and ``proba()``, as
+    soft_step's."""
+    if mode not in ("gram", "separable"):
+        raise ValueError(f"density mode must be 'gram' or 'separable', not {mode!r}")
+    unl = _as_index(unlabeled_idx, state.device)
+    if int(unl.shape[0]) == 0:
+        raise ValueError("unlabeled set is empty (the reference loop breaks here)")
+    if mode == "separable":
+        flags, unl, n_cand = state.row_flags(unl)
+        kk = min(int(k), n_cand)
+        loc = state.local_positions(unl)
+        sums, _, _, _, scores, keys, _ = forest_score_soft_dw(
+            state, forest, flags, state.density_exact(), DAL_DENSITY_EXACT, beta=beta, want_hi=False)
+        idx, _ = topk_keys(keys, kk, state.row_base)
+        sel_scores = scores[idx - state.row_base]
+        state.check_status()
+        return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, sums=(sums, loc),
+                         denominator=forest.denominator)
+    state._excluded_since_step = False
+    # the density GEMM goes to the GPU first; the host prepares the rest while it runs
+    dens, colsum_ready = _density_for_step(state, density_fixed)
+    flags, unl, n_cand = state.row_flags(unl)
+    kk = min(int(k), n_cand)
+    loc = state.local_positions(unl)
+    if state.forest_events is None and state.select_events is None:
+        sums, scores, idx, sel_scores = dw_step_local(state, forest, flags, dens, None, kk, beta, state.colsum(),
+                                                      colsum_ready, soft=True)
+    else:  # the per-kernel timing path keeps K2 / K3 apart
+        sums, _, entropy, row_index, scores, keys_lo, keys_hi = forest_score_soft_dw(
+            state, forest, flags, dens, DAL_DENSITY_FIXED, density_err=density_error(state), beta=beta, want_hi=True)
+        # the main stream joins the column sum inside the call, just before the re-rank
+        idx, sel_scores, _ = dw_select_local(state, flags, row_index, keys_lo, keys_hi, entropy, kk, beta,
+                                             state.colsum(), colsum_ready=colsum_ready)
+    state.check_status(state.last_status)  # the word the step read (no second sync)
     return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, sums=(sums, loc),
                      denominator=forest.denominator)
 

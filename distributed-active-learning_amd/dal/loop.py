@@ -92,6 +92,10 @@ class LoopResult:
     metrics: list = field(default_factory=list)  # dal.metrics.evaluate's dict per iteration (run_loop(measures=))
 
 
+# the strategies that score with the density (``density_over`` applies; E starts as the initial labeled rows)
+DENSITY_STRATEGIES = ("density", "information_density", "soft_information_density")
+
+
 def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
              window_size: int = 10, n_estimators: int = 10, max_iterations=None,
              seed: int = 0, select_fn=None, device=None, beta: float = 1.0,
@@ -101,7 +105,10 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     """Run the AL loop.  strategy: "uncertainty" (uncertainty_sampling.py),
     "density" (density_weighting.py, E = L0 = range(window_size)),
     "information_density" (class entropy x density, E = L0;
-    density_weighting.select_multiclass), "lal" (ActiveLearnerLAL.selectNext,
+    density_weighting.select_multiclass), "soft_information_density"
+    (entropy(predict_proba) x density over the averaged leaf class
+    distributions, E = L0; density_weighting.select_soft: soft votes, below,
+    for any label count), "lal" (ActiveLearnerLAL.selectNext,
     lal_direct_mllib_implementation/classes/active_learner.py:240-343:
     dal.active_learner.select_lal with ``lal_model``, a
     dal.forest.RegressionForest over the five LAL features; binary only; the
@@ -140,7 +147,8 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     dal.metrics.evaluate's (tests inject the restatement; None: the HIP
     kernel).  measures=None changes nothing: same calls, log and ``accuracy``.
 
-    density_over ("density" and "information_density" only): which rows the
+    density_over ("density", "information_density" and
+    "soft_information_density" only): which rows the
     density d_i = sum_{j not in E} cos(x_i, x_j) sums over.  "initial" (the
     default) is the reference: E is frozen at the rows the loop starts from,
     so every row labeled later keeps contributing to every density
@@ -162,9 +170,13 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     through dal.forest.ProbabilityForest.from_sklearn, for any label count.
     trainer="gpu" (its forests keep no leaf distributions) or any other
     strategy raises ValueError.  False, the default, makes the calls it made.
+    strategy="soft_information_density" scores soft votes by definition: it
+    needs the same trainers, raises the same error for trainer="gpu", and
+    accepts soft_votes=True as redundant.
     """
-    if soft_votes:
-        if strategy not in ("uncertainty", "ranked_batch"):
+    soft_density = strategy == "soft_information_density"  # (soft votes by its definition: the flag is redundant)
+    if soft_votes or soft_density:
+        if not soft_density and strategy not in ("uncertainty", "ranked_batch"):
             raise ValueError(f"soft_votes=True belongs to strategy 'uncertainty' or 'ranked_batch': {strategy!r} "
                              "scores hard votes")
         if trainer == "gpu":
@@ -172,9 +184,9 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
                              "forest: trainer='gpu' keeps no leaf distributions")
     if density_over not in ("initial", "unlabeled"):
         raise ValueError(f"density_over must be 'initial' or 'unlabeled', not {density_over!r}")
-    if density_over == "unlabeled" and strategy not in ("density", "information_density"):
-        raise ValueError(f"density_over='unlabeled' needs strategy 'density' or 'information_density': "
-                         f"{strategy!r} has no density")
+    if density_over == "unlabeled" and strategy not in DENSITY_STRATEGIES:
+        raise ValueError(f"density_over='unlabeled' needs strategy 'density', 'information_density' or "
+                         f"'soft_information_density': {strategy!r} has no density")
     from .forest import Forest
 
     # more than two label values: multiclass uncertainty sampling (per-class
@@ -218,7 +230,7 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     if select_fn is None and strategy != "random":
         from .engine import PoolState
 
-        excluded = np.asarray(labeled, dtype=np.int64) if strategy in ("density", "information_density") else None
+        excluded = np.asarray(labeled, dtype=np.int64) if strategy in DENSITY_STRATEGIES else None
         state = PoolState(X, excluded=excluded, device=device)
         if sim_pool is not None:
             from .similarity import _bf16_pool
@@ -275,7 +287,7 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
         elif select_fn is not None:
             chosen = np.asarray(select_fn(strategy, X, unlabeled, rf, k))
         else:
-            if soft_votes:
+            if soft_votes or soft_density:
                 from .forest import ProbabilityForest
 
                 if isinstance(rf, (GpuForestModel, Forest)):
@@ -298,6 +310,9 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
             elif strategy == "information_density":
                 from .density_weighting import select_multiclass
                 sel = select_multiclass(state, unlabeled, forest, k, beta=beta)
+            elif soft_density:
+                from .density_weighting import select_soft
+                sel = select_soft(state, unlabeled, forest, k, beta=beta)
             elif strategy == "lal":
                 from .active_learner import select_lal
                 sel = select_lal(state, unlabeled, forest, lal_model, k, n_labeled=len(labeled),

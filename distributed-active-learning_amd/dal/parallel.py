@@ -46,20 +46,28 @@ from ._lib import DAL_ASCENDING, DAL_CANON_CHUNK, DAL_DESCENDING, DAL_KEY_NONE, 
 RCCL_RESERVED_CUS = 8
 
 # selection modes that score with the density: "dw" (binary, the reference's
-# one-sided entropy) and "dw_multiclass" (class entropy, any C >= 2)
+# one-sided entropy) and "dw_multiclass" (class entropy, any C >= 2) over hard
+# votes, and "dw_soft" (the entropy of a ProbabilityForest's averaged leaf
+# distributions) over soft votes
 DENSITY_MODES = ("dw", "dw_multiclass")
+SOFT_DENSITY_MODES = ("dw_soft",)
+ALL_DENSITY_MODES = DENSITY_MODES + SOFT_DENSITY_MODES
 
 
 def _soft_forest(forest, mode: str) -> bool:
-    """True for a dal.forest.ProbabilityForest (soft votes), which mode "us"
-    alone scores; any other mode raises ValueError, before any work."""
+    """True for a dal.forest.ProbabilityForest (soft votes), which modes "us"
+    and "dw_soft" alone score; any other mode raises ValueError, before any
+    work -- as does mode "dw_soft" for a hard-voting Forest."""
     from .forest import ProbabilityForest
 
     soft = isinstance(forest, ProbabilityForest)
-    if soft and mode != "us":
-        raise ValueError(f"a ProbabilityForest (soft votes) is scored by mode='us' only: mode={mode!r} has no "
-                         "soft-vote form (the density-weighted and LAL scores take hard votes; "
-                         "forest.hard() gives the hard-voting Forest)")
+    if soft and mode != "us" and mode not in SOFT_DENSITY_MODES:
+        raise ValueError(f"a ProbabilityForest (soft votes) is scored by mode='us' or mode='dw_soft' only: "
+                         f"mode={mode!r} has no soft-vote form (the hard-vote density-weighted and LAL scores take "
+                         "hard votes; forest.hard() gives the hard-voting Forest)")
+    if mode in SOFT_DENSITY_MODES and not soft:
+        raise ValueError("mode='dw_soft' scores a ProbabilityForest (soft votes): a hard-voting Forest belongs to "
+                         "mode='dw' (binary) or mode='dw_multiclass'")
     return soft
 
 
@@ -336,10 +344,13 @@ class ShardedSelector:
                      strategy: str = "least_confidence", beta: float = 1.0,
                      density_mode: str = "gram", warm: bool = None) -> LocalTopk:
         """This rank's exact local top-k.  mode: "us" (uncertainty), "dw"
-        (binary density weighting) or "dw_multiclass" (class entropy x
+        (binary density weighting), "dw_multiclass" (class entropy x
         density, any forest of two or more classes; the C-class score kernel
-        and dal_dw_select).  A dal.forest.ProbabilityForest (soft votes) is
-        scored by mode "us" alone; every other mode raises ValueError.  ``warm``: the density was cached
+        and dal_dw_select) or "dw_soft" (entropy of the averaged leaf
+        distributions x density: a dal.forest.ProbabilityForest alone, through
+        dal_dw_step_soft).  A ProbabilityForest (soft votes) is scored by
+        modes "us" and "dw_soft" alone; every other mode raises ValueError.
+        ``warm``: the density was cached
         before this step (the score kernel then reads the shard's blocked
         copy, as the single-GPU warm step does; a cold step keeps the
         row-major kernel and builds no copy).  None: cached now."""
@@ -404,6 +415,30 @@ class ShardedSelector:
                     want_hi=True, xb=xb)
                 i, s, kk_keys = dw_select_local(st, flags, rix, klo, khi, ent, kk, beta, colsum,
                                                 cap_scale=self.cap_scale, sync=False)
+        elif mode == "dw_soft":
+            # entropy(predict_proba) x density: the soft kernel's density-weighted
+            # form on the row-major shard (it has no blocked form), then the same
+            # exact selection with lut = entropy, votes = the identity index
+            from ._lib import DAL_DENSITY_EXACT, DAL_DENSITY_FIXED
+            from .engine import forest_score_soft_dw
+
+            colsum = self.global_colsum(partials_full)
+            if density_mode == "separable":
+                _, _, _, _, sc, kys, _ = forest_score_soft_dw(
+                    st, forest, flags, st.density_exact(colsum), DAL_DENSITY_EXACT, beta=beta, want_hi=False)
+                i, kk_keys = topk_keys(kys, kk, st.row_base)
+                s = sc[i - st.row_base]
+            else:
+                dens = self.local_density(u_full)
+                if st.events_off():  # one fused call (dal_dw_step_soft), as the single-GPU step
+                    _, _, i, s, kk_keys = dw_step_local(st, forest, flags, dens, None, kk, beta, colsum,
+                                                        cap_scale=self.cap_scale, sync=False, soft=True)
+                else:  # bench per-kernel timing: K2 and K3 as separate calls
+                    _, _, ent, rix, _, klo, khi = forest_score_soft_dw(
+                        st, forest, flags, dens, DAL_DENSITY_FIXED, density_err=density_error(st), beta=beta,
+                        want_hi=True)
+                    i, s, kk_keys = dw_select_local(st, flags, rix, klo, khi, ent, kk, beta, colsum,
+                                                    cap_scale=self.cap_scale, sync=False)
         elif soft:  # soft votes: the averaged leaf distributions, the same merge
             from .engine import SOFT_KINDS, forest_score_soft
             from .luts import MULTICLASS_ASCENDING
@@ -616,7 +651,7 @@ def _select(sels, ops, unlabeled_idx, forest, k, mode, strategy, beta, sort_fn, 
     unls = [s.index_tensor(unlabeled_idx) for s in sels]
     u_fulls = parts_fulls = [None] * len(sels)
     warm = [s._density is not None for s in sels]  # (a cold step's score kernel keeps the row-major pool)
-    if mode in DENSITY_MODES:  # uncertainty sampling never normalises (no density, no zero-norm check)
+    if mode in ALL_DENSITY_MODES:  # uncertainty sampling never normalises (no density, no zero-norm check)
         need_u = density_mode == "gram" and not all(warm)
         if need_u or any(s._parts_full is None for s in sels):
             preps = [s.prep() for s in sels]
@@ -652,7 +687,7 @@ def _select(sels, ops, unlabeled_idx, forest, k, mode, strategy, beta, sort_fn, 
         # queued: the step's one host sync, and every rank sees the same bits
         merged = _merge(ops, tops, [s.status_word() for s in sels], sels[0].world, k, sort_fn, all_valid)
     st = merged[0][1]  # the OR of every rank's status word: identical on all ranks and jobs
-    if mode not in DENSITY_MODES:
+    if mode not in ALL_DENSITY_MODES:
         st &= ~_lib.DAL_FLAG_ZERO_NORM  # a zero row only matters to the cosine density
     if st & _lib.DAL_FLAG_ZERO_NORM:
         raise ValueError("pool contains a zero-norm row: cosine similarity is undefined "

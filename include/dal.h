@@ -568,6 +568,39 @@ int dal_forest_score_soft(const float* x, int64_t n, int64_t d, int64_t x_stride
                           int32_t depth, int32_t n_classes, int score_kind, const uint8_t* row_flags, int order,
                           uint64_t* sums, uint8_t* pred, double* scores, uint64_t* keys, dal_stream_t stream);
 
+/* ---- soft votes: class entropy x density^beta, interval keys --------------
+ * modAL's information density on predict_proba: entropy(predict_proba) *
+ * density^beta.  New symbols only: dal_abi_version() stays 10, and a caller
+ * probes for the symbol (absent from older libraries).  Forest, x_stride, sums
+ * and pred as dal_forest_score_soft; the kind is DAL_SOFT_ENTROPY and the
+ * order descending:
+ *   entropy[i]   = dal_forest_score_soft(DAL_SOFT_ENTROPY)'s scores[i], the
+ *                  same bits (>= +0.0, never NaN; within n_classes 2^-49 of
+ *                  the host's entropy of S_c / M)
+ *   scores[i]    = entropy[i] * d_i^beta   (one fp64 multiply, no FMA; d_i^beta
+ *                  = d_i at beta == 1), NaN for DAL_ROW_EXCLUDED rows
+ *   row_index[i] = i   (int32: n <= INT32_MAX, else DAL_ERR_SHAPE)
+ * d_i, density_kind, density_err, keys, keys_hi (nullable) and the candidates'
+ * DAL_KEY_NONE exactly as dal_forest_score_multiclass_dw: with
+ * DAL_DENSITY_FIXED keys[i] / keys_hi[i] are the keys of scores[i] -+ err_i,
+ * err_i = entropy[i] * density_err at beta == 1 (the d^beta image of the
+ * interval otherwise), floored at |scores[i]| * 4.5e-16 and zero where
+ * entropy[i] == 0 or the row is excluded; with DAL_DENSITY_EXACT keys_hi ==
+ * keys.  Exactness is therefore stated on the entropy the call returned: for
+ * every candidate outside the excluded set, keys_hi <= key(entropy[i] *
+ * d_canonical^beta) <= keys.  The exact selection is dal_dw_select unchanged,
+ * with votes = row_index and lut = entropy.
+ * Before any device call: a null x, inner, leaf_id, leaf_q, density, entropy,
+ * row_index, scores or keys, or a bad density_kind, is DAL_ERR_ARG; then
+ * dal_forest_score_soft's DAL_ERR_SHAPE conditions and n > INT32_MAX; then its
+ * DAL_ERR_UNSUPPORTED ones.  n == 0 returns DAL_OK and launches nothing. */
+int dal_forest_score_soft_dw(const float* x, int64_t n, int64_t d, int64_t x_stride, const int32_t* inner,
+                             const int32_t* leaf_id, const uint32_t* leaf_q, int64_t n_leaves, int32_t n_trees,
+                             int32_t depth, int32_t n_classes, const void* density, int density_kind,
+                             double density_err, const uint8_t* row_flags, double beta, uint64_t* sums,
+                             uint8_t* pred, double* entropy, int32_t* row_index, double* scores, uint64_t* keys,
+                             uint64_t* keys_hi, dal_stream_t stream);
+
 /* ---- (a11) top-k: sortBy(score).take(k) --------------------------------
  * Replaces uncertainty_sampling.py:106,109 / density_weighting.py:168,172.
  * The k smallest keys, ties -> lower index; out_idx = idx_base + row, sorted
@@ -705,6 +738,32 @@ int dal_dw_step_multiclass(const float* x, const float* xb, const void* fprep, i
                            dal_event_t colsum_ready, dal_stream_t stream);
 int dal_dw_step_multiclass_form(int64_t n, int64_t d, int32_t n_trees, int32_t depth, int32_t n_classes, int64_t k,
                                 int64_t cap, int32_t level1_passes, int blocked);
+
+/* ---- one density-weighted iteration over a soft-vote forest in one call ---
+ * A new symbol only: dal_abi_version() stays 10 (absent from older
+ * libraries).  dal_dw_step_soft is equivalent to dal_forest_score_soft_dw(x,
+ * ..., density_fixed, DAL_DENSITY_FIXED, density_err, row_flags, beta, sums,
+ * pred, entropy, row_index, scores, keys_lo, keys_hi) followed by
+ * dal_dw_select(keys_lo, keys_hi, row_index, row_flags, n, k, idx_base,
+ * entropy, beta, x, d, x_stride, norm64, colsum, cap, level1_passes, ...) --
+ * same outputs, same bits.  The soft kernel does not fold group minima: the
+ * step takes the exact level 1 (level1_passes == 0, or a capacity above
+ * DAL_SORT_CAP_PAYLOAD whatever level1_passes says), or with the fast level 1
+ * one group-minimum pass after the score kernel and then ONE launch that
+ * derives tau, appends the candidates with their canonical scores and sorts
+ * them.  step_flags: DAL_STEP_RESET_STATUS and DAL_STEP_WS_CLEAN as for
+ * dal_dw_step; any other bit is DAL_ERR_ARG.  sums and pred are nullable;
+ * every other buffer is required (DAL_ERR_ARG), then the score entry's
+ * DAL_ERR_SHAPE and DAL_ERR_UNSUPPORTED checks; n == 0 returns DAL_OK before
+ * the selection's checks.  Workspace: dal_dw_step_workspace_bytes. */
+int dal_dw_step_soft(const float* x, int64_t n, int64_t d, int64_t x_stride, const int32_t* inner,
+                     const int32_t* leaf_id, const uint32_t* leaf_q, int64_t n_leaves, int32_t n_trees,
+                     int32_t depth, int32_t n_classes, const int64_t* density_fixed, double density_err,
+                     const uint8_t* row_flags, double beta, int64_t idx_base, const double* norm64,
+                     const double* colsum, int64_t k, int64_t cap, int32_t level1_passes, uint32_t step_flags,
+                     void* ws, size_t ws_bytes, uint64_t* sums, uint8_t* pred, double* entropy, int32_t* row_index,
+                     double* scores, uint64_t* keys_lo, uint64_t* keys_hi, int64_t* out_idx, double* out_scores,
+                     uint64_t* out_keys, int32_t* dev_status, dal_event_t colsum_ready, dal_stream_t stream);
 
 /* ---- warm-step plan: a replayed dal_dw_step with a one-call host side -----
  * dal_dw_plan_create captures dal_dw_step (DAL_STEP_RESET_STATUS |
