@@ -40,6 +40,19 @@
 // density word is loaded with its flags when the tile is staged; the
 // epilogue's fp64 temporaries exist after the cross-lane sum only.  The DW =
 // false kernels are the code they were without it.
+//
+// The BALD form (dal_forest_score_soft_bald) scores the trees' disagreement,
+// H(pbar) - (1/T) sum_t H(p_t): a leaf's entropy is one more fixed-point word
+// (leaf_h, rint(H_l 2^29)) and a row's sum of them one more exact 64-bit
+// integer per lane, added across the row's lanes like the class sums.  In LDS
+// the word sits at column C of the leaf's row of round2(C + 1) words (for odd
+// C the padding word that was there already) and arrives in the 8-byte reads
+// the row takes anyway; from global memory it comes from the caller's [L]
+// array.  (For odd C the reads, the adds and the cross-lane sum are the class
+// sums' own: the word lands in the spare accumulator s[C].)  The row leader
+// forms entropy - hsum / (T 2^29), clamped at +0.0.
+// Everything it adds is gated by `if constexpr (BALD)`: the other kernels are
+// the code they were.
 #include "forest_shared.hpp"
 
 namespace dal {
@@ -88,9 +101,37 @@ struct SoftDwArgs : SoftArgs {
   int32_t* status_reset;  // nullable; dal_dw_step_soft: zeroed by the grid's first thread
 };
 
+// The BALD form (dal_forest_score_soft_bald): the entropy (kind =
+// DAL_SOFT_ENTROPY) minus the mean of the reached leaves' entropies.
+struct SoftBaldArgs : SoftArgs {
+  const uint32_t* leaf_h;    // [n_leaves] rint(H_l 2^DAL_SOFT_ENTROPY_SHIFT)
+  unsigned long long* hsum;  // nullable
+  double* entropy;           // nullable
+};
+
 // Words per leaf row of the LDS copy of the leaf table: C rounded up to even,
 // so a row is 8-byte aligned and read in 8-byte pieces.
 __host__ __device__ inline int soft_lds_stride(int n_classes) { return (n_classes + 1) & ~1; }
+// ... BALD: of the C class words and the leaf's entropy word at column C.
+template <bool BALD>
+__host__ __device__ inline int soft_lds_row(int n_classes) {
+  return soft_lds_stride(n_classes + (BALD ? 1 : 0));
+}
+// Word c of leaf l's LDS row: the class word, (BALD) the entropy word at
+// column C, zero padding after them.
+template <bool BALD, class Args>
+__device__ __forceinline__ uint32_t soft_lds_word(const Args& A, int l, int c) {
+  if constexpr (BALD) {
+    if (c == A.n_classes) return A.leaf_h[l];
+  }
+  return c < A.n_classes ? A.leaf_q[l * A.n_classes + c] : 0u;
+}
+// The caller's [L] array of leaf entropy words (BALD; nothing otherwise).
+template <bool BALD, class Args>
+__device__ __forceinline__ const uint32_t* soft_leaf_h(const Args& A) {
+  if constexpr (BALD) return A.leaf_h;
+  else return nullptr;
+}
 
 // s[c] += q[c], c < C, for the leaf whose words start at q: the padded LDS row
 // in 8-byte pieces (Q_LDS; ds_read_b64 moves the bytes per LDS cycle of the
@@ -112,6 +153,35 @@ __device__ __forceinline__ void add_leaf(unsigned long long (&s)[W], const uint3
     for (int c = 0; c < W; ++c)
       if (c < C) s[c] += q[c];
   }
+}
+
+// BALD: add_leaf, and the leaf's entropy word.  Q_LDS: q is the leaf's row of
+// round2(C + 1) words, the entropy word at column C.  Odd C (< W): the word is
+// the second half of the last class piece, where add_leaf's row has its zero
+// padding, and add_leaf's own 8-byte reads add it into s[C], the accumulator
+// no class uses -- no read and no add beyond the entropy kernel's; the caller
+// takes the row's sum from s[C] (soft_spare_sum).  Even C: the first word of
+// one more piece, added into hs.  Otherwise (the caller's tables) the word is
+// leaf_h[l], added into hs.
+template <int W, bool Q_LDS>
+__device__ __forceinline__ void add_leaf_bald(unsigned long long (&s)[W], unsigned long long& hs, const uint32_t* q,
+                                              int C, const uint32_t* leaf_h, unsigned l) {
+  add_leaf<W, Q_LDS>(s, q, C);
+  if constexpr (Q_LDS) {
+    if (!(C & 1)) hs += q[C];  // (block-uniform)
+  } else {
+    hs += leaf_h[l];
+  }
+}
+
+// s[C] for odd C, read through a select over the W registers (compile-time
+// indices): the sum of the entropy words add_leaf_bald left there.
+template <int W>
+__device__ __forceinline__ unsigned long long soft_spare_sum(const unsigned long long (&s)[W], int C) {
+  unsigned long long v = 0ull;
+#pragma unroll
+  for (int j = 1; j < W; j += 2) v = j == C ? s[j] : v;
+  return v;
 }
 
 // The class-ordered entropy of a row whose tpr lanes (consecutive, sub = the
@@ -143,9 +213,11 @@ __device__ __forceinline__ double soft_entropy(const unsigned long long (&s)[W],
 // The row leader's epilogue: s holds the row's C class sums, entropy the
 // row's class entropy (DAL_SOFT_ENTROPY only; DW: always).  DW: dens_pre, the
 // row's density word, loaded with its flags.
-template <int W, bool DW, bool POW, class Args>
+// BALD: hs, the row's sum of leaf entropy words.
+template <int W, bool DW, bool POW, bool BALD, class Args>
 __device__ __forceinline__ void soft_epilogue(const Args& A, const unsigned long long (&s)[W], int64_t row,
-                                              uint8_t fl, long long dens_pre, double M, double entropy) {
+                                              uint8_t fl, long long dens_pre, double M, double entropy,
+                                              unsigned long long hs) {
   const int C = A.n_classes;
   // largest and second-largest sum, the lowest class holding the largest
   long long m1 = -1, m2 = -1;
@@ -164,7 +236,17 @@ __device__ __forceinline__ void soft_epilogue(const Args& A, const unsigned long
     }
   }
   double score = entropy;  // DW: times density^beta below
-  if constexpr (!DW) {
+  if constexpr (BALD) {
+    // entropy - hsum / (T 2^29): one division of two exact doubles (hs < 2^41),
+    // one subtraction; what the word rounding and the log2 push below zero
+    // (and -0.0) is +0.0
+    const double g = __ddiv_rn(static_cast<double>(hs), static_cast<double>(A.n_trees) *
+                                                            static_cast<double>(1u << DAL_SOFT_ENTROPY_SHIFT));
+    const double b = __dsub_rn(entropy, g);
+    score = b > 0.0 ? b : 0.0;
+    if (A.hsum) A.hsum[row] = hs;
+    if (A.entropy) A.entropy[row] = entropy;
+  } else if constexpr (!DW) {
     score = A.kind == DAL_SOFT_ENTROPY
                 ? entropy
                 : __ddiv_rn(static_cast<double>(A.kind == DAL_SOFT_MARGIN ? m1 - m2 : m1), M);
@@ -212,11 +294,12 @@ __device__ __forceinline__ void soft_epilogue(const Args& A, const unsigned long
 // dens_pre, its density word, loaded with them (the epilogue's fp64
 // temporaries exist on the row leader after the cross-lane sum only).  qstride:
 // words per leaf row of leaf_q (the LDS copy's padded row, or C).
-template <int W, bool X_LDS, bool F_LDS, bool DW, bool POW, class Args>
+// BALD: leaf_h, the caller's entropy words (read when the forest is not in LDS).
+template <int W, bool X_LDS, bool F_LDS, bool DW, bool POW, bool BALD, class Args>
 __device__ __forceinline__ void score_tile_soft(const Args& A, const float* xs, int xstride, int64_t tile, int R,
                                                 int tpr, const int2* inner, const int32_t* leaf_id,
                                                 const uint32_t* leaf_q, int qstride, uint8_t fl_pre,
-                                                long long dens_pre) {
+                                                long long dens_pre, const uint32_t* leaf_h) {
   const int n_inner = (1 << A.depth) - 1;
   const int n_leaf = 1 << A.depth;
   const int tid = threadIdx.x;
@@ -230,6 +313,7 @@ __device__ __forceinline__ void score_tile_soft(const Args& A, const float* xs, 
   unsigned long long s[W];
 #pragma unroll
   for (int c = 0; c < W; ++c) s[c] = 0ull;
+  unsigned long long hs = 0ull;  // BALD: the sum of the reached leaves' entropy words
   if (live) {
     int t = sub;
     for (; t + (kSoftIlp - 1) * tpr < A.n_trees; t += kSoftIlp * tpr) {
@@ -252,7 +336,11 @@ __device__ __forceinline__ void score_tile_soft(const Args& A, const float* xs, 
         l[j] = id < last_leaf ? id : last_leaf;
       }
 #pragma unroll
-      for (int j = 0; j < kSoftIlp; ++j) add_leaf<W, F_LDS>(s, leaf_q + static_cast<size_t>(l[j]) * qstride, A.n_classes);
+      for (int j = 0; j < kSoftIlp; ++j) {
+        const uint32_t* q = leaf_q + static_cast<size_t>(l[j]) * qstride;
+        if constexpr (BALD) add_leaf_bald<W, F_LDS>(s, hs, q, A.n_classes, leaf_h, l[j]);
+        else add_leaf<W, F_LDS>(s, q, A.n_classes);
+      }
     }
     for (; t < A.n_trees; t += tpr) {
       int h = 0;
@@ -261,20 +349,32 @@ __device__ __forceinline__ void score_tile_soft(const Args& A, const float* xs, 
         h = 2 * h + (xrow[nd.x] <= __int_as_float(nd.y) ? 1 : 2);
       }
       const unsigned id = static_cast<unsigned>(leaf_id[t * n_leaf + (h - n_inner)]);
-      add_leaf<W, F_LDS>(s, leaf_q + static_cast<size_t>(id < last_leaf ? id : last_leaf) * qstride, A.n_classes);
+      const unsigned l = id < last_leaf ? id : last_leaf;
+      const uint32_t* q = leaf_q + static_cast<size_t>(l) * qstride;
+      if constexpr (BALD) add_leaf_bald<W, F_LDS>(s, hs, q, A.n_classes, leaf_h, l);
+      else add_leaf<W, F_LDS>(s, q, A.n_classes);
     }
   }
   // a row's tpr threads are consecutive lanes (tpr a power of two <= 64): their
   // partial sums add as integers, so the lane mapping cannot change a bit
+  if constexpr (BALD) {  // (first: only the row leader reads it again, after the entropy)
+    for (int o = 1; o < tpr; o <<= 1) hs += __shfl_xor(hs, o);
+  }
   for (int o = 1; o < tpr; o <<= 1) {
 #pragma unroll
     for (int c = 0; c < W; ++c) s[c] += __shfl_xor(s[c], o);
   }
+  if constexpr (BALD && F_LDS) {
+    // odd C: the entropy words went into s[C] with the 8-byte reads and were
+    // added across the lanes with the class sums (hs is zero); s[C] is read by
+    // nothing else (the entropy, the prediction and the stores stop at C)
+    if (A.n_classes & 1) hs = soft_spare_sum<W>(s, A.n_classes);
+  }
   const double M = static_cast<double>(A.n_trees) * 2147483648.0;  // T 2^31, exact
   double entropy = 0.0;
-  if (DW || A.kind == DAL_SOFT_ENTROPY) entropy = soft_entropy<W>(s, A.n_classes, tpr, sub, M);  // (block-uniform)
+  if (DW || BALD || A.kind == DAL_SOFT_ENTROPY) entropy = soft_entropy<W>(s, A.n_classes, tpr, sub, M);  // (block-uniform)
   if (!(live && sub == 0)) return;
-  soft_epilogue<W, DW, POW>(A, s, row, fl_pre, dens_pre, M, entropy);
+  soft_epilogue<W, DW, POW, BALD>(A, s, row, fl_pre, dens_pre, M, entropy, hs);
 }
 
 // What the body (forest_soft_body.inc) does for the density-weighted form
@@ -299,7 +399,7 @@ __device__ __forceinline__ long long soft_density_word(const Args& A, int64_t ro
 template <int W, bool X_LDS, bool F_LDS, bool PERSIST>
 __global__ __launch_bounds__(kSoftThreads) void forest_soft_kernel(SoftArgs A, int R, int tpr, int x_floats, bool vec4,
                                                                    bool pad4, bool dma, int64_t n_tiles) {
-  constexpr bool DW = false, POW = false;
+  constexpr bool DW = false, POW = false, BALD = false;
 #include "forest_soft_body.inc"
 }
 
@@ -309,21 +409,34 @@ template <int W, bool X_LDS, bool F_LDS, bool PERSIST, bool POW>
 __global__ __launch_bounds__(kSoftThreads) void forest_soft_dw_kernel(SoftDwArgs A, int R, int tpr, int x_floats,
                                                                       bool vec4, bool pad4, bool dma,
                                                                       int64_t n_tiles) {
-  constexpr bool DW = true;
+  constexpr bool DW = true, BALD = false;
+#include "forest_soft_body.inc"
+}
+
+// The BALD form (dal_forest_score_soft_bald): the same body, one more integer
+// accumulator per lane and the leaf's entropy word in its LDS row.
+template <int W, bool X_LDS, bool F_LDS, bool PERSIST>
+__global__ __launch_bounds__(kSoftThreads) void forest_soft_bald_kernel(SoftBaldArgs A, int R, int tpr, int x_floats,
+                                                                        bool vec4, bool pad4, bool dma,
+                                                                        int64_t n_tiles) {
+  constexpr bool DW = false, POW = false, BALD = true;
 #include "forest_soft_body.inc"
 }
 
 // The kernel of a form.
-template <int W, bool XL, bool FL, bool PS, bool DW, bool POW>
+template <int W, bool XL, bool FL, bool PS, bool DW, bool POW, bool BALD>
 constexpr auto soft_kernel() {
-  if constexpr (DW) return &forest_soft_dw_kernel<W, XL, FL, PS, POW>;
+  if constexpr (BALD) return &forest_soft_bald_kernel<W, XL, FL, PS>;
+  else if constexpr (DW) return &forest_soft_dw_kernel<W, XL, FL, PS, POW>;
   else return &forest_soft_kernel<W, XL, FL, PS>;
 }
 
 // The row-major tiling rule of the hard-vote kernels (forest_shared.hpp,
 // forest_tiling).  DW (Args = SoftDwArgs): the density-weighted kernels, POW
-// picked by beta -- the beta == 1 kernels hold no pow call.
-template <int W, bool DW, bool POW, class Args>
+// picked by beta -- the beta == 1 kernels hold no pow call.  BALD (Args =
+// SoftBaldArgs): the residency test counts the leaf rows with the entropy
+// word, so an even-C forest can leave LDS earlier than it does for the entropy.
+template <int W, bool DW, bool POW, bool BALD, class Args>
 int soft_launch(const Args& A, int64_t d, int64_t ldx, hipStream_t st) {
   const ForestTiling T = forest_tiling(A.x, d, ldx, A.n_trees, kSoftThreads);
   const int R = T.R, tpr = kSoftThreads / R;
@@ -334,12 +447,12 @@ int soft_launch(const Args& A, int64_t d, int64_t ldx, hipStream_t st) {
   const int64_t n_inner = (int64_t{1} << A.depth) - 1, n_leaf = int64_t{1} << A.depth;
   // nodes, leaf ids, then the padded leaf table from the next 16-B boundary
   const int64_t f_bytes = round_up(A.n_trees * (n_inner * 8 + n_leaf * 4), 16) +
-                          static_cast<int64_t>(A.n_leaves) * soft_lds_stride(A.n_classes) * 4;
+                          static_cast<int64_t>(A.n_leaves) * soft_lds_row<BALD>(A.n_classes) * 4;
   const bool f_lds = f_bytes <= kSoftForestLds;
   const size_t smem = static_cast<size_t>(xf) * 4 + (f_lds ? static_cast<size_t>(f_bytes) : 0);
 #define DAL_SOFT_LAUNCH(XL, FL, PS)                                                                          \
   do {                                                                                                       \
-    const auto kern = soft_kernel<W, XL, FL, PS, DW, POW>();                                                 \
+    const auto kern = soft_kernel<W, XL, FL, PS, DW, POW, BALD>();                                           \
     const void* fn = reinterpret_cast<const void*>(kern);                                                    \
     int64_t grid = blocks;                                                                                   \
     if (PS) { /* a persistent grid of exactly the blocks resident at once */                                 \
@@ -396,8 +509,8 @@ int soft_dw_launch(const SoftStepScore& S, const void* density, int density_kind
                      density, density_kind, S.density_err, S.beta, S.entropy, S.row_index, keys_hi, status_reset};
   return dispatch_soft_width(S.n_classes, [&](auto w) {
     constexpr int W = decltype(w)::value;
-    return S.beta == 1.0 ? soft_launch<W, true, false>(A, S.d, S.ldx, st)  // no pow, no call
-                         : soft_launch<W, true, true>(A, S.d, S.ldx, st);
+    return S.beta == 1.0 ? soft_launch<W, true, false, false>(A, S.d, S.ldx, st)  // no pow, no call
+                         : soft_launch<W, true, true, false>(A, S.d, S.ldx, st);
   });
 }
 
@@ -457,7 +570,7 @@ extern "C" int dal_forest_score_soft(const float* x, int64_t n, int64_t d, int64
                    keys};
   const hipStream_t st = as_stream(stream);
   return dispatch_soft_width(n_classes, [&](auto w) {
-    return soft_launch<decltype(w)::value, false, false>(A, d, x_stride, st);
+    return soft_launch<decltype(w)::value, false, false, false>(A, d, x_stride, st);
   });
 }
 
@@ -474,4 +587,24 @@ extern "C" int dal_forest_score_soft_dw(const float* x, int64_t n, int64_t d, in
   const SoftStepScore S{x,     n,         d,       x_stride, inner, leaf_id, leaf_q,  n_leaves, n_trees,
                         depth, n_classes, nullptr, density_err, beta, sums,   pred,    entropy,  row_index};
   return soft_dw_launch(S, density, density_kind, row_flags, scores, keys, keys_hi, nullptr, as_stream(stream));
+}
+
+extern "C" int dal_forest_score_soft_bald(const float* x, int64_t n, int64_t d, int64_t x_stride,
+                                          const int32_t* inner, const int32_t* leaf_id, const uint32_t* leaf_q,
+                                          const uint32_t* leaf_h, int64_t n_leaves, int32_t n_trees, int32_t depth,
+                                          int32_t n_classes, const uint8_t* row_flags, int order, uint64_t* sums,
+                                          uint8_t* pred, uint64_t* hsum, double* entropy, double* scores,
+                                          uint64_t* keys, dal_stream_t stream) {
+  const bool args_ok = x && inner && leaf_id && leaf_q && leaf_h && scores && keys &&
+                       (order == DAL_ASCENDING || order == DAL_DESCENDING);
+  if (const int rc = soft_validate(args_ok, n, d, x_stride, n_leaves, n_trees, depth, n_classes, false)) return rc;
+  if (n == 0) return DAL_OK;
+  const SoftBaldArgs A{{x, n, static_cast<int>(d), x_stride, reinterpret_cast<const int2*>(inner), leaf_id, leaf_q,
+                        static_cast<int>(n_leaves), n_trees, depth, n_classes, DAL_SOFT_ENTROPY, row_flags, order,
+                        reinterpret_cast<unsigned long long*>(sums), pred, scores, keys},
+                       leaf_h, reinterpret_cast<unsigned long long*>(hsum), entropy};
+  const hipStream_t st = as_stream(stream);
+  return dispatch_soft_width(n_classes, [&](auto w) {
+    return soft_launch<decltype(w)::value, false, false, true>(A, d, x_stride, st);
+  });
 }

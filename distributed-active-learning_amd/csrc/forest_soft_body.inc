@@ -3,12 +3,15 @@
 // forest_soft_dw_kernel<W, X_LDS, F_LDS, PERSIST, POW>: one text, two kernels
 // (the way forest_multi_body.inc serves the hard-vote kernels; the uncertainty
 // kernel keeps its name, its argument struct and its instructions).  In scope:
-// W, X_LDS, F_LDS, PERSIST, DW, POW and the kernel's parameters A, R, tpr,
-// x_floats, vec4, pad4, dma, n_tiles.
+// W, X_LDS, F_LDS, PERSIST, DW, POW, BALD and the kernel's parameters A, R,
+// tpr, x_floats, vec4, pad4, dma, n_tiles.
 //
 // DW (A is a SoftDwArgs): the row leader's density word is loaded with its
 // flags, once per tile; the first thread of the grid zeroes A.status_reset
 // (dal_dw_step_soft's DAL_STEP_RESET_STATUS).
+//
+// BALD (A is a SoftBaldArgs): a leaf's LDS row is round2(C + 1) words, the
+// entropy word A.leaf_h[l] at column C.
   static_assert(!PERSIST || X_LDS, "the persistent form stages rows by LDS-DMA");
   soft_reset_status<DW>(A);
   if (PERSIST) {
@@ -32,12 +35,12 @@
     const size_t q_off = static_cast<size_t>(
         round_up(static_cast<int64_t>(x_floats) * 4 + static_cast<int64_t>(A.n_trees) * (n_inner * 8 + n_leaf * 4), 16));
     uint32_t* qs = reinterpret_cast<uint32_t*>(smem + q_off);
-    qstride = soft_lds_stride(A.n_classes);
+    qstride = soft_lds_row<BALD>(A.n_classes);
     for (int e = tid; e < A.n_trees * n_inner; e += kSoftThreads) fs[e] = A.inner[e];
     for (int e = tid; e < A.n_trees * n_leaf; e += kSoftThreads) ls[e] = A.leaf_id[e];
     for (int e = tid; e < A.n_leaves * qstride; e += kSoftThreads) {
       const int l = e / qstride, c = e - l * qstride;
-      qs[e] = c < A.n_classes ? A.leaf_q[l * A.n_classes + c] : 0u;
+      qs[e] = soft_lds_word<BALD>(A, l, c);
     }
     inner = fs;
     leaf_id = ls;
@@ -108,8 +111,8 @@
       }
     }
     __syncthreads();
-    score_tile_soft<W, X_LDS, F_LDS, DW, POW>(A, xs, xstride, tile, R, tpr, inner, leaf_id, leaf_q, qstride, fl_pre,
-                                              dens_pre);
+    score_tile_soft<W, X_LDS, F_LDS, DW, POW, BALD>(A, xs, xstride, tile, R, tpr, inner, leaf_id, leaf_q, qstride,
+                                                    fl_pre, dens_pre, soft_leaf_h<BALD>(A));
     if (!PERSIST) break;
     __syncthreads();  // every wave done with the tile before the next one is staged
   }

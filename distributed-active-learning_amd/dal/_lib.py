@@ -68,6 +68,7 @@ DAL_SOFT_ONE = 1 << 31
 DAL_SOFT_LEAST_CONFIDENCE = 0
 DAL_SOFT_MARGIN = 1
 DAL_SOFT_ENTROPY = 2
+DAL_SOFT_ENTROPY_SHIFT = 29
 
 
 def kcenter_record_bytes(d: int) -> int:
@@ -162,6 +163,9 @@ SIGNATURES = {
                                          c_int32, c_int32, c_int32, c_void_p, c_int, c_double, c_void_p, c_double,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
+    "dal_forest_score_soft_bald": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dal_dw_step_soft": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                  c_int32, c_int32, c_int32, c_void_p, c_double, c_void_p, c_double, c_int64,
                                  c_void_p, c_void_p, c_int64, c_int64, c_int32, ctypes.c_uint32, c_void_p, c_size_t,

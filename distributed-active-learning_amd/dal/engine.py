@@ -74,14 +74,20 @@ class Selection:
     sums            int64 [U, C]: the exact class sums S_c of every unlabeled
                     row (a soft-vote step, soft_step; None otherwise);
                     ``proba()`` gives them over M = T 2^31 as fp64
+    entropy         fp64 [U]: the consensus entropy H(pbar) of every unlabeled
+                    row (a soft-vote step with strategy="bald"; None otherwise)
+    hsum            int64 [U]: the exact sum of the reached leaves' entropy
+                    words (strategy="bald"; None otherwise); the score is
+                    max(entropy - hsum / (T 2^29), +0.0)
 
-    ``scores`` / ``votes`` / ``counts`` / ``sums`` may be given as (per-row tensor, positions): they are
+    ``scores`` / ``votes`` / ``counts`` / ``sums`` / ``entropy`` / ``hsum`` may be given as (per-row tensor, positions): they are
     gathered into unlabeled order on first access (the per-row arrays are
     complete in HBM when the step returns; the gather is only a re-layout, so
     a caller that reads just the selection pays no extra launches).
     """
 
-    def __init__(self, scores, indices, selected_scores, votes=None, counts=None, sums=None, denominator=None):
+    def __init__(self, scores, indices, selected_scores, votes=None, counts=None, sums=None, denominator=None,
+                 entropy=None, hsum=None):
         self._scores = scores
         self.indices = indices
         self.selected_scores = selected_scores
@@ -89,6 +95,8 @@ class Selection:
         self._counts = counts
         self._sums = sums
         self.denominator = denominator  # M = T 2^31 of a soft-vote step
+        self._entropy = entropy
+        self._hsum = hsum
 
     @staticmethod
     def _gathered(v):
@@ -117,6 +125,16 @@ class Selection:
         self._sums = self._gathered(self._sums)
         return self._sums
 
+    @property
+    def entropy(self):
+        self._entropy = self._gathered(self._entropy)
+        return self._entropy
+
+    @property
+    def hsum(self):
+        self._hsum = self._gathered(self._hsum)
+        return self._hsum
+
     def proba(self):
         """fp64 [U, C]: the averaged class probabilities of a soft-vote step,
         (double)S_c / (double)M, one IEEE division per entry."""
@@ -131,6 +149,8 @@ class Selection:
         self._votes = self._gathered(self._votes)
         self._counts = self._gathered(self._counts)
         self._sums = self._gathered(self._sums)
+        self._entropy = self._gathered(self._entropy)
+        self._hsum = self._gathered(self._hsum)
 
     def __iter__(self):
         """Unpacks as the reference-shaped triple (scores, indices, selected_scores)."""
@@ -919,6 +939,31 @@ def forest_score_soft(state: PoolState, forest, flags, order: int, kind: int):
     return sums, pred, scores, keys
 
 
+def forest_score_soft_bald(state: PoolState, forest, flags, order: int = DAL_DESCENDING):
+    """Launch dal_forest_score_soft_bald over the shard: the trees'
+    disagreement H(pbar) - (1/T) sum_t H(p_t) of a ProbabilityForest (BALD, the
+    mean KL divergence to the consensus), on the forest's own leaf entropy
+    words (``forest.leaf_h``).  Returns (sums int64 [n, C], pred uint8 [n],
+    hsum int64 [n], entropy fp64 [n] -- dal_forest_score_soft's entropy, the
+    same bits --, scores, keys).  flags None: every row is a candidate."""
+    torch = _torch()
+    forest.check_features(state.d)
+    inner, leaf_id, leaf_q = forest.device(state.device)  # (checks the limits and the leaf ids before the upload)
+    leaf_h = forest.device_leaf_h(state.device)
+    dev = state.device
+    n, C = state.n, int(forest.n_classes)
+    sums = torch.empty((n, C), dtype=torch.int64, device=dev)
+    pred = torch.empty(n, dtype=torch.uint8, device=dev)
+    hsum = torch.empty(n, dtype=torch.int64, device=dev)
+    entropy = torch.empty(n, dtype=torch.float64, device=dev)
+    scores = torch.empty(n, dtype=torch.float64, device=dev)
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    call("dal_forest_score_soft_bald", _ptr(state.x), n, state.d, state.d, _ptr(inner), _ptr(leaf_id), _ptr(leaf_q),
+         _ptr(leaf_h), forest.n_leaves, forest.n_trees, int(forest.depth), C, 0 if flags is None else _ptr(flags),
+         int(order), _ptr(sums), _ptr(pred), _ptr(hsum), _ptr(entropy), _ptr(scores), _ptr(keys), _stream(dev))
+    return sums, pred, hsum, entropy, scores, keys
+
+
 def forest_score_soft_dw(state: PoolState, forest, flags, density, density_kind: int, density_err: float = 0.0,
                          beta: float = 1.0, want_hi: bool = True):
     """Launch dal_forest_score_soft_dw over the shard: the soft-vote class
@@ -1289,20 +1334,27 @@ def soft_step(state: PoolState, unlabeled_idx, forest, k: int, strategy: str = "
     class distributions and the soft-vote score (dal_forest_score_soft), then
     the top-k of the keys.  Scores, indices and selected scores as
     multiclass_step; the Selection carries ``sums`` ([U, C] int64) and
-    ``proba()``; ``votes`` and ``counts`` are None."""
-    if strategy not in SOFT_KINDS:
-        raise ValueError(f"strategy must be one of {tuple(SOFT_KINDS)}")
+    ``proba()``; ``votes`` and ``counts`` are None.  strategy="bald": the
+    trees' disagreement (dal_forest_score_soft_bald), descending; the
+    Selection also carries ``entropy`` (fp64 [U]) and ``hsum`` (int64 [U])."""
+    if strategy not in SOFT_KINDS and strategy != "bald":
+        raise ValueError(f"strategy must be one of {tuple(SOFT_KINDS) + ('bald',)}")
     flags, unl, n_cand = state.row_flags(unlabeled_idx)
     if n_cand == 0:
         raise ValueError("unlabeled set is empty (the reference loop breaks here)")
     kk = min(int(k), n_cand)
     loc = state.local_positions(unl)
-    order = DAL_ASCENDING if MULTICLASS_ASCENDING[strategy] else DAL_DESCENDING
-    sums, _, scores, keys = forest_score_soft(state, forest, flags, order, SOFT_KINDS[strategy])
+    entropy = hsum = None
+    if strategy == "bald":
+        sums, _, hsum, entropy, scores, keys = forest_score_soft_bald(state, forest, flags, DAL_DESCENDING)
+        entropy, hsum = (entropy, loc), (hsum, loc)
+    else:
+        order = DAL_ASCENDING if MULTICLASS_ASCENDING[strategy] else DAL_DESCENDING
+        sums, _, scores, keys = forest_score_soft(state, forest, flags, order, SOFT_KINDS[strategy])
     idx, _ = topk_keys(keys, kk, state.row_base)
     sel_scores = scores[idx - state.row_base]
     return Selection(scores=(scores, loc), indices=idx, selected_scores=sel_scores, sums=(sums, loc),
-                     denominator=forest.denominator)
+                     denominator=forest.denominator, entropy=entropy, hsum=hsum)
 
 
 def soft_density_step(state: PoolState, unlabeled_idx, forest, k: int, beta: float = 1.0, density_fixed=None,

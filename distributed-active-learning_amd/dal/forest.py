@@ -24,12 +24,13 @@ side -- parity unpinned for such data: no reference-held model covers it).
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (DAL_MAX_TREE_DEPTH, DAL_MC_MAX_CLASSES, DAL_REG_MAX_DEPTH, DAL_SOFT_MAX_CLASSES,
-                   DAL_SOFT_MAX_DEPTH, DAL_SOFT_MAX_TREES, DAL_SOFT_ONE)
+from ._lib import (DAL_MAX_TREE_DEPTH, DAL_MC_MAX_CLASSES, DAL_REG_MAX_DEPTH, DAL_SOFT_ENTROPY_SHIFT,
+                   DAL_SOFT_MAX_CLASSES, DAL_SOFT_MAX_DEPTH, DAL_SOFT_MAX_TREES, DAL_SOFT_ONE)
 
 _POS_INF_BITS = np.array([np.inf], dtype=np.float32).view(np.int32)[0]
 
@@ -556,6 +557,30 @@ def quantize_distribution(distribution) -> np.ndarray:
     return q.astype(np.uint32)
 
 
+def leaf_entropy_words(leaf_q) -> np.ndarray:
+    """uint32 [L]: rint(H_l 2^29) of leaf words ``leaf_q`` [L, C] -- the
+    entropy of the leaf's own fixed-point distribution, on Python floats in
+    class order: e = 0.0; e = e + h(float(q) / 2.0**31), h(p) = (-p) log2(p),
+    h(0) = +0.0; rounding half to even.  H_l <= log2(32) = 5, so a word is
+    below 2^32 and a row's sum of at most 255 of them below 2^41."""
+    q = np.asarray(leaf_q)
+    if q.ndim != 2 or q.shape[1] > DAL_SOFT_MAX_CLASSES:
+        raise ValueError(f"leaf_q must be [L, C] with C <= {DAL_SOFT_MAX_CLASSES}")
+    one = 2.0 ** 31
+    scale = float(1 << DAL_SOFT_ENTROPY_SHIFT)
+    out = np.empty(q.shape[0], dtype=np.uint32)
+    for l, row in enumerate(q.tolist()):
+        e = 0.0
+        for w in row:
+            p = float(w) / one
+            e = e + (0.0 if p == 0.0 else (-p) * math.log2(p))
+        word = round(e * scale)  # (round(): half to even)
+        if not 0 <= word < (1 << 32):
+            raise ValueError("a leaf's entropy word leaves 32 bits: its words are no distribution")
+        out[l] = word
+    return out
+
+
 @dataclass
 class ProbabilityForest:
     """A forest of soft-voting trees: a leaf contributes its class distribution
@@ -566,6 +591,9 @@ class ProbabilityForest:
       leaf_id  int32  [T, 2^D]         row of ``leaf_q`` of every heap leaf (a
                                        shallow leaf's id repeated over its subtree)
       leaf_q   uint32 [L, C]           rint(p 2^31) per class (quantize_distribution)
+      leaf_h   uint32 [L]              rint(H_l 2^29), the entropy of the leaf's own
+                                       words (leaf_entropy_words; computed on first
+                                       use, dal_forest_score_soft_bald's fourth table)
     1 <= T <= 255, 2 <= C <= 32, D <= DAL_SOFT_MAX_DEPTH.  A row's class sums
     S_c = sum_t leaf_q[leaf_id[t, leaf_t(x)], c] are exact integers and the
     averaged probability is S_c / (T 2^31)."""
@@ -604,6 +632,29 @@ class ProbabilityForest:
             raise ValueError(f"a leaf id lies outside the leaf table's {self.n_leaves} rows")
         if int(self.leaf_q.max()) > DAL_SOFT_ONE:
             raise ValueError("a leaf word exceeds 2^31")
+        h = self._dev.get("leaf_h")
+        if h is not None and (h.dtype != np.uint32 or h.shape != (self.n_leaves,)):
+            raise ValueError(f"leaf_h must be uint32 [{self.n_leaves}], one entropy word per leaf")
+
+    @property
+    def leaf_h(self) -> np.ndarray:
+        """uint32 [L]: every leaf's entropy word rint(H_l 2^29)
+        (leaf_entropy_words of leaf_q), computed once on the host."""
+        if "leaf_h" not in self._dev:
+            self._dev["leaf_h"] = leaf_entropy_words(self.leaf_q)
+        return self._dev["leaf_h"]
+
+    def device_leaf_h(self, device):
+        """leaf_h as a device tensor (its int32 bit pattern), uploaded once per
+        device on first use; ``device()`` keeps returning its three tables."""
+        import torch
+
+        key = ("leaf_h", str(device))
+        if key not in self._dev:
+            h = self.leaf_h
+            self.check()
+            self._dev[key] = torch.from_numpy(np.ascontiguousarray(h, dtype=np.uint32).view(np.int32)).to(device)
+        return self._dev[key]
 
     def check_features(self, d: int):
         """Raise unless every inner node tests a feature in [0, d)."""

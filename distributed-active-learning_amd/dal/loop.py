@@ -108,7 +108,10 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     density_weighting.select_multiclass), "soft_information_density"
     (entropy(predict_proba) x density over the averaged leaf class
     distributions, E = L0; density_weighting.select_soft: soft votes, below,
-    for any label count), "lal" (ActiveLearnerLAL.selectNext,
+    for any label count), "bald" (the trees' disagreement H(pbar) - mean_t
+    H(p_t) over the leaf class distributions, the mean KL divergence to the
+    consensus: dal.uncertainty_sampling.select(strategy="bald"); soft votes,
+    below, for any label count), "lal" (ActiveLearnerLAL.selectNext,
     lal_direct_mllib_implementation/classes/active_learner.py:240-343:
     dal.active_learner.select_lal with ``lal_model``, a
     dal.forest.RegressionForest over the five LAL features; binary only; the
@@ -172,11 +175,12 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
     strategy raises ValueError.  False, the default, makes the calls it made.
     strategy="soft_information_density" scores soft votes by definition: it
     needs the same trainers, raises the same error for trainer="gpu", and
-    accepts soft_votes=True as redundant.
+    accepts soft_votes=True as redundant.  So does strategy="bald".
     """
     soft_density = strategy == "soft_information_density"  # (soft votes by its definition: the flag is redundant)
-    if soft_votes or soft_density:
-        if not soft_density and strategy not in ("uncertainty", "ranked_batch"):
+    bald = strategy == "bald"  # (likewise)
+    if soft_votes or soft_density or bald:
+        if not (soft_density or bald) and strategy not in ("uncertainty", "ranked_batch"):
             raise ValueError(f"soft_votes=True belongs to strategy 'uncertainty' or 'ranked_batch': {strategy!r} "
                              "scores hard votes")
         if trainer == "gpu":
@@ -287,7 +291,7 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
         elif select_fn is not None:
             chosen = np.asarray(select_fn(strategy, X, unlabeled, rf, k))
         else:
-            if soft_votes or soft_density:
+            if soft_votes or soft_density or bald:
                 from .forest import ProbabilityForest
 
                 if isinstance(rf, (GpuForestModel, Forest)):
@@ -301,6 +305,9 @@ def run_loop(X, y, X_test=None, y_test=None, strategy: str = "uncertainty",
             if strategy == "uncertainty":
                 from .uncertainty_sampling import select
                 sel = select(state, unlabeled, forest, k)
+            elif bald:
+                from .uncertainty_sampling import select
+                sel = select(state, unlabeled, forest, k, strategy="bald")
             elif strategy == "ranked_batch":
                 from .uncertainty_sampling import select_batch
                 sel = select_batch(state, unlabeled, lab, forest, k, alpha=alpha, sim_pool=sim_pool)

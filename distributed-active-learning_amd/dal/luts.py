@@ -101,13 +101,15 @@ def batch_weights_multiclass(strategy: str, scores, n_classes: int):
     (numpy array or torch tensor; dal.engine.multiclass_step's ``scores``),
     one fp64 operation per row: least_confidence 1 - maxp, margin 1 - margin,
     entropy H / log2(C) with the module's log(x)/log(2), then capped at 1 (the
-    uniform vote's quotient can round one ulp above)."""
+    uniform vote's quotient can round one ulp above).  "bald" (soft votes: the
+    trees' disagreement, dal.engine.soft_step) takes the entropy rule: BALD <=
+    H(pbar) <= log2(C)."""
     C = int(n_classes)
     if C < 2:
         raise ValueError("n_classes must be >= 2")
     if strategy in ("least_confidence", "margin"):
         return 1.0 - scores
-    if strategy != "entropy":
+    if strategy not in ("entropy", "bald"):
         raise ValueError(f"unknown strategy {strategy!r}; expected one of {STRATEGIES}")
     if isinstance(scores, np.ndarray):
         return (scores / _log2(C)).clip(max=1.0)

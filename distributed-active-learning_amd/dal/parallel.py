@@ -54,13 +54,16 @@ SOFT_DENSITY_MODES = ("dw_soft",)
 ALL_DENSITY_MODES = DENSITY_MODES + SOFT_DENSITY_MODES
 
 
-def _soft_forest(forest, mode: str) -> bool:
+def _soft_forest(forest, mode: str, strategy: str = None) -> bool:
     """True for a dal.forest.ProbabilityForest (soft votes), which modes "us"
     and "dw_soft" alone score; any other mode raises ValueError, before any
     work -- as does mode "dw_soft" for a hard-voting Forest."""
     from .forest import ProbabilityForest
 
     soft = isinstance(forest, ProbabilityForest)
+    if strategy == "bald" and mode == "us" and not soft:
+        raise ValueError("strategy='bald' (the trees' disagreement) needs a ProbabilityForest (soft votes): a "
+                         "hard-voting Forest keeps no leaf distributions")
     if soft and mode != "us" and mode not in SOFT_DENSITY_MODES:
         raise ValueError(f"a ProbabilityForest (soft votes) is scored by mode='us' or mode='dw_soft' only: "
                          f"mode={mode!r} has no soft-vote form (the hard-vote density-weighted and LAL scores take "
@@ -350,6 +353,9 @@ class ShardedSelector:
         distributions x density: a dal.forest.ProbabilityForest alone, through
         dal_dw_step_soft).  A ProbabilityForest (soft votes) is scored by
         modes "us" and "dw_soft" alone; every other mode raises ValueError.
+        Mode "us" over such a forest also takes strategy="bald" (the trees'
+        disagreement, dal_forest_score_soft_bald; a row's score does not
+        depend on the shard, so the merge is the same).
         ``warm``: the density was cached
         before this step (the score kernel then reads the shard's blocked
         copy, as the single-GPU warm step does; a cold step keeps the
@@ -359,7 +365,7 @@ class ShardedSelector:
         from .luts import ASCENDING
 
         st = self.state
-        soft = _soft_forest(forest, mode)
+        soft = _soft_forest(forest, mode, strategy)
         if mode == "dw" and forest.n_classes > 2:
             raise ValueError(f"density weighting is binary only: the forest has {forest.n_classes} classes")
         if st.n == 0:
@@ -440,11 +446,14 @@ class ShardedSelector:
                     i, s, kk_keys = dw_select_local(st, flags, rix, klo, khi, ent, kk, beta, colsum,
                                                     cap_scale=self.cap_scale, sync=False)
         elif soft:  # soft votes: the averaged leaf distributions, the same merge
-            from .engine import SOFT_KINDS, forest_score_soft
+            from .engine import SOFT_KINDS, forest_score_soft, forest_score_soft_bald
             from .luts import MULTICLASS_ASCENDING
 
-            order = DAL_ASCENDING if MULTICLASS_ASCENDING[strategy] else DAL_DESCENDING
-            _, _, sc, kys = forest_score_soft(st, forest, flags, order, SOFT_KINDS[strategy])
+            if strategy == "bald":  # the trees' disagreement: a row's score does not depend on the shard
+                _, _, _, _, sc, kys = forest_score_soft_bald(st, forest, flags, DAL_DESCENDING)
+            else:
+                order = DAL_ASCENDING if MULTICLASS_ASCENDING[strategy] else DAL_DESCENDING
+                _, _, sc, kys = forest_score_soft(st, forest, flags, order, SOFT_KINDS[strategy])
             i, kk_keys = topk_keys(kys, kk, st.row_base)
             s = sc[i - st.row_base]
         elif forest.n_classes > 2:  # multiclass uncertainty: the C-class kernel, the same merge
@@ -647,7 +656,7 @@ def _select(sels, ops, unlabeled_idx, forest, k, mode, strategy, beta, sort_fn, 
     """select over the jobs ``sels`` (one rank's selector, or P emulated
     shards) with the collectives ``ops``: one (indices, scores) per job.  Every
     decision is taken from values that are the same on every rank."""
-    _soft_forest(forest, mode)
+    _soft_forest(forest, mode, strategy)
     unls = [s.index_tensor(unlabeled_idx) for s in sels]
     u_fulls = parts_fulls = [None] * len(sels)
     warm = [s._density is not None for s in sels]  # (a cold step's score kernel keeps the row-major pool)

@@ -17,6 +17,17 @@ from .forest import Forest, ProbabilityForest
 from .luts import STRATEGIES
 
 
+def _check_strategy(strategy: str, forest):
+    """The three strategies, and "bald" for a ProbabilityForest alone (a
+    hard-voting Forest keeps no leaf distributions); before any work."""
+    if strategy == "bald":
+        if not isinstance(forest, ProbabilityForest):
+            raise ValueError("strategy='bald' (the trees' disagreement) needs a ProbabilityForest (soft votes): a "
+                             "hard-voting Forest keeps no leaf distributions")
+    elif strategy not in STRATEGIES:
+        raise ValueError(f"strategy must be one of {STRATEGIES}")
+
+
 def select(pool, unlabeled_idx, forest: Forest, k: int, strategy: str = "least_confidence",
            device=None) -> Selection:
     """Score every unlabeled row and select the k most uncertain.
@@ -37,10 +48,13 @@ def select(pool, unlabeled_idx, forest: Forest, k: int, strategy: str = "least_c
     distributions, scikit-learn's ``predict_proba``) is scored by the same
     three strategies on the averaged probabilities, exactly
     (dal.engine.soft_step): the Selection then carries ``sums`` [U, C] and
-    ``proba()``; ``votes`` and ``counts`` are None.
+    ``proba()``; ``votes`` and ``counts`` are None.  Such a forest alone also
+    takes strategy "bald": the trees' disagreement H(pbar) - mean_t H(p_t)
+    (the mean KL divergence to the consensus; query by committee), largest
+    first, with ``entropy`` [U] and ``hsum`` [U] beside the sums.  A
+    hard-voting Forest raises ValueError for it.
     """
-    if strategy not in STRATEGIES:
-        raise ValueError(f"strategy must be one of {STRATEGIES}")
+    _check_strategy(strategy, forest)
     state = as_pool_state(pool, device=device)
     if isinstance(forest, ProbabilityForest):
         return soft_step(state, unlabeled_idx, forest, k, strategy)
@@ -61,7 +75,8 @@ def select_batch(pool, unlabeled_idx, labeled_idx, forest: Forest, k: int, strat
     the score entries ``select`` uses.  Weights in [0, 1], higher = more
     uncertain: binary, dal.luts.batch_weight_lut(strategy, T) gathered by the
     votes; multiclass and soft votes (a ProbabilityForest),
-    dal.luts.batch_weights_multiclass of the scores.  They
+    dal.luts.batch_weights_multiclass of the scores ("bald", a
+    ProbabilityForest only: score / log2(C) capped at 1, the entropy rule).  They
     are scattered to pool rows on the device; the candidates are the unlabeled
     rows, the comparison set starts as ``labeled_idx`` (at least one row).
 
@@ -80,8 +95,7 @@ def select_batch(pool, unlabeled_idx, labeled_idx, forest: Forest, k: int, strat
     from .engine import _as_index
     from .similarity import _bf16_pool, ranked_batch_select
 
-    if strategy not in STRATEGIES:
-        raise ValueError(f"strategy must be one of {STRATEGIES}")
+    _check_strategy(strategy, forest)
     state = as_pool_state(pool, device=device)
     if state.row_base or state.n_total != state.n:
         raise ValueError("select_batch needs the whole pool, not a row shard")
@@ -106,7 +120,7 @@ def select_batch(pool, unlabeled_idx, labeled_idx, forest: Forest, k: int, strat
     ranked = ranked_batch_select(simx, labeled_idx, weights, k, alpha=alpha, candidates=unl, device=dev)
     sel = Selection(scores=ranked.scores, indices=ranked.indices, selected_scores=ranked.selected_scores,
                     votes=scored._votes, counts=scored._counts, sums=scored._sums,
-                    denominator=scored.denominator)
+                    denominator=scored.denominator, entropy=scored._entropy, hsum=scored._hsum)
     sel.selected_similarity = ranked.selected_similarity
     sel.weights = w_unl
     return sel

@@ -601,6 +601,43 @@ int dal_forest_score_soft_dw(const float* x, int64_t n, int64_t d, int64_t x_str
                              uint8_t* pred, double* entropy, int32_t* row_index, double* scores, uint64_t* keys,
                              uint64_t* keys_hi, dal_stream_t stream);
 
+/* ---- soft votes: BALD, the trees' mutual information ----------------------
+ * Query by committee on the leaf distributions: the mean KL divergence of the
+ * trees' distributions p_t to their average,
+ *   (1/T) sum_t KL(p_t || pbar) = H(pbar) - (1/T) sum_t H(p_t)
+ * (BALD; the committee's Jensen-Shannon divergence; modAL's KL disagreement).
+ * A new symbol only: dal_abi_version() stays 10, and a caller probes for the
+ * symbol (absent from older libraries).  Forest, x_stride, sums, pred, keys
+ * and the candidates' DAL_KEY_NONE as dal_forest_score_soft.
+ *
+ * leaf_h (uint32 [n_leaves]) holds every leaf's entropy in fixed point,
+ *   leaf_h[l] = rint(H_l 2^DAL_SOFT_ENTROPY_SHIFT),
+ *   H_l = ((0.0 + h(q[l][0] / 2^31)) + h(q[l][1] / 2^31)) + ..., h as above
+ * (H_l <= log2(32) = 5 and 5 2^29 < 2^32; dal.forest.ProbabilityForest.leaf_h
+ * computes the words on the host).  The call is defined on the words it is
+ * given:
+ *   hsum[i]    = sum_t leaf_h[leaf_id[t][leaf_t(x_i)]]    exact, < 2^41 (nullable)
+ *   entropy[i] = dal_forest_score_soft(DAL_SOFT_ENTROPY)'s scores[i], the same
+ *                bits (nullable)
+ *   g          = (double)hsum[i] / (double)(n_trees 2^29), one IEEE division of
+ *                two exactly representable integers
+ *   b          = entropy[i] - g, one rounding, no FMA
+ *   scores[i]  = b > 0 ? b : +0.0     never negative, -0.0 or NaN
+ * In real arithmetic b >= 0 (-p log p is concave); the clamp removes what the
+ * 2^-30 word rounding and the fp64 log2 can push below zero.  scores are
+ * within (n_classes + 1) 2^-49 of the host's evaluation of the same words.
+ * ``order`` keys the scores (DAL_DESCENDING selects the largest disagreement).
+ * Before any device call: a null x, inner, leaf_id, leaf_q, leaf_h, scores or
+ * keys, or a bad order, is DAL_ERR_ARG; then dal_forest_score_soft's
+ * DAL_ERR_SHAPE and DAL_ERR_UNSUPPORTED conditions, in its order.  n == 0
+ * returns DAL_OK and launches nothing. */
+#define DAL_SOFT_ENTROPY_SHIFT 29
+int dal_forest_score_soft_bald(const float* x, int64_t n, int64_t d, int64_t x_stride, const int32_t* inner,
+                               const int32_t* leaf_id, const uint32_t* leaf_q, const uint32_t* leaf_h,
+                               int64_t n_leaves, int32_t n_trees, int32_t depth, int32_t n_classes,
+                               const uint8_t* row_flags, int order, uint64_t* sums, uint8_t* pred, uint64_t* hsum,
+                               double* entropy, double* scores, uint64_t* keys, dal_stream_t stream);
+
 /* ---- (a11) top-k: sortBy(score).take(k) --------------------------------
  * Replaces uncertainty_sampling.py:106,109 / density_weighting.py:168,172.
  * The k smallest keys, ties -> lower index; out_idx = idx_base + row, sorted
